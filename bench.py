@@ -2,11 +2,15 @@
 """Throughput of the GEDepth training hot path on MI355X (BASELINE.json metric: training img/s, KITTI 352x1120).
 
     python bench.py --gpus 1 --steps K --warmup W            (N>1: launched by torch.distributed.run, one rank/GPU)
+    python bench.py --gpus 1 --steps K --warmup W --full     (+ the secondary measurements below)
+    python bench.py ... --dump-outputs DIR                   (+ what the last timed step computed, as DIR/<name>.npy)
 
 A step = forward (DepthFormer Swin encoder + HAHI neck + ground embedding + DenseDepth head) + SiLog(+CE) loss +
 backward + gradient all-reduce (N>1) + grad-clip + AdamW on one synthetic KITTI-shaped batch that is already
-resident in HBM.  Prints ONE JSON line (rank 0) with the whole-job img/s, the roofline of the dominant hand-written
-kernel (HIP-event timed inside the timed region) and, at N=1, the CPU oracle timed on the host cores.
+resident in HBM.  Prints ONE JSON line (rank 0) with the whole-job img/s and ms per timed step.  A plain run does
+only that: set up, warm up, time --steps steps, dump outputs if asked, print.  --full adds the H2D-inclusive pass,
+the per-bucket gradient-exchange trace (N>1), the roofline of the dominant hand-written kernel (HIP events, a
+separate pass), the fp32 leg and, at N=1, the CPU oracle timed on the host cores.
 """
 import argparse
 import json
@@ -50,11 +54,17 @@ def parse():
                          'device is the bound anyway (8 images per GPU: 49.3 ms either way)')
     ap.add_argument('--layout', default='nhwc', choices=['nchw', 'nhwc'],
                     help='nhwc: channels-last conv stack (depth.models.utils.to_channels_last): no MIOpen layout transposes, tokens <-> maps are views')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-h2d', action='store_true', help='skip the extra pass that feeds the batch from pinned host memory every step')
-    ap.add_argument('--no-kernel-timing', action='store_true', help='skip the second (HIP-event profiled) pass')
-    ap.add_argument('--profile-steps', type=int, default=5, help='steps of the separate per-kernel timing pass')
-    ap.add_argument('--no-fp32', action='store_true', help='skip the extra reference-precision (fp32) measurement at N=1')
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline also run the secondary measurements: H2D-inclusive pass, gradient-exchange trace (N>1), '
+                         'per-kernel timing pass (roofline), fp32 leg and CPU oracle baseline (N=1); each can be left out with its --no-* flag')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed step computed (losses; a fixed, seeded sample of the updated parameters and of '
+                         'their gradients) as DIR/<name>.npy, float32 / float64; that step starts from the run\'s initial state')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full: skip the CPU oracle baseline')
+    ap.add_argument('--no-h2d', action='store_true', help='--full: skip the extra pass that feeds the batch from pinned host memory every step')
+    ap.add_argument('--no-kernel-timing', action='store_true', help='--full: skip the second (HIP-event profiled) pass')
+    ap.add_argument('--profile-steps', type=int, default=5, help='steps of the separate per-kernel timing pass (--full)')
+    ap.add_argument('--no-fp32', action='store_true', help='--full: skip the extra reference-precision (fp32) measurement at N=1')
     ap.add_argument('--fp32-steps', type=int, default=5)
     ap.add_argument('--gemm-tuning', default='load', choices=['off', 'load', 'tune'],
                     help='hipBLASLt/rocBLAS solution table for the Linear layers (gedepth_amd/mmrt/tuning.py)')
@@ -212,6 +222,7 @@ def build_job(args, cfg, dev, rank, dtype, graph=True):
             return gstep(b)
         step.graphed = gstep
     step.eager = eager_step
+    step.model = model
     step.batch = batch
     step.ddp = ddp
     return step, per_gpu, optimizer
@@ -274,12 +285,20 @@ def fence():
     torch.cuda.synchronize()
 
 
-def timed_steps(step, warmup, steps, dev, world):
+def timed_steps(step, warmup, steps, dev, world, before_last=None):
+    """``before_last``: called between the last two timed steps with the clock stopped (both sides fenced), so that it costs the
+    measurement nothing."""
     for _ in range(warmup):
         out = step()
     fence()
     t0 = time.perf_counter()
-    for _ in range(steps):
+    for i in range(steps):
+        if before_last is not None and i == steps - 1:
+            fence()
+            paused = time.perf_counter()
+            before_last()
+            fence()
+            t0 += time.perf_counter() - paused
         out = step()
     fence()
     elapsed = time.perf_counter() - t0
@@ -287,6 +306,63 @@ def timed_steps(step, warmup, steps, dev, world):
     if world > 1:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     return t.item(), out
+
+
+def snapshot_state(model, optimizer):
+    """The training state a run starts from, kept on the device: parameters and buffers by name, the optimizer's moments per parameter
+    and its step counter (the optimizer's own state_dict, which follows any later re-ordering of its arena)."""
+    return {k: v.detach().clone() for k, v in model.state_dict().items()}, optimizer.state_dict()
+
+
+@torch.no_grad()
+def restore_state(model, optimizer, snap):
+    """Put ``snapshot_state``'s state back in place (same storage: a captured hipGraph keeps its addresses) and rebuild the bf16 shadow."""
+    params, opt = snap
+    for k, t in model.state_dict(keep_vars=True).items():
+        t.detach().copy_(params[k])
+    optimizer.load_state_dict(opt)
+    optimizer.arena.refresh_shadow(copy=True)
+
+
+DUMP_SAMPLE = 1 << 22         # elements per sampled array (16 MB as float32)
+DUMP_SEED = 20240601
+
+
+def dump_outputs(path, out, model, optimizer):
+    """What the caller of the timed step receives after the last timed step, as <path>/<name>.npy: the total loss and every
+    logged loss term (float64 scalars), and a fixed, seeded sample of the parameters the step updated and of the gradients
+    it computed, as the optimizer's arena holds them (float32).  The sample is drawn from the parameters concatenated in name order, each flattened in its
+    logical (NCHW) order, so it does not depend on the arena layout or on the memory format of the weights.  The inputs are the
+    same in every run, and so is the state the dumped step starts from: with --dump-outputs the last timed step trains from the run's
+    initial state (restore_state, with the clock stopped), not from the state the earlier steps left.  Those steps reduce with float
+    atomics in no fixed order, and training compounds such rounding differences step after step; one step from a fixed state
+    carries only its own rounding (two runs on one MI355X: losses bit-identical, gradients within 1e-4 of their largest magnitude;
+    a parameter whose exact gradient is zero, such as a bias ahead of a normalisation, gets a rounding-noise gradient, and AdamW's
+    first step moves it by +-lr whatever that noise's size, so such parameters may differ by 2 lr)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, 'loss.npy'), np.asarray(float(out['loss'].detach().float().item()), dtype=np.float64))
+    for k, v in out['log_vars'].items():
+        np.save(os.path.join(path, 'log_vars_' + ''.join(c if c.isalnum() else '_' for c in k) + '.npy'), np.asarray(float(v), dtype=np.float64))
+    params = [p for _, p in sorted(model.named_parameters(), key=lambda kv: kv[0]) if p.requires_grad]
+    n = sum(p.numel() for p in params)
+    k = min(n, DUMP_SAMPLE)
+    stride = n // k
+    rng = np.random.default_rng(DUMP_SEED)
+    idx = torch.from_numpy(np.arange(k, dtype=np.int64) * stride + rng.integers(0, stride, k, dtype=np.int64))
+    idx = idx.to(params[0].device)
+    with torch.no_grad():
+        flat_p = torch.cat([p.detach().reshape(-1).float() for p in params])
+        np.save(os.path.join(path, 'params_sample.npy'), flat_p[idx].cpu().numpy())
+        del flat_p
+        arena = optimizer.arena                        # the gradients the optimizer stepped with (p.grad may be a tensor autograd handed over)
+        grad = {id(p): arena._view(arena.flat_grad, off, p) for p, (off, _) in zip(arena.params, arena.slices())}
+        flat_g = torch.cat([grad[id(p)].reshape(-1).float() for p in params])
+        np.save(os.path.join(path, 'grads_sample.npy'), flat_g[idx].cpu().numpy())
+        del flat_g
+    for k, v in out.get('log_imgs', {}).items():                   # only when the head's log_images is on (not in the shipped configs)
+        a = np.asarray(v.float().numpy() if torch.is_tensor(v) else v, dtype=np.float32).reshape(-1)
+        np.save(os.path.join(path, 'log_imgs_' + k + '.npy'), a[::max(1, a.size // (DUMP_SAMPLE // 8))][:DUMP_SAMPLE // 8])
 
 
 def main():
@@ -319,33 +395,47 @@ def main():
 
     note(f'model built ({args.config}, {args.dtype}); warm-up + timed region')
     kernels.FALLBACKS.clear()
+    # --dump-outputs: the last timed step starts from the initial state, so that what it computes is the same in every run
+    before_last = None
+    if args.dump_outputs:
+        snap = snapshot_state(step.model, optimizer)
+        before_last = lambda: restore_state(step.model, optimizer, snap)       # noqa: E731
     # ---- pass 1: the headline number; the per-kernel event profiler is OFF inside the timed region
-    elapsed, out = timed_steps(step, args.warmup, args.steps, dev, world)
+    elapsed, out = timed_steps(step, args.warmup, args.steps, dev, world, before_last)
+    before_last = snap = None
     loss = out['log_vars']['loss']
-    note(f'timed region done: {1e3 * elapsed / args.steps:.2f} ms/step; H2D-inclusive pass')
-    h2d_elapsed, h2d_bytes = h2d_inclusive(step, args.steps, dev, world) if not args.no_h2d else (None, 0)
-    # ---- gradient exchange: one extra step with per-bucket timing (outside the timed region: the trace synchronises the device)
+    note(f'timed region done: {1e3 * elapsed / args.steps:.2f} ms/step')
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out, step.model, optimizer)
+        note(f'outputs written to {args.dump_outputs}')
+    # ---- everything below the headline runs with --full only
+    h2d_elapsed, h2d_bytes = None, 0
     ddp_info = step.ddp.describe()
-    if ddp_info['active']:
-        step.ddp.trace(True)
-        step.eager()                                         # launched from Python: a graph replay runs no hooks, so there is nothing to stamp
-        fence()
-        step.ddp.trace(False)
-        ddp_info['trace'] = [dict(bucket=r['bucket'], MB=round(r['bytes'] / 2 ** 20, 2), params=r['params'], launch_ms=round(r['launch_ms'], 3),
-                                  done_ms=round(r['done_ms'], 3)) for r in step.ddp.bucket_trace()]
-        ddp_info['note'] = ('ms since the first gradient hook of that step; launch = all-reduce enqueued on RCCL while backward continues, '
-                            'done = wait() returned in finish(); an exchange that hides completes before the last bucket is launched')
-    note('kernel-timing pass')
-    # ---- pass 2: the same steps again with HIP events around every hand-written kernel (roofline object)
     prof, stages = [], []
-    if not args.no_kernel_timing and args.profile_steps > 0:
-        kernels.PROFILER.enable()
-        for _ in range(args.profile_steps):
-            step()
-        fence()
-        kernels.PROFILER.disable()
-        prof = kernels.PROFILER.summary()
-        stages = kernels.PROFILER.msda_bwd_stages()
+    if args.full:
+        if not args.no_h2d:
+            note('H2D-inclusive pass')
+            h2d_elapsed, h2d_bytes = h2d_inclusive(step, args.steps, dev, world)
+        # ---- gradient exchange: one extra step with per-bucket timing (outside the timed region: the trace synchronises the device)
+        if ddp_info['active']:
+            step.ddp.trace(True)
+            step.eager()                                     # launched from Python: a graph replay runs no hooks, so there is nothing to stamp
+            fence()
+            step.ddp.trace(False)
+            ddp_info['trace'] = [dict(bucket=r['bucket'], MB=round(r['bytes'] / 2 ** 20, 2), params=r['params'], launch_ms=round(r['launch_ms'], 3),
+                                      done_ms=round(r['done_ms'], 3)) for r in step.ddp.bucket_trace()]
+            ddp_info['note'] = ('ms since the first gradient hook of that step; launch = all-reduce enqueued on RCCL while backward continues, '
+                                'done = wait() returned in finish(); an exchange that hides completes before the last bucket is launched')
+        # ---- pass 2: the same steps again with HIP events around every hand-written kernel (roofline object)
+        if not args.no_kernel_timing and args.profile_steps > 0:
+            note('kernel-timing pass')
+            kernels.PROFILER.enable()
+            for _ in range(args.profile_steps):
+                step()
+            fence()
+            kernels.PROFILER.disable()
+            prof = kernels.PROFILER.summary()
+            stages = kernels.PROFILER.msda_bwd_stages()
     prof_ms_per_step = sum(r['total_ms'] for r in prof) / max(1, args.profile_steps)
 
     if rank == 0:
@@ -408,7 +498,7 @@ def main():
     torch.cuda.empty_cache()
 
     # ---- reference-precision (fp32, exact-fp32 attention off: library fp32 GEMM/conv + the same HIP kernels) line at N=1
-    if world == 1 and args.dtype != 'fp32' and not args.no_fp32:
+    if args.full and world == 1 and args.dtype != 'fp32' and not args.no_fp32:
         # the committed MIOpen find-db holds the fp32 problems of the DEFAULT workload (tools/tune_tables.py --dtype fp32): find mode
         # resolves them from the db; for any other workload every fp32 convolution would be timed from scratch (minutes), so those
         # use MIOpen's immediate-mode heuristics (GE_FP32_FIND=0 forces that for the default workload too)
@@ -429,7 +519,7 @@ def main():
         del step32, opt32, o32
         torch.cuda.empty_cache()
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             note('cpu baseline (oracle, 1+3 train steps, 1+3 eval)')
             res['cpu_baseline'] = cpu_baseline(args.config, args.height, args.width)
         print(json.dumps(res), file=result_out, flush=True)

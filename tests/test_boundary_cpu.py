@@ -14,7 +14,6 @@ from gedepth_amd.depth.models import MODELS, build_depther
 from gedepth_amd.mmrt.config import Config, DictAction
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = '/root/reference'
 REGISTRY_NAMES = ['DepthEncoderDecoder', 'DepthFormerSwin', 'HAHIHeteroNeck', 'LightPEMASKNeck', 'DynamicPENeckSOFT',
                   'DenseDepthHead', 'SigLoss', 'CrossEntropyLoss', 'BinaryCrossEntropyLoss']
 
@@ -43,22 +42,33 @@ def test_config_inheritance_and_delete():
     assert 'model = dict(' in cfg.pretty_text
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason='reference tree only exists in the build container')
+def _untag(d):
+    return tuple(d['__tuple__']) if set(d) == {'__tuple__'} else d
+
+
+def reference_configs():
+    """The reference's own config files as they resolved, loaded byte-unchanged through our loader (tests/golden/reference_configs.json,
+    written by tests/golden/make_golden_configs.py; tuples kept as tuples)."""
+    with open(os.path.join(ROOT, 'tests', 'golden', 'reference_configs.json')) as fh:
+        return json.load(fh, object_hook=_untag)
+
+
 @pytest.mark.parametrize('name', ['depthformer_v.py', 'depthformer_a.py', 'depthformer_a_ddad.py', 'depthformer_v_ddad.py'])
 def test_reference_configs_load_unchanged_and_resolve_identically(name):
-    """The reference's own config files load byte-unchanged through our loader, and our re-structured
+    """The reference's own config files load byte-unchanged through our loader (recorded in the fixture), and our re-structured
     configs resolve to the same model / optimizer / schedule."""
-    ref = Config.fromfile(os.path.join(REF, 'configs', 'depthformer', name))
-    ours = Config.fromfile(cfg_path(name))
+    ref = reference_configs()[name]
+    ours = Config.fromfile(cfg_path(name)).to_dict()
     for key in ['model', 'optimizer', 'optimizer_config', 'lr_config', 'runner', 'checkpoint_config', 'evaluation',
                 'log_config', 'dist_params', 'workflow', 'data']:
-        assert ref.to_dict()[key] == ours.to_dict()[key], key
+        assert ref[key] == ours[key], key
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason='reference tree only exists in the build container')
 def test_reference_ddad_configs_load():
+    refs = reference_configs()
     for name in ['depthformer_v_ddad.py', 'depthformer_a_ddad.py']:
-        cfg = Config.fromfile(os.path.join(REF, 'configs', 'depthformer', name))
+        assert refs[name]['model']['type'] == 'DepthEncoderDecoder'
+        cfg = Config.fromfile(cfg_path(name))
         assert cfg.model.type == 'DepthEncoderDecoder'
 
 

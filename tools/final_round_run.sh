@@ -6,17 +6,17 @@ OUT=$REPO/gpurun_out/final_$TAG
 mkdir -p $OUT
 ulimit -c 0
 cd $REPO
-python bench.py > $OUT/bench.json 2> $OUT/bench.err
+python bench.py --full > $OUT/bench.json 2> $OUT/bench.err
 head -c 400 $OUT/bench.json; echo
 bash tools/profile_bench.sh $TAG > $OUT/profile.log 2>&1
-python bench.py --config depthformer_a.py --no-cpu-baseline --no-fp32 > $OUT/bench_config3.json 2> /dev/null                       # hipGraph (auto: 2 images per GPU)
-python bench.py --config depthformer_a.py --no-cpu-baseline --no-fp32 --graph off > $OUT/bench_config3_eager.json 2> /dev/null
-python bench.py --config depthformer_a_ddad.py --height 1216 --width 1936 --batch 1 --no-cpu-baseline --no-fp32 > $OUT/bench_config4.json 2> /dev/null
+python bench.py --full --config depthformer_a.py --no-cpu-baseline --no-fp32 > $OUT/bench_config3.json 2> /dev/null                       # hipGraph (auto: 2 images per GPU)
+python bench.py --full --config depthformer_a.py --no-cpu-baseline --no-fp32 --graph off > $OUT/bench_config3_eager.json 2> /dev/null
+python bench.py --full --config depthformer_a_ddad.py --height 1216 --width 1936 --batch 1 --no-cpu-baseline --no-fp32 > $OUT/bench_config4.json 2> /dev/null
 # (config #5, --attn fp8, is a numerics demonstrator since round 6: tested, not benched — DESIGN.md §8.2)
 # gradient exchange forced on one rank: bucket layout in arrival order + per-bucket launch / completion trace
-GE_DDP_FORCE=1 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 1 --no-cpu-baseline --no-fp32 --no-h2d --no-kernel-timing > $OUT/bench_ddp_forced.json 2> /dev/null
-GE_DDP_FORCE=1 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29518 bench.py --gpus 1 --config depthformer_a.py --no-cpu-baseline --no-fp32 --no-h2d --no-kernel-timing > $OUT/bench_ddp_forced_config3.json 2> /dev/null
-GE_GRAPH_DDP=0 GE_DDP_FORCE=1 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29519 bench.py --gpus 1 --config depthformer_a.py --no-cpu-baseline --no-fp32 --no-h2d --no-kernel-timing > $OUT/bench_ddp_forced_config3_eager.json 2> /dev/null
+GE_DDP_FORCE=1 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 1 --full --no-cpu-baseline --no-fp32 --no-h2d --no-kernel-timing > $OUT/bench_ddp_forced.json 2> /dev/null
+GE_DDP_FORCE=1 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29518 bench.py --gpus 1 --full --config depthformer_a.py --no-cpu-baseline --no-fp32 --no-h2d --no-kernel-timing > $OUT/bench_ddp_forced_config3.json 2> /dev/null
+GE_GRAPH_DDP=0 GE_DDP_FORCE=1 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29519 bench.py --gpus 1 --full --config depthformer_a.py --no-cpu-baseline --no-fp32 --no-h2d --no-kernel-timing > $OUT/bench_ddp_forced_config3_eager.json 2> /dev/null
 python tools/library_roofline.py > $OUT/library_roofline.txt 2>&1
 python tools/ubench/aten_sites.py > $OUT/aten_call_sites.txt 2>&1
 CFG=depthformer_a.py python tools/ubench/aten_sites.py > $OUT/aten_call_sites_config3.txt 2>&1

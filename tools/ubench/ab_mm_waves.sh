@@ -1,7 +1,7 @@
 cd ${GRAFT_REPO_ROOT:-/root/repo}
 mkdir -p gpurun_out/mmw
 timeout 300 python -m pytest tests/test_kernels_gpu.py -q -k "msda" > gpurun_out/mmw/t.log 2>&1; tail -2 gpurun_out/mmw/t.log
-ARGS="--no-cpu-baseline --no-fp32 --no-h2d --steps 20 --warmup 5"
+ARGS="--full --no-cpu-baseline --no-fp32 --no-h2d --steps 20 --warmup 5"
 show() { python - $1 <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).readline())

@@ -5,7 +5,7 @@ REPO=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$REPO/gpurun_out/ab_order
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-ARGS="--no-cpu-baseline --no-fp32 --no-h2d --steps 20 --warmup 5"
+ARGS="--full --no-cpu-baseline --no-fp32 --no-h2d --steps 20 --warmup 5"
 python $REPO/bench.py $ARGS > /dev/null 2>&1          # warm caches
 for mode in 61 125 61 125; do
   GE_MSDA_MODE=$mode python $REPO/bench.py $ARGS 2>/dev/null > $OUT/bench_$mode.json
