@@ -1,0 +1,269 @@
+"""Depth for one camera frame (role of depth/apis/inference.py:12-105: ``init_depther`` / ``inference_depther``).
+
+The reference's ``inference_depther`` replaces ``LoadImageFromFile`` by a plain ``LoadImage``, so the two ground-embedding channels
+never reach a GEDepth model.  Here a frame takes the configured KITTI test protocol — LoadImageFromFile(USEPE) -> KBCrop ->
+MultiScaleFlipAug(RandomFlip, Normalize) -> ``aug_test`` — on the device, through ``DepthInferencer``:
+
+  1. the uint8 BGR frame is uploaded from pinned memory (non-blocking, on the engine's stream);
+  2. ``ge_infer_front`` (csrc/infer.hip) writes both flip views, normalised, into a static (2, 5, 352, 1216) buffer;
+  3. ``model.encode_decode`` runs the two views as ONE batch-2 forward (clamped and rescaled, as ``inference`` does);
+  4. ``ge_tta_merge`` forms (view 0 + mirror(view 1)) / 2 into a static (1, 352, 1216) output, in aug_test's order;
+  5. the output is copied to the host.
+
+After two eager calls, steps 3-4 are captured in a hipGraph and replayed for every later frame.  KB crop makes the forward's shape
+constant, so frames of every KITTI size share one graph; only the front end's arguments change, and it stays outside the graph.
+"""
+import os.path as osp
+
+import numpy as np
+import torch
+from PIL import Image
+
+from ... import kernels as K
+from ...mmrt.checkpoint import load_checkpoint
+from ...mmrt.config import Config
+from ..models import build_depther
+
+__all__ = ['init_depther', 'inference_depther', 'DepthInferencer', 'kitti_front_spec']
+
+# test-time transforms of MultiScaleFlipAug the device front end restates (ImageToTensor / Collect are layout only)
+_FRONT_TRANSFORMS = ('RandomFlip', 'Normalize', 'ImageToTensor', 'Collect')
+_PROTOCOL = 'LoadImageFromFile(USEPE) -> KBCrop -> MultiScaleFlipAug(RandomFlip, Normalize)'
+
+
+def init_depther(config, checkpoint=None, device='cuda:0'):
+    """Build a depther from a config file path or ``Config``; load ``checkpoint`` (mmcv layout) when given; the model keeps the config
+    as ``model.cfg``, sits on ``device`` and is in eval mode."""
+    if isinstance(config, str):
+        config = Config.fromfile(config)
+    elif not isinstance(config, Config):
+        raise TypeError(f'config must be a filename or Config object, but got {type(config)}')
+    config.model.pretrained = None
+    config.model.train_cfg = None
+    model = build_depther(config.model, test_cfg=config.get('test_cfg'))
+    if checkpoint is not None:
+        ckpt = load_checkpoint(model, checkpoint, map_location='cpu')
+        meta = ckpt.get('meta') or {}
+        for key in ('CLASSES', 'PALETTE'):
+            if key in meta:
+                setattr(model, key, meta[key])
+    model.cfg = config
+    model.to(device)
+    model.eval()
+    return model
+
+
+def kitti_front_spec(cfg):
+    """The parameters of the configured test pipeline the device front end needs; ``NotImplementedError`` for any other protocol."""
+    pipeline = cfg.data.test.pipeline
+    types = [t['type'] for t in pipeline]
+    load = next((t for t in pipeline if t['type'] == 'LoadImageFromFile'), None)
+    kb = next((t for t in pipeline if t['type'] == 'KBCrop'), None)
+    aug = next((t for t in pipeline if t['type'] == 'MultiScaleFlipAug'), None)
+    other = [t for t in types if t not in ('LoadImageFromFile', 'LoadKITTICamIntrinsic', 'KBCrop', 'MultiScaleFlipAug')]
+    if other:
+        raise NotImplementedError(f'test pipeline step(s) {", ".join(other)}: no device front end for them (inference_depther '
+                                  f'implements the KITTI protocol {_PROTOCOL})')
+    if load is None or kb is None or aug is None or not load.get('USEPE', False):
+        raise NotImplementedError(f'test pipeline {types}: inference_depther implements the KITTI protocol {_PROTOCOL} only')
+    if load.get('LOAD_DYNAMIC_PE', False):
+        raise NotImplementedError('LoadImageFromFile(LOAD_DYNAMIC_PE=True): no device front end for it')
+    inner = [t['type'] for t in aug['transforms']]
+    for t in inner:
+        if t not in _FRONT_TRANSFORMS:
+            raise NotImplementedError(f'MultiScaleFlipAug transform {t}: no device front end for it ({_PROTOCOL})')
+    norm = next((t for t in aug['transforms'] if t['type'] == 'Normalize'), None)
+    if norm is None:
+        raise NotImplementedError(f'MultiScaleFlipAug without Normalize: not the KITTI protocol {_PROTOCOL}')
+    directions = aug.get('flip_direction', 'horizontal')
+    directions = directions if isinstance(directions, list) else [directions]
+    flip = bool(aug.get('flip', False)) and 'RandomFlip' in inner
+    if aug.get('img_ratios') is not None or (flip and directions != ['horizontal']):
+        raise NotImplementedError('multi-scale or vertical-flip test-time augmentation: no device front end for it')
+    return dict(height=int(kb.get('height', 352)), width=int(kb.get('width', 1216)), views=2 if flip else 1,
+                # Normalize holds mean / std as float32 and widens them to float64 (imageops.imnormalize)
+                mean=[float(np.float32(v)) for v in norm['mean']], std=[float(np.float32(v)) for v in norm['std']],
+                to_rgb=bool(norm.get('to_rgb', True)), depth_scale=float(norm.get('depth_scale', 200)),
+                pe_max=float(load.get('pe_max', 200)), pe_root=load.get('pe_root'))
+
+
+def _img_prefix(cfg):
+    test = cfg.data.test
+    img_dir, root = test.get('img_dir'), test.get('data_root')
+    if img_dir is None:
+        return root
+    return img_dir if root is None or osp.isabs(img_dir) else osp.join(root, img_dir)
+
+
+def _pe_file(spec, prefix, path):
+    """``<pe_root or img prefix>/<date>/pe/pe_165.npy`` for an image path inside the test tree, as LoadImageFromFile finds it; else None."""
+    if not isinstance(path, str) or prefix is None:
+        return None
+    rel = osp.relpath(osp.abspath(path), osp.abspath(prefix))
+    if rel.startswith('..') or osp.isabs(rel):
+        return None
+    root = spec['pe_root'] if spec['pe_root'] is not None else prefix
+    npy = osp.join(root, rel.split(osp.sep)[0], 'pe', 'pe_165.npy')
+    return npy if osp.isfile(npy) else None
+
+
+_NO_PE = ('no ground depth for this frame: pass pe= (the raw (H, W) map), calib=(calib_cam_to_cam.txt, calib_velo_to_cam.txt), or an '
+          'image path inside cfg.data.test.data_root/img_dir whose <date>/pe/pe_165.npy exists')
+
+
+def _decode(img):
+    """A path (decoded as the host LoadImageFromFile does: PIL, RGB -> BGR) or an (H, W, 3) uint8 BGR array -> contiguous uint8 BGR."""
+    if isinstance(img, str):
+        return np.ascontiguousarray(np.asarray(Image.open(img).convert('RGB'))[..., ::-1])
+    a = np.asarray(img)
+    if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3:
+        raise TypeError(f'img must be a path or an (H, W, 3) uint8 BGR array, got {a.shape} {a.dtype}')
+    return np.ascontiguousarray(a)
+
+
+class DepthInferencer:
+    """The flip-TTA engine of one model and precision (module docstring).  ``captures`` counts hipGraph captures; ``reset()`` drops them.
+
+    A capture is keyed by the precision and the ``kernel_variant`` of every module that has one.  It bakes in the addresses of the
+    parameters, buffers and static tensors: parameters must be updated IN PLACE (``load_state_dict``, ``param.data.copy_``) for a replay to
+    see them; replacing a parameter tensor needs ``reset()``.  Host-side heuristics evaluated at capture time (the cross-attention's query
+    order) are frozen into the graph as in mmrt/graph.py; results do not depend on them."""
+
+    WARMUP = 2
+
+    def __init__(self, model, bf16=False):
+        self.model, self.bf16 = model, bool(bf16)
+        cfg = getattr(model, 'cfg', None)
+        if cfg is None:
+            raise ValueError('model.cfg is missing: build the model with init_depther (or set model.cfg to its Config)')
+        self.spec = kitti_front_spec(cfg)
+        self.prefix = _img_prefix(cfg)
+        self.device = next(model.parameters()).device
+        s = self.spec
+        self.static_in = torch.empty(s['views'], 5, s['height'], s['width'], device=self.device, dtype=torch.float32)
+        self.static_out = torch.empty(1, s['height'], s['width'], device=self.device, dtype=torch.float32)
+        self.stream = torch.cuda.Stream(self.device)
+        self._pinned = None
+        self._pe = {}
+        self.reset()
+
+    def reset(self):
+        """Drop every captured graph (and its memory pool) and the warm-up counts."""
+        self.graphs, self.calls, self.captures = {}, {}, 0
+
+    # ---- ground depth
+    def _cache(self, key, make):
+        if key not in self._pe:
+            if len(self._pe) >= 16:
+                self._pe.clear()
+            self._pe[key] = make()
+        return self._pe[key]
+
+    def ground_depth(self, H, W, path=None, pe=None, calib=None, cam_height=1.65):
+        """Raw (H, W) f32 ground depth on the device: ``pe``, else ``calib``, else ``<date>/pe/pe_165.npy`` of the test tree."""
+        if pe is not None:
+            t = torch.as_tensor(pe)
+            if tuple(t.shape) != (H, W):
+                raise ValueError(f'pe has shape {tuple(t.shape)}, the frame is {(H, W)}')
+            return t.to(self.device, torch.float32, non_blocking=True).contiguous()
+        if calib is not None:
+            from ..datasets.gpu_pipeline import ground_depth_from_calibration
+            cam, velo = (osp.abspath(p) for p in calib)
+            return self._cache(('calib', cam, velo, float(cam_height), H, W),
+                               lambda: ground_depth_from_calibration(cam, velo, H, W, cam_height, self.device).contiguous())
+        npy = _pe_file(self.spec, self.prefix, path)
+        if npy is None:
+            raise ValueError(_NO_PE)
+
+        def load():
+            a = np.load(npy).astype(np.float32)
+            if a.shape != (H, W):
+                raise ValueError(f'{npy} has shape {a.shape}, the frame is {(H, W)}')
+            return torch.from_numpy(a).to(self.device).contiguous()
+        return self._cache(('npy', npy, H, W), load)
+
+    # ---- one frame
+    def _key(self):
+        return (self.bf16,) + tuple(m.kernel_variant for m in self.model.modules() if hasattr(m, 'kernel_variant'))
+
+    def _metas(self, filename, shape):
+        s = self.spec
+        kb = (s['height'], s['width'], 5)
+        norm = dict(mean=np.float32(s['mean']), std=np.float32(s['std']), to_rgb=s['to_rgb'])
+        return [dict(filename=filename, ori_filename=filename, ori_shape=kb, img_shape=tuple(shape) + (5,), pad_shape=tuple(shape) + (5,),
+                     scale_factor=1.0, flip=bool(v), flip_direction='horizontal', img_norm_cfg=norm) for v in range(s['views'])]
+
+    def _body(self, metas):
+        with torch.no_grad(), torch.autocast('cuda', dtype=torch.bfloat16, enabled=self.bf16):
+            pred = self.model.encode_decode(self.static_in, metas, rescale=True)
+        pred = pred.float().contiguous()
+        if self.spec['views'] == 2:
+            K.tta_merge(pred, self.static_out)
+        else:
+            self.static_out.copy_(pred[0])
+
+    def upload(self, bgr):
+        """Host uint8 frame -> device, through a reused pinned buffer and a non-blocking copy on the current stream."""
+        n = bgr.size
+        if self._pinned is None or self._pinned.numel() < n:
+            self._pinned = torch.empty(n, dtype=torch.uint8, pin_memory=True)
+        host = self._pinned[:n].view(bgr.shape)
+        host.numpy()[...] = bgr
+        return host.to(self.device, non_blocking=True)
+
+    def __call__(self, img, pe=None, calib=None, cam_height=1.65, graph=True):
+        bgr = _decode(img)
+        H, W = bgr.shape[:2]
+        s = self.spec
+        if H < s['height'] or W < s['width']:
+            raise ValueError(f'frame {(H, W)} is smaller than the KB crop {(s["height"], s["width"])}')
+        top, left = int(H - s['height']), int((W - s['width']) / 2)               # KBCrop
+        metas = self._metas(img if isinstance(img, str) else None, (H, W))
+        cur = torch.cuda.current_stream(self.device)
+        self.stream.wait_stream(cur)
+        with torch.cuda.stream(self.stream):
+            raw = self.ground_depth(H, W, img if isinstance(img, str) else None, pe, calib, cam_height)
+            dev = self.upload(bgr)
+            K.infer_front(dev, raw, self.static_in, top, left, s['mean'], s['std'], s['to_rgb'], s['pe_max'], s['depth_scale'])
+            key = self._key()
+            g = self.graphs.get(key) if graph else None
+            if graph and g is None and self.calls.get(key, 0) >= self.WARMUP:
+                g = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(g, stream=self.stream):
+                    self._body(metas)
+                self.graphs[key] = g
+                self.captures += 1
+            if g is not None:
+                g.replay()
+            else:
+                self._body(metas)
+                if graph:
+                    self.calls[key] = self.calls.get(key, 0) + 1
+            out = self.static_out.cpu().numpy()                # synchronises the engine's stream; a fresh host array per frame
+        cur.wait_stream(self.stream)
+        return out
+
+
+def inference_depther(model, img, pe=None, calib=None, cam_height=1.65, bf16=False, graph=True):
+    """Depth for each frame of ``img`` (a path, an (H, W, 3) uint8 BGR array, or a list of these): a list with one (1, 352, 1216)
+    float32 array per frame — what ``model(return_loss=False, rescale=True, **data)`` returns for that frame through the config's test
+    pipeline.  The raw (H, W) ground depth at frame size comes from ``pe`` (array or device tensor; a list: one per frame), else from
+    ``calib=(calib_cam_to_cam.txt, calib_velo_to_cam.txt)`` with ``cam_height`` (computed on the device, cached per calibration and
+    size), else from ``<date>/pe/pe_165.npy`` of an image path inside ``cfg.data.test.data_root/img_dir``.  ``bf16``: the forward under
+    bf16 autocast.  ``graph``: replay a captured hipGraph of forward + merge after two eager calls (``DepthInferencer``)."""
+    imgs = img if isinstance(img, list) else [img]
+    pes = pe if isinstance(pe, list) else [pe] * len(imgs)
+    if len(pes) != len(imgs):
+        raise ValueError(f'{len(pes)} ground-depth maps for {len(imgs)} frames')
+    cfg = getattr(model, 'cfg', None)
+    if cfg is None:
+        raise ValueError('model.cfg is missing: build the model with init_depther (or set model.cfg to its Config)')
+    spec, prefix = kitti_front_spec(cfg), _img_prefix(cfg)                    # argument errors before any device work
+    if calib is None and any(p is None and _pe_file(spec, prefix, i) is None for i, p in zip(imgs, pes)):
+        raise ValueError(_NO_PE)
+    engines = model.__dict__.setdefault('_ge_inferencers', {})
+    bf16 = bool(bf16)
+    if bf16 not in engines or engines[bf16].spec != spec or engines[bf16].prefix != prefix:     # model.cfg replaced: a new engine
+        engines[bf16] = DepthInferencer(model, bf16)
+    eng = engines[bf16]
+    return [eng(i, p, calib, cam_height, graph) for i, p in zip(imgs, pes)]

@@ -105,6 +105,17 @@ def read_kitti_calibration(cam_path, velo_path):
     return P2, R0, Tr
 
 
+def ground_depth_from_calibration(cam_path, velo_path, H, W, cam_height=1.65, device='cuda'):
+    """(H, W) f32 ground depth of a camera on the device, with the arithmetic of preprocess_data_kitti.py:29-56 (ge_ground_plane)."""
+    from ...kernels import ground_plane
+    P2, R0, Tr = read_kitti_calibration(cam_path, velo_path)
+    A = P2 @ R0 @ Tr
+    Rinv = np.linalg.inv(A[:3, :3])
+    RT = Rinv @ A[:3, 3]
+    _, pe32 = ground_plane(Rinv[2], float(RT[2] - cam_height), H, W, device=device, want_f64=False)
+    return pe32
+
+
 # ---------------------------------------------------------------------------------------------- device side
 def _lib():
     return hip.lib()
@@ -138,13 +149,9 @@ class KITTIGPUPipeline:
         key = (date, H, W)
         if key not in self._pe:
             if self.pe_source == 'calib':
-                from ...kernels import ground_plane
                 d = osp.join(self.root, date)
-                P2, R0, Tr = read_kitti_calibration(osp.join(d, 'calib_cam_to_cam.txt'), osp.join(d, 'calib_velo_to_cam.txt'))
-                A = P2 @ R0 @ Tr
-                Rinv = np.linalg.inv(A[:3, :3])
-                RT = Rinv @ A[:3, 3]
-                _, pe32 = ground_plane(Rinv[2], float(RT[2] - self.cam_height), H, W, device=self.device, want_f64=False)
+                pe32 = ground_depth_from_calibration(osp.join(d, 'calib_cam_to_cam.txt'), osp.join(d, 'calib_velo_to_cam.txt'), H, W,
+                                                     self.cam_height, self.device)
             else:
                 pe = np.load(osp.join(self.root, date, 'pe', 'pe_165.npy')).astype(np.float32)
                 assert pe.shape == (H, W), (pe.shape, H, W)

@@ -71,9 +71,10 @@ class LoadImageFromFile:
     ``data/kitti/input/``."""
 
     def __init__(self, to_float32=False, color_type='color', file_client_args=None, imdecode_backend='cv2', USEPE=False,
-                 LOAD_DYNAMIC_PE=False, pe_root=None, **unused_mask_options):
+                 LOAD_DYNAMIC_PE=False, pe_root=None, pe_max=200, **unused_mask_options):
         self.to_float32, self.color_type, self.imdecode_backend = to_float32, color_type, imdecode_backend
         self.USEPE, self.LOAD_DYNAMIC_PE, self.pe_root = USEPE, LOAD_DYNAMIC_PE, pe_root
+        self.pe_max = pe_max                                  # the reference's hard-coded 200 (loading.py:397-401)
         if LOAD_DYNAMIC_PE:
             raise NotImplementedError('LOAD_DYNAMIC_PE (ground depth from GT slopes) is not used by the released configs')
 
@@ -94,7 +95,7 @@ class LoadImageFromFile:
         if self.USEPE:
             pe_comput = self._pe(results)
             pe = pe_comput.copy()
-            pe[pe > 200] = 0
+            pe[pe > self.pe_max] = 0
             pe[pe < 0] = 0
             img = np.concatenate((img, pe[..., None], pe_comput[..., None]), axis=-1)     # float32 (H, W, 5)
             results['pe_ori_point'] = pe_comput[-1, -1]

@@ -559,6 +559,24 @@ int ge_aug_area_u8(const uint8_t* src_hwc, float* dst, int H, int W, int Ho, int
 int ge_aug_splat(const float* src, float* dst, int H, int W, int Ho, int Wo, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Single-frame inference front end and flip-TTA merge (csrc/infer.hip; gedepth_amd/depth/apis/inference.py, the role of
+ * depth/apis/inference.py of the reference).
+ * ge_infer_front: HWC uint8 BGR frame + (H, W) raw ground depth -> dst (views, 5, Hc, Wc) f32, the KITTI test pipeline
+ *   (configs/_base_/datasets/kitti_gedepth.py: LoadImageFromFile(USEPE) -> KBCrop -> MultiScaleFlipAug(RandomFlip, Normalize)) in
+ *   one launch: view 0 = the window at (top, left), view 1 (views == 2) = its horizontal mirror.  Per element exactly
+ *   ge_aug_load -> ge_aug_color_normalize(color_on = 0) -> ge_aug_window(flip): truncate to uint8, BGR -> RGB when to_rgb,
+ *   (x - mean) * (1 / std) in f64 rounded to f32 (mean3 / std3 host double[3]); channel 3 = pe with > pe_max or < 0 zeroed, then
+ *   / depth_scale where positive; channel 4 = raw pe.  Wc % 4 == 0 and dst 16-byte aligned, else GE_ERR_UNSUPPORTED.
+ * ge_tta_merge: src (2, H, W) = the (clamped, rescaled) predictions of the two views -> dst (H, W) = (src[0] + mirror(src[1])) / 2,
+ *   the operation order of encoder_decoder.py aug_test (bit-identical to the ATen composition).  W % 4 == 0, src and dst 16-byte
+ *   aligned, else GE_ERR_UNSUPPORTED.
+ */
+int ge_infer_front(const uint8_t* bgr_hwc, const float* pe, float* dst, int H, int W, int top, int left, int Hc, int Wc,
+                   int views, float pe_max, const double* mean3, const double* std3, float depth_scale, int to_rgb,
+                   void* stream);
+int ge_tta_merge(const float* src, float* dst, int H, int W, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * SiLog loss statistics (fp32 in, fp64 accumulate), SigLoss.sigloss
  * (depth/models/losses/sigloss.py:36-53) without the dynamic-shape boolean gather:
  * over valid = gt > 0:  stats[0] = n, stats[1] = sum g, stats[2] = sum g^2 with
