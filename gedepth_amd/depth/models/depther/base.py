@@ -4,9 +4,13 @@ MI355X-first difference: the reference does one ``all_reduce`` + ``.item()`` per
 iteration (base.py:197-202 — 2-3 host syncs per step).  Here the scalars are stacked into one tensor, reduced
 with ONE collective, and only brought to the host when a logger actually reads them (``DeferredLogVars``).
 """
+import os
+import os.path as osp
+import warnings
 from abc import ABCMeta, abstractmethod
 from collections import OrderedDict
 
+import numpy as np
 import torch
 import torch.distributed as dist
 
@@ -46,6 +50,23 @@ class DeferredLogVars(OrderedDict):
     def tensor(self):
         """Device tensor of the (already all-reduced) values, or None once materialised."""
         return self._tensor
+
+
+_PIL_SAVE_ARGS = {'png': dict(compress_level=1), 'jpg': dict(quality=95), 'jpeg': dict(quality=95)}     # OpenCV's imwrite defaults
+_warned_no_display = False
+
+
+def _to_host(depth):
+    return depth.detach().cpu().numpy() if torch.is_tensor(depth) else np.asarray(depth)
+
+
+def _imwrite_bgr(bgr, out_file):
+    """``mmcv.imwrite(bgr, out_file)``: the BGR array is stored as an RGB image (format from the extension), parent directories created."""
+    from PIL import Image
+    d = osp.dirname(osp.abspath(out_file))
+    os.makedirs(d, exist_ok=True)
+    ext = osp.splitext(out_file)[1][1:].lower()
+    Image.fromarray(np.ascontiguousarray(bgr[..., ::-1])).save(out_file, **_PIL_SAVE_ARGS.get(ext, {}))
 
 
 class BaseDepther(BaseModule, metaclass=ABCMeta):
@@ -115,6 +136,33 @@ class BaseDepther(BaseModule, metaclass=ABCMeta):
 
     def val_step(self, data_batch, **kwargs):
         return self(**data_batch, **kwargs)
+
+    def show_result(self, img, result, win_name='', show=False, wait_time=0, out_file=None, format_only=False):
+        """Write ``depth = result[0]`` (base.py:206-247 of the reference, its behaviour rather than its docstring).
+
+        ``format_only``: ``np.save(out_file, depth)``, the raw map.  Otherwise ``out_file`` gets ``colorize(depth)`` over
+        ``[decode_head.min_depth, decode_head.max_depth]`` as an image whose pixels are matplotlib's RGB (PNG written like OpenCV's
+        default).  Parent directories of ``out_file`` are created.  ``show``: there is no display here, so it only warns (once); ``img``
+        (a path or an array) only fed that display and is not read.  With neither ``show`` nor ``out_file`` it warns and returns
+        ``depth`` unchanged."""
+        global _warned_no_display
+        depth = result[0]
+        if show and not _warned_no_display:
+            warnings.warn('show_result(show=True): no display support in gedepth_amd; nothing is shown (use out_file)')
+            _warned_no_display = True
+        if out_file is not None:
+            if format_only:
+                os.makedirs(osp.dirname(osp.abspath(out_file)), exist_ok=True)
+                np.save(out_file, _to_host(depth))
+            else:
+                from ...utils import colorize
+                bgr = _to_host(colorize(depth, vmin=self.decode_head.min_depth, vmax=self.decode_head.max_depth)).squeeze()
+                if bgr.ndim != 3:
+                    raise ValueError(f'show_result writes one image: result[0] must be one depth map, got shape {np.shape(depth)}')
+                _imwrite_bgr(bgr, out_file)
+        if not (show or out_file):
+            warnings.warn('show==False and out_file is not specified, only result depth will be returned')
+            return depth
 
     @staticmethod
     def _parse_losses(losses):

@@ -1,3 +1,4 @@
+from .color_depth import colorize
 from .position_encoding import SinePositionalEncoding
 
-__all__ = ['SinePositionalEncoding']
+__all__ = ['SinePositionalEncoding', 'colorize']

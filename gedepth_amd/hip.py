@@ -12,6 +12,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('GE_LIB') or os.path.join(_HERE, 'csrc', 'libgedepth_hip.so')     # GE_LIB: a differently built library (A/B timing)
 GE_F32, GE_BF16 = 0, 1
+GE_COLORIZE_VMIN_DATA, GE_COLORIZE_VMAX_DATA, GE_COLORIZE_EQUAL = 1, 2, 4      # ge_depth_colorize flags
 
 _c = ctypes
 _vp, _i, _f, _l, _d, _sz, _u64 = _c.c_void_p, _c.c_int, _c.c_float, _c.c_long, _c.c_double, _c.c_size_t, _c.c_ulonglong
@@ -114,6 +115,7 @@ SIGNATURES = {
     'ge_aug_splat': (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
     'ge_infer_front': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _vp, _vp, _f, _i, _vp]),
     'ge_tta_merge': (_i, [_vp, _vp, _i, _i, _vp]),
+    'ge_depth_colorize': (_i, [_vp, _l, _f, _f, _f, _i, _vp, _vp, _i, _vp, _vp]),
     'ge_silog_stats': (_i, [_vp, _vp, _f, _vp, _l, _vp]),
     'ge_silog_bwd': (_i, [_vp, _vp, _f, _vp, _vp, _vp, _l, _vp]),
     'ge_sumsq': (_i, [_vp, _l, _vp, _vp]),

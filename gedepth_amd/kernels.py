@@ -2150,3 +2150,47 @@ def tta_merge(pred, out=None):
         out = torch.empty(1, H, W, device=pred.device, dtype=_f32)
     hip.check(hip.lib().ge_tta_merge(hip.ptr(pred, _f32, 'pred'), hip.ptr(out, _f32, 'out'), H, W, hip.stream()), 'ge_tta_merge')
     return out
+
+
+# --------------------------------------------------------------------- depth colorization (csrc/visualize.hip)
+
+def _colorize_bounds(vmin, vmax):
+    """(vmin_f32, vmax_f32, den, flags) of ``ge_depth_colorize`` with numpy 2's scalar semantics: a None bound is the data's float32
+    min / max (decided on the device); for two given bounds ``vmin != vmax`` and ``vmax - vmin`` are evaluated on the host with the
+    caller's own scalars (two Python numbers subtract in float64, a numpy float32 makes it float32) and the difference is rounded to f32."""
+    import numpy as np
+    vmin, vmax = [v.item() if torch.is_tensor(v) else v for v in (vmin, vmax)]
+    flags = (hip.GE_COLORIZE_VMIN_DATA if vmin is None else 0) | (hip.GE_COLORIZE_VMAX_DATA if vmax is None else 0)
+    lo = 0.0 if vmin is None else float(np.float32(vmin))
+    hi = 0.0 if vmax is None else float(np.float32(vmax))
+    den = 0.0
+    if not flags:
+        if vmin != vmax:
+            den = float(np.float32(vmax - vmin))
+        else:
+            flags |= hip.GE_COLORIZE_EQUAL
+    return lo, hi, den, flags
+
+
+def depth_colorize(value, vmin, vmax, lut):
+    """``value`` (...) float32 CUDA tensor -> (..., 3) uint8 BGR: ``lut[index]`` with the colormap index of matplotlib's
+    ``Colormap.__call__`` applied to ``(value - vmin) / (vmax - vmin)`` (reference ``colorize``); ``vmin`` / ``vmax`` None: the data's
+    min / max.  ``lut``: (N + 3, 3) uint8 CUDA tensor, N colours then under / over / bad."""
+    if not value.is_cuda:
+        hip.ptr(value, name='value')                               # raises: CPU tensors are not run
+    if value.dtype != _f32:
+        value = value.float()
+    value = _c(value)
+    if lut.dtype != torch.uint8 or lut.dim() != 2 or lut.shape[1] != 3 or lut.shape[0] < 4:
+        raise TypeError(f'lut must be an (N + 3, 3) uint8 tensor, got {tuple(lut.shape)} {lut.dtype}')
+    if value.numel() == 0:
+        raise ValueError('colorize of an empty array')
+    lo, hi, den, flags = _colorize_bounds(vmin, vmax)
+    ws = None
+    if flags & (hip.GE_COLORIZE_VMIN_DATA | hip.GE_COLORIZE_VMAX_DATA):
+        ws = torch.empty(512, device=value.device, dtype=_f32)       # partial (min, max) pairs, from the caching allocator
+    out = torch.empty(tuple(value.shape) + (3,), device=value.device, dtype=torch.uint8)
+    hip.check(hip.lib().ge_depth_colorize(hip.ptr(value, _f32, 'value'), value.numel(), lo, hi, den, flags, hip.ptr(ws, _f32, 'ws'),
+                                          hip.ptr(_c(lut), torch.uint8, 'lut'), lut.shape[0] - 3, hip.ptr(out, torch.uint8, 'out'),
+                                          hip.stream()), 'ge_depth_colorize')
+    return out

@@ -577,6 +577,21 @@ int ge_infer_front(const uint8_t* bgr_hwc, const float* pe, float* dst, int H, i
 int ge_tta_merge(const float* src, float* dst, int H, int W, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Depth colorization (csrc/visualize.hip; gedepth_amd/depth/utils/color_depth.py, the role of depth/utils/color_depth.py colorize of the
+ * reference followed by matplotlib's Colormap.__call__(x, bytes=True) and [..., :3][..., ::-1]).
+ * ge_depth_colorize: src (n) f32 -> dst_bgr (n, 3) uint8, dst = lut_bgr[idx] with lut_bgr the (N + 3, 3) BGR table (N colours, then
+ *   under, over, bad).  Per element in f32, as numpy does: x = (v - vmin) / den (IEEE division), or x = v * 0 when GE_COLORIZE_EQUAL;
+ *   xa = x * N; xa == N -> N - 1; NaN -> N + 2, xa < 0 -> N, xa >= N -> N + 1, else trunc(xa).  With GE_COLORIZE_VMIN_DATA /
+ *   GE_COLORIZE_VMAX_DATA that bound is min(src) / max(src) (NaN-propagating), reduced on the device through minmax_ws (512 floats,
+ *   device), and then equality and den = vmax - vmin are decided in f32 on the device (den and GE_COLORIZE_EQUAL are ignored); otherwise
+ *   the caller passes vmin rounded to f32, den, and GE_COLORIZE_EQUAL when vmin == vmax.  Any src / dst alignment; N <= 4096, else
+ *   GE_ERR_UNSUPPORTED.
+ */
+enum { GE_COLORIZE_VMIN_DATA = 1, GE_COLORIZE_VMAX_DATA = 2, GE_COLORIZE_EQUAL = 4 };
+int ge_depth_colorize(const float* src, long n, float vmin, float vmax, float den, int flags, float* minmax_ws,
+                      const uint8_t* lut_bgr, int N, uint8_t* dst_bgr, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * SiLog loss statistics (fp32 in, fp64 accumulate), SigLoss.sigloss
  * (depth/models/losses/sigloss.py:36-53) without the dynamic-shape boolean gather:
  * over valid = gt > 0:  stats[0] = n, stats[1] = sum g, stats[2] = sum g^2 with

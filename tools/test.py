@@ -1,13 +1,21 @@
 #!/usr/bin/env python
-"""Evaluate / run a depther — CLI of the reference's tools/test.py:21-68 (config, checkpoint, --eval, --options).
+"""Evaluate / run a depther — CLI of the reference's tools/test.py:21-68 (config, checkpoint, --eval, --options, --out,
+--format-only, --show, --show-dir, --eval-options, --launcher).
 
 With a KITTI tree at ``cfg.data.test.data_root`` this is the Eigen-split protocol of the reference: test pipeline with
 flip test-time augmentation, ``forward_test`` (``return_loss=False``), KB crop + Garg crop, per-image metrics, nan-mean
 summary (gedepth_amd/depth/apis/test.py, gedepth_amd/depth/datasets/kitti.py).  ``--synthetic N`` runs the same model
 protocol on N synthetic KITTI-shaped inputs instead (no dataset needed).
+
+Any of ``--out`` / ``--format-only`` / ``--show`` / ``--show-dir``, or ``--launcher pytorch``, runs the reference's dataset route:
+``--show-dir DIR`` writes one colorized depth image per test image (``BaseDepther.show_result``), ``--format-only --show-dir DIR`` the
+raw maps as ``.npy``, ``--out FILE.pkl`` pickles the results list (metric tuples with ``--eval``, else the maps) on rank 0, and
+``--launcher pytorch`` (tools/dist_test.sh) evaluates one shard per rank with ``multi_gpu_test``.
 """
 import argparse
+import os
 import os.path as osp
+import pickle
 import sys
 
 import numpy as np
@@ -22,7 +30,7 @@ from gedepth_amd.mmrt.checkpoint import load_checkpoint  # noqa: E402
 from gedepth_amd.mmrt.config import Config, DictAction  # noqa: E402
 
 
-def main():
+def parse_args(argv=None):
     p = argparse.ArgumentParser(description='depth test (and eval) a model')
     p.add_argument('config')
     p.add_argument('checkpoint', nargs='?', default=None)
@@ -31,12 +39,73 @@ def main():
     p.add_argument('--synthetic', type=int, default=2, help='N synthetic inputs; 0 = evaluate cfg.data.test')
     p.add_argument('--flip-tta', action='store_true')
     p.add_argument('--bf16', action='store_true', help='bf16 autocast inference')
-    args = p.parse_args()
+    p.add_argument('--out', help='output result file in pickle format (.pkl / .pickle), written by rank 0')
+    p.add_argument('--format-only', action='store_true',
+                   help='format the results (dataset.format_results) without evaluating; with --show-dir the raw maps are saved as .npy')
+    p.add_argument('--show', action='store_true', help='show results (no display support here: warns and shows nothing)')
+    p.add_argument('--show-dir', help='directory where the colorized depth maps (or, with --format-only, the raw .npy maps) are saved')
+    p.add_argument('--eval-options', nargs='+', default=None, help='k=v options for evaluate / format_results')
+    p.add_argument('--launcher', choices=['none', 'pytorch'], default='none', help='job launcher (pytorch: torch.distributed.run)')
+    p.add_argument('--local_rank', '--local-rank', type=int, default=0)
+    p.add_argument('--gpu-collect', action='store_true',
+                   help='accepted for compatibility, no effect: multi_gpu_test always gathers with all_gather_object')
+    p.add_argument('--tmpdir', help='accepted for compatibility, no effect: multi_gpu_test collects no temporary files')
+    args = p.parse_args(argv)
+    if 'LOCAL_RANK' not in os.environ:
+        os.environ['LOCAL_RANK'] = str(args.local_rank)
+    if args.eval and args.format_only:
+        raise ValueError('--eval and --format-only cannot be both specified')
+    if args.out is not None and not args.out.endswith(('.pkl', '.pickle')):
+        raise ValueError('The output file must be a pkl file.')
+    return args
+
+
+def run_dataset(args, cfg):
+    """The reference's dataset route: (distributed) evaluation of cfg.data.test with --out / --format-only / --show / --show-dir."""
+    from gedepth_amd.depth.apis.test import multi_gpu_test, single_gpu_test
+    from gedepth_amd.depth.datasets import build_dataloader, build_dataset
+    from gedepth_amd.mmrt.ddp import init_dist
+    from gedepth_amd.mmrt.runner import get_dist_info
+    data_root = cfg.data.test.get('data_root')
+    if not (data_root and osp.isdir(data_root)):
+        sys.exit(f'tools/test.py: cfg.data.test.data_root = {data_root!r} is not a directory; the dataset route (--out, --format-only, '
+                 '--show, --show-dir, --launcher pytorch) evaluates the test split there (set it with --options data.test.data_root=...)')
+    eval_kwargs = DictAction.parse(args.eval_options)
+    distributed = args.launcher == 'pytorch'
+    if distributed:
+        init_dist(cfg.get('dist_params', {}).get('backend', 'nccl'))
+    dataset = build_dataset(cfg.data.test, dict(test_mode=True))
+    loader = build_dataloader(dataset, 1, cfg.data.workers_per_gpu, dist=distributed, shuffle=False)
+    model = build_depther(cfg.model, test_cfg=cfg.get('test_cfg'))
+    if args.checkpoint:
+        load_checkpoint(model, args.checkpoint, map_location='cpu')
+    model = model.cuda().eval()
+    test = multi_gpu_test if distributed else single_gpu_test
+    with torch.autocast('cuda', dtype=torch.bfloat16, enabled=args.bf16):
+        results = test(model, loader, pre_eval=args.eval is not None, format_only=args.format_only, format_args=eval_kwargs,
+                       show=args.show, out_dir=args.show_dir)
+    rank, _ = get_dist_info()
+    if rank == 0:
+        if args.out:
+            os.makedirs(osp.dirname(osp.abspath(args.out)), exist_ok=True)
+            print(f'\nwriting results to {args.out}')
+            with open(args.out, 'wb') as fh:
+                pickle.dump(results, fh)
+        if args.eval:
+            dataset.evaluate(results, args.eval, **eval_kwargs)
+    if torch.distributed.is_available() and torch.distributed.is_initialized():
+        torch.distributed.destroy_process_group()
+
+
+def main():
+    args = parse_args()
     cfg = Config.fromfile(args.config)
     if args.options:
         cfg.merge_from_dict(DictAction.parse(args.options))
     cfg.model.pretrained = None
     cfg.model.train_cfg = None
+    if args.out or args.format_only or args.show or args.show_dir or args.launcher == 'pytorch':
+        return run_dataset(args, cfg)
     model = build_depther(cfg.model, test_cfg=cfg.get('test_cfg'))
     if args.checkpoint:
         load_checkpoint(model, args.checkpoint, map_location='cpu')
