@@ -117,10 +117,6 @@ def ground_depth_from_calibration(cam_path, velo_path, H, W, cam_height=1.65, de
 
 
 # ---------------------------------------------------------------------------------------------- device side
-def _lib():
-    return hip.lib()
-
-
 def _planes(C, H, W, dev):
     return torch.empty(C, H, W, device=dev, dtype=_f32)
 
@@ -163,14 +159,13 @@ class KITTIGPUPipeline:
     def _resize(self, x, size, mode):
         C, Hs, Ws = x.shape
         out = _planes(C, size[0], size[1], x.device)
-        hip.check(_lib().ge_aug_resize(hip.ptr(x), hip.ptr(out), C, Hs, Ws, size[0], size[1], mode, hip.stream()), 'ge_aug_resize')
+        hip.call('ge_aug_resize', hip.ptr(x), hip.ptr(out), C, Hs, Ws, size[0], size[1], mode, hip.stream())
         return out
 
     def _window(self, x, size, oy, ox, flip=False, fill=0.0):
         C, Hs, Ws = x.shape
         out = _planes(C, size[0], size[1], x.device)
-        hip.check(_lib().ge_aug_window(hip.ptr(x), hip.ptr(out), C, Hs, Ws, size[0], size[1], int(oy), int(ox), int(flip), float(fill),
-                                       hip.stream()), 'ge_aug_window')
+        hip.call('ge_aug_window', hip.ptr(x), hip.ptr(out), C, Hs, Ws, size[0], size[1], int(oy), int(ox), int(flip), float(fill), hip.stream())
         return out
 
     def _rotate(self, x, angle, border, mode):
@@ -179,8 +174,7 @@ class KITTIGPUPipeline:
         m = np.array([inv[0, 0], inv[0, 1], off[0], inv[1, 0], inv[1, 1], off[1]]).astype(np.float32)
         arr = (ctypes.c_float * 6)(*[float(v) for v in m])
         out = _planes(C, H, W, x.device)
-        hip.check(_lib().ge_aug_rotate(hip.ptr(x), hip.ptr(out), C, H, W, ctypes.cast(arr, ctypes.c_void_p), float(border), mode,
-                                       hip.stream()), 'ge_aug_rotate')
+        hip.call('ge_aug_rotate', hip.ptr(x), hip.ptr(out), C, H, W, ctypes.cast(arr, ctypes.c_void_p), float(border), mode, hip.stream())
         return out
 
     def _front(self, sample):
@@ -193,12 +187,12 @@ class KITTIGPUPipeline:
         kh, kw = self.kb_crop
         top, left = int(H - kh), int((W - kw) / 2)                                   # KBCrop, transforms.py:150-205
         img = _planes(5, kh, kw, dev)
-        hip.check(_lib().ge_aug_load(hip.ptr(bgr), hip.ptr(pe), hip.ptr(img), H, W, top, left, kh, kw, 200.0, hip.stream()), 'ge_aug_load')
+        hip.call('ge_aug_load', hip.ptr(bgr), hip.ptr(pe), hip.ptr(img), H, W, top, left, kh, kw, 200.0, hip.stream())
         depth = k = None
         if 'depth_png' in sample:
             png = sample['depth_png'].to(dev, non_blocking=True).contiguous()
             depth = _planes(1, kh, kw, dev)
-            hip.check(_lib().ge_aug_depth(hip.ptr(png), hip.ptr(depth), H, W, top, left, kh, kw, self.depth_scale, hip.stream()), 'ge_aug_depth')
+            hip.call('ge_aug_depth', hip.ptr(png), hip.ptr(depth), H, W, top, left, kh, kw, self.depth_scale, hip.stream())
         if 'pe_k' in sample:
             kmap = sample['pe_k'].to(dev, non_blocking=True).contiguous()
             if tuple(kmap.shape) != (H, W):                                          # loading.py:146: nearest resize to the depth map
@@ -226,11 +220,9 @@ class KITTIGPUPipeline:
         out_img = torch.empty_like(img)
         col = params['color']
         colors = (ctypes.c_double * 3)(*(col[2] if col else (1.0, 1.0, 1.0)))
-        hip.check(_lib().ge_aug_color_normalize(hip.ptr(img), hip.ptr(out_img), img.shape[1], img.shape[2], int(col is not None),
-                                                float(col[0]) if col else 1.0, float(col[1]) if col else 1.0,
-                                                ctypes.cast(colors, ctypes.c_void_p), ctypes.cast(self.mean, ctypes.c_void_p),
-                                                ctypes.cast(self.std, ctypes.c_void_p), self.pe_depth_scale, int(self.to_rgb),
-                                                hip.stream()), 'ge_aug_color_normalize')
+        hip.call('ge_aug_color_normalize', hip.ptr(img), hip.ptr(out_img), img.shape[1], img.shape[2], int(col is not None),
+                 float(col[0]) if col else 1.0, float(col[1]) if col else 1.0, ctypes.cast(colors, ctypes.c_void_p),
+                 ctypes.cast(self.mean, ctypes.c_void_p), ctypes.cast(self.std, ctypes.c_void_p), self.pe_depth_scale, int(self.to_rgb), hip.stream())
         out = dict(img=out_img, pe_ori_point=pe_ori_point,
                    img_metas=dict(filename=sample['filename'], ori_filename=sample['ori_filename'], ori_shape=(kh, kw, 5),
                                   img_shape=tuple(out_img.shape[1:]) + (5,), pad_shape=tuple(out_img.shape[1:]) + (5,),
@@ -312,7 +304,7 @@ class DDADGPUPipeline(KITTIGPUPipeline):
         oh, ow = self.kb_crop
         pe_raw = self.ground_depth(sample['camera'], H, W)
         img = _planes(5, oh, ow, dev)
-        hip.check(_lib().ge_aug_area_u8(hip.ptr(bgr), hip.ptr(img), H, W, oh, ow, hip.stream()), 'ge_aug_area_u8')
+        hip.call('ge_aug_area_u8', hip.ptr(bgr), hip.ptr(img), H, W, oh, ow, hip.stream())
         pe = pe_raw.clone()                                                         # LoadDDADImageFromFile: channel 3 = pe with (250, inf) and (-inf, 0) zeroed
         pe[pe > 250] = 0
         pe[pe < 0] = 0
@@ -321,9 +313,9 @@ class DDADGPUPipeline(KITTIGPUPipeline):
         if 'depth' in sample:
             d = sample['depth'].to(dev, non_blocking=True).contiguous()
             depth = _planes(1, oh, ow, dev)
-            hip.check(_lib().ge_aug_splat(hip.ptr(d), hip.ptr(depth), d.shape[0], d.shape[1], oh, ow, hip.stream()), 'ge_aug_splat')
+            hip.call('ge_aug_splat', hip.ptr(d), hip.ptr(depth), d.shape[0], d.shape[1], oh, ow, hip.stream())
         if 'pe_k' in sample:
             kk = sample['pe_k'].to(dev, non_blocking=True).contiguous()
             k = _planes(1, oh, ow, dev)
-            hip.check(_lib().ge_aug_splat(hip.ptr(kk), hip.ptr(k), kk.shape[0], kk.shape[1], oh, ow, hip.stream()), 'ge_aug_splat')
+            hip.call('ge_aug_splat', hip.ptr(kk), hip.ptr(k), kk.shape[0], kk.shape[1], oh, ow, hip.stream())
         return img, depth, k, pe_raw[-1, -1]

@@ -1,127 +1,55 @@
 """ctypes binding of libgedepth_hip.so (C ABI: include/gedepth_hip.h).
 
+The header is the only statement of the ABI: ``SIGNATURES`` (name -> (restype, argtypes)) is parsed from it at import, so a new entry
+point is declared there and nowhere else.  ``call(name, *args)`` launches an entry point that returns an error code and raises on a
+non-zero one; size queries and predicates that return a value are called on ``lib()`` directly.
+
 There is deliberately NO fallback: if the shared library is missing, or a tensor is not a
 contiguous CUDA(HIP) tensor of the expected dtype, the call raises.  Build the library with
 ``gedepth_amd/csrc/build.sh`` (or ``python -c 'import __graft_entry__ as g; g.build()'``).
 """
 import ctypes
 import os
+import re
 
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('GE_LIB') or os.path.join(_HERE, 'csrc', 'libgedepth_hip.so')     # GE_LIB: a differently built library (A/B timing)
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), 'include', 'gedepth_hip.h')
 GE_F32, GE_BF16 = 0, 1
 GE_COLORIZE_VMIN_DATA, GE_COLORIZE_VMAX_DATA, GE_COLORIZE_EQUAL = 1, 2, 4      # ge_depth_colorize flags
 
-_c = ctypes
-_vp, _i, _f, _l, _d, _sz, _u64 = _c.c_void_p, _c.c_int, _c.c_float, _c.c_long, _c.c_double, _c.c_size_t, _c.c_ulonglong
+_SCALARS = {'int': ctypes.c_int, 'long': ctypes.c_long, 'float': ctypes.c_float, 'double': ctypes.c_double, 'size_t': ctypes.c_size_t,
+            'uint64_t': ctypes.c_ulonglong, 'unsigned long long': ctypes.c_ulonglong}
+_DECL = re.compile(r'\b(int|size_t)\s+(ge_\w+)\s*\(([^()]*)\)\s*;')
 
-# name -> (restype, argtypes): mirrors include/gedepth_hip.h one to one
-SIGNATURES = {
-    'ge_abi_version': (_i, []),
-    'ge_window_attn_fwd': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _i, _i, _vp]),
-    'ge_window_attn_bwd_workspace': (_sz, [_i, _i, _i, _i]),
-    'ge_window_attn_bwd': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _i, _i, _vp]),
-    'ge_msda_fwd': (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
-    'ge_msda_mode': (_i, [_i]),
-    'ge_msda_bwd_workspace': (_sz, [_vp, _i, _i, _i, _i, _i, _i]),
-    'ge_msda_bwd': (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _i, _i, _i, _vp]),
-    'ge_msda_bwd_plan': (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp]),
-    'ge_msda_bwd_timing': (_i, [_i]),
-    'ge_msda_bwd_timing_read': (_i, [_i, _vp, _vp, _vp, _i]),
-    'ge_msda_prep_fwd': (_i, [_vp, _l, _vp, _l, _vp, _l, _l, _l, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
-    'ge_msda_prep_bwd': (_i, [_vp, _vp, _vp, _vp, _vp, _l, _vp, _l, _vp, _i, _i, _i, _i, _i, _i, _vp]),
-    'ge_msda_raw_supported': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i]),
-    'ge_msda_fwd_raw': (_i, [_vp, _vp, _vp, _i, _vp, _l, _vp, _l, _vp, _l, _l, _l, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
-    'ge_msda_bwd_raw': (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _l, _vp, _l, _vp, _vp, _sz, _i, _i, _i, _i, _i, _i, _i, _vp]),
-    'ge_msda_mm_supported': (_i, [_vp, _i, _i, _i, _i, _i, _i, _i]),
-    'ge_msda_fwd_mm': (_i, [_vp, _vp, _vp, _l, _vp, _l, _vp, _l, _l, _l, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
-    'ge_msda_bwd_lw_mm': (_i, [_vp, _vp, _vp, _l, _vp, _l, _vp, _l, _l, _l, _vp, _vp, _vp, _l, _vp, _l, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
-    'ge_msda_bwd_mm_workspace': (_sz, [_i, _i, _i, _i]),
-    'ge_msda_bwd_mm_stats_offset': (_sz, [_i, _i, _i, _i]),
-    'ge_msda_bwd_value_mm': (_i, [_vp, _vp, _l, _vp, _l, _vp, _l, _l, _l, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
-    'ge_msda_fwd_mm_part': (_i, [_vp, _vp, _vp, _l, _vp, _l, _vp, _l, _l, _l, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
-    'ge_msda_bwd_lw_mm_part': (_i, [_vp, _vp, _vp, _l, _vp, _l, _vp, _l, _l, _l, _vp, _vp, _vp, _l, _vp, _l, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
-    'ge_msda_bwd_vs_workspace': (_sz, [_vp, _i, _i, _i, _i, _i, _i]),
-    'ge_msda_bwd_vs_stats_offset': (_sz, [_vp, _i, _i, _i, _i, _i, _i]),
-    'ge_msda_bwd_value_vs': (_i, [_vp, _vp, _l, _vp, _l, _vp, _l, _l, _l, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _i, _i, _i, _vp]),
-    'ge_msda_bwd_value_raw_levels': (_i, [_vp, _vp, _l, _vp, _l, _vp, _l, _l, _l, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
-    'ge_msda_bwd_value': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _i, _i, _i, _vp]),
-    'ge_msda_bwd_value_raw': (_i, [_vp, _vp, _l, _vp, _l, _vp, _l, _l, _l, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _i, _i, _i, _vp]),
-    'ge_msda_dref': (_i, [_vp, _l, _vp, _vp, _l, _i, _i, _i, _i, _vp]),
-    'ge_rng_salt': (_i, [_vp]),
-    'ge_tokens_from_map': (_i, [_vp, _l, _vp, _vp, _l, _i, _i, _l, _f, _u64, _i, _vp]),
-    'ge_map_from_tokens': (_i, [_vp, _l, _vp, _l, _vp, _l, _i, _i, _l, _f, _u64, _i, _vp]),
-    'ge_bilinear_fwd': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
-    'ge_bilinear_bwd': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
-    'ge_layernorm_fwd': (_i, [_vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _l, _i, _f, _vp]),
-    'ge_layernorm_bwd': (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _l, _i, _vp]),
-    'ge_layernorm_bwd_res': (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _l, _i, _vp]),
-    'ge_layernorm_bwd_multi': (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _l, _i, _vp]),
-    'ge_layernorm_fold': (_i, [_vp, _vp, _i, _i, _vp]),
-    'ge_residual_scale_add': (_i, [_vp, _i, _vp, _i, _vp, _vp, _i, _l, _vp]),
-    'ge_scale_rows': (_i, [_vp, _i, _vp, _vp, _i, _i, _l, _vp]),
-    'ge_bn_workspace': (_sz, [_i]),
-    'ge_bn_act_fwd': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _l, _f, _f, _f, _i, _vp]),
-    'ge_bn_act_bwd': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _l, _f, _i, _vp]),
-    'ge_bias_act_fwd': (_i, [_vp, _vp, _i, _i, _l, _f, _i, _vp]),
-    'ge_bias_act_bwd': (_i, [_vp, _vp, _vp, _vp, _i, _i, _l, _f, _i, _vp]),
-    'ge_ground_embed_fwd': (_i, [_vp, _vp, _vp, _l, _vp, _f, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
-    'ge_ground_embed_bwd': (_i, [_vp, _vp, _vp, _l, _vp, _f, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
-    'ge_ground_vanilla_fwd': (_i, [_vp, _vp, _l, _f, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
-    'ge_ground_vanilla_bwd': (_i, [_vp, _l, _f, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
-    'ge_depth_fuse_fwd': (_i, [_vp, _vp, _vp, _f, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
-    'ge_depth_fuse_bwd': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
-    'ge_ground_plane': (_i, [_vp, _d, _vp, _vp, _i, _i, _vp]),
-    'ge_slope_class': (_i, [_vp, _vp, _d, _i, _vp, _i, _i, _vp]),
-    'ge_slope_class_ddad': (_i, [_vp, _vp, _d, _vp, _i, _i, _vp]),
-    'ge_pe_channels': (_i, [_vp, _vp, _f, _l, _vp]),
-    'ge_bn_act_nhwc_fwd': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _l, _i, _f, _f, _f, _i, _vp]),
-    'ge_bn_act_nhwc_bwd': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _l, _i, _f, _i, _vp]),
-    'ge_bias_act_nhwc_fwd': (_i, [_vp, _vp, _l, _i, _f, _i, _vp]),
-    'ge_bias_act_nhwc_bwd': (_i, [_vp, _vp, _vp, _vp, _vp, _l, _i, _f, _i, _vp]),
-    'ge_bilinear_nhwc_fwd': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
-    'ge_bilinear_nhwc_bwd': (_i, [_vp, _vp, _vp, _sz, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
-    'ge_concat_rows_fwd': (_i, [_vp, _l, _l, _vp, _vp, _vp, _l, _i, _i, _i, _f, _u64, _i, _vp]),
-    'ge_slice_rows_drop': (_i, [_vp, _vp, _l, _i, _i, _i, _f, _u64, _i, _vp]),
-    'ge_add_rows': (_i, [_vp, _vp, _vp, _i, _l, _i, _i, _vp]),
-    'ge_colsum': (_i, [_vp, _l, _i, _vp, _vp, _i, _i, _vp]),
-    'ge_bias_gelu_fwd': (_i, [_vp, _vp, _vp, _l, _i, _i, _vp]),
-    'ge_bias_gelu_bwd': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _l, _i, _i, _vp]),
-    'ge_upcat_nhwc_fwd': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
-    'ge_upcat_nhwc_bwd': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
-    'ge_upsum_nhwc_fwd': (_i, [_vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
-    'ge_conv3x3_nhwc_fwd': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _i, _vp]),
-    'ge_conv3x3_nhwc_wgrad': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
-    'ge_conv1x1_nhwc_wgrad': (_i, [_vp, _vp, _vp, _l, _i, _i, _i, _vp]),
-    'ge_conv1x1_bn_workspace': (_sz, [_i, _i]),
-    'ge_conv1x1_bn_stats': (_i, [_vp, _l, _i, _vp, _i, _vp, _vp, _vp, _vp, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp]),
-    'ge_conv1x1_bn_act_fwd': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _l, _i, _i, _f, _vp]),
-    'ge_conv1x1_bn_bwd_mask': (_i, [_vp, _l, _vp, _l, _vp, _vp, _vp, _vp, _l, _i, _f, _vp]),
-    'ge_conv1x1_bn_bwd_finalize': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _l, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    'ge_conv1x1_bn_dgrad': (_i, [_vp, _vp, _vp, _vp, _vp, _l, _i, _i, _vp]),
-    'ge_conv3x3_c1_fwd': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
-    'ge_conv3x3_c1_bwd': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
-    'ge_gemm_nt': (_i, [_vp, _l, _vp, _l, _vp, _vp, _l, _l, _i, _i, _i, _vp]),
-    'ge_nhwc_workspace': (_sz, [_i, _i]),
-    'ge_aug_load': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _vp]),
-    'ge_aug_depth': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _f, _vp]),
-    'ge_aug_resize': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
-    'ge_aug_rotate': (_i, [_vp, _vp, _i, _i, _i, _vp, _f, _i, _vp]),
-    'ge_aug_window': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _f, _vp]),
-    'ge_aug_color_normalize': (_i, [_vp, _vp, _i, _i, _i, _f, _f, _vp, _vp, _vp, _f, _i, _vp]),
-    'ge_aug_area_u8': (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
-    'ge_aug_splat': (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
-    'ge_infer_front': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _vp, _vp, _f, _i, _vp]),
-    'ge_tta_merge': (_i, [_vp, _vp, _i, _i, _vp]),
-    'ge_depth_colorize': (_i, [_vp, _l, _f, _f, _f, _i, _vp, _vp, _i, _vp, _vp]),
-    'ge_silog_stats': (_i, [_vp, _vp, _f, _vp, _l, _vp]),
-    'ge_silog_bwd': (_i, [_vp, _vp, _f, _vp, _vp, _vp, _l, _vp]),
-    'ge_sumsq': (_i, [_vp, _l, _vp, _vp]),
-    'ge_adamw_step': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _l, _vp]),
-    'ge_adamw_step_shadow': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _l, _vp, _vp]),
-}
+
+def parse_header(text):
+    """C declarations ``int|size_t ge_*(...);`` -> {name: (restype, argtypes)}.  Every pointer is bound as c_void_p (device pointers are
+    passed as integers, host arrays through ctypes.cast).  Strict: a parameter type outside ``_SCALARS`` raises and names the function, and
+    so does a ``ge_`` name followed by ``(`` that is not part of a declaration this pattern reads."""
+    text = re.sub(r'/\*.*?\*/|//[^\n]*', ' ', text, flags=re.S)
+    sigs = {}
+    for res, name, params in _DECL.findall(text):
+        args = []
+        for p in ([] if params.strip() == 'void' else params.split(',')):
+            if '*' in p:
+                args.append(ctypes.c_void_p)
+                continue
+            ctype = ' '.join(w for w in p.split()[:-1] if w != 'const')          # the last word is the parameter's name
+            if ctype not in _SCALARS:
+                raise TypeError(f'{name}: parameter "{" ".join(p.split())}" has a type the ctypes binding does not map')
+            args.append(_SCALARS[ctype])
+        sigs[name] = (_SCALARS[res], args)
+    stray = set(re.findall(r'\b(ge_\w+)\s*\(', text)) - set(sigs)
+    if stray:
+        raise TypeError(f'cannot parse the declaration of {", ".join(sorted(stray))}')
+    return sigs
+
+
+with open(HEADER_PATH) as _fh:
+    SIGNATURES = parse_header(_fh.read())          # name -> (restype, argtypes)
 
 _lib = None
 
@@ -156,6 +84,13 @@ def check(code, what):
     if code != 0:
         raise RuntimeError(f'{what} failed with code {code} '
                            f'({"bad argument" if code == 10001 else "unsupported" if code == 10002 else "hipError_t"})')
+
+
+def call(name, *args):
+    """Run entry point ``name`` (one that returns an error code; the stream is its last argument, as in the header) and raise on failure."""
+    code = getattr(_lib or lib(), name)(*args)
+    if code:
+        check(code, name)
 
 
 def dtype_code(t):

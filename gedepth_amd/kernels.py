@@ -40,8 +40,7 @@ class _Profiler:
         out = []
         total, n, name = ctypes.c_double(), ctypes.c_long(), ctypes.create_string_buffer(64)
         for i in range(5):
-            hip.check(hip.lib().ge_msda_bwd_timing_read(i, ctypes.addressof(total), ctypes.addressof(n),
-                                                        ctypes.addressof(name), 64), 'ge_msda_bwd_timing_read')
+            hip.call('ge_msda_bwd_timing_read', i, ctypes.addressof(total), ctypes.addressof(n), ctypes.addressof(name), 64)
             if n.value:
                 out.append(dict(name=name.value.decode(), launches=n.value, avg_us=1e3 * total.value / n.value,
                                 total_ms=total.value, bytes_per_launch=self.stage_bytes.get(i, 0) / n.value))
@@ -87,6 +86,14 @@ def _es(t):
     return t.element_size()
 
 
+def _launch(label, nbytes, name, *args, flops=0):
+    """Every kernel launch of this module: entry point ``name`` of the library with ``args`` (the stream last, as in the header), its error
+    code checked; under the profiler it is timed as ``label`` with its algorithmic bytes / flops."""
+    if PROFILER.on:
+        return PROFILER.run(label, nbytes, lambda: hip.call(name, *args), flops)
+    hip.call(name, *args)
+
+
 # A/B switch for the fused passes added in round 3: GE_DISABLE=upcat,upsum,bias_gelu,msda_raw makes the named entry points take their
 # two-pass composition (still HIP kernels / library calls: a measurement aid for same-box comparisons, not a fall-back)
 DISABLED = {t for t in os.environ.get('GE_DISABLE', '').split(',') if t}
@@ -110,11 +117,9 @@ class _WindowAttention(torch.autograd.Function):
         out = torch.empty(B, L, C3 // 3, device=qkv.device, dtype=qkv.dtype)
         nbytes = 4 * B * L * (C3 // 3) * _es(qkv) + 169 * num_heads * 4
         n_wh = B * ((H + 6) // 7) * ((W + 6) // 7) * num_heads            # (window, head) pairs; 2 contractions of 2*49*49*32 flops each
-        PROFILER.run(f'window_attn_fwd[{B}x{H}x{W} nH{num_heads} s{shift} {_tag(qkv)} v{variant}]', nbytes, lambda: hip.check(
-            hip.lib().ge_window_attn_fwd(
-                hip.ptr(qkv, name='qkv'), hip.ptr(qkv_bias, _f32), hip.ptr(bias_table, _f32), hip.ptr(out),
-                B, H, W, num_heads, shift, scale, hip.dtype_code(qkv), variant, hip.stream()), 'ge_window_attn_fwd'),
-            flops=n_wh * 2 * 2 * 49 * 49 * 32)
+        _launch(f'window_attn_fwd[{B}x{H}x{W} nH{num_heads} s{shift} {_tag(qkv)} v{variant}]', nbytes, 'ge_window_attn_fwd', hip.ptr(qkv, name='qkv'),
+                hip.ptr(qkv_bias, _f32), hip.ptr(bias_table, _f32), hip.ptr(out), B, H, W, num_heads, shift, scale, hip.dtype_code(qkv), variant,
+                hip.stream(), flops=n_wh * 2 * 2 * 49 * 49 * 32)
         ctx.save_for_backward(qkv, qkv_bias, bias_table)
         ctx.geom = (B, H, W, num_heads, shift, scale, variant)
         return out
@@ -131,11 +136,9 @@ class _WindowAttention(torch.autograd.Function):
         ws = torch.empty(max(int(lib.ge_window_attn_bwd_workspace(B, H, W, nH)), 4) // 4, device=qkv.device, dtype=_f32)
         nbytes = 7 * qkv.numel() // 3 * _es(qkv)
         n_wh = B * ((H + 6) // 7) * ((W + 6) // 7) * nH                     # backward: S, dP, dQ, dK, dV = 5 contractions
-        PROFILER.run(f'window_attn_bwd[{B}x{H}x{W} nH{nH} s{shift} {_tag(qkv)} v{variant}]', nbytes, lambda: hip.check(
-            lib.ge_window_attn_bwd(
-                hip.ptr(qkv), hip.ptr(qkv_bias), hip.ptr(bias_table), hip.ptr(d_out), hip.ptr(d_qkv), hip.ptr(d_qb),
-                hip.ptr(d_tab), hip.ptr(ws), B, H, W, nH, shift, scale, hip.dtype_code(qkv), variant, hip.stream()),
-            'ge_window_attn_bwd'), flops=n_wh * 5 * 2 * 49 * 49 * 32)
+        _launch(f'window_attn_bwd[{B}x{H}x{W} nH{nH} s{shift} {_tag(qkv)} v{variant}]', nbytes, 'ge_window_attn_bwd', hip.ptr(qkv), hip.ptr(qkv_bias),
+                hip.ptr(bias_table), hip.ptr(d_out), hip.ptr(d_qkv), hip.ptr(d_qb), hip.ptr(d_tab), hip.ptr(ws), B, H, W, nH, shift, scale,
+                hip.dtype_code(qkv), variant, hip.stream(), flops=n_wh * 5 * 2 * 49 * 49 * 32)
         return d_qkv, d_qb, d_tab, None, None, None, None, None, None
 
 
@@ -148,17 +151,40 @@ def window_attention(qkv, qkv_bias, bias_table, H, W, num_heads, shift, scale, v
 # ------------------------------------------------------------------------------------ MSDA
 MSDA_BINNED_BACKWARD = True     # False: single-pass fp32-atomic scatter (no workspace)
 
-def _levels(spatial_shapes):
-    flat = [int(v) for hw in spatial_shapes for v in hw]
-    return (ctypes.c_int * len(flat))(*flat), len(flat) // 2
+
+class _Levels:
+    """A list of (H, W) maps — the value levels, or the query grid — as the entry points take it: ``hw`` the normalised tuple of tuples,
+    ``n`` their number, ``ptr`` the host int[2 n] (None for no maps).  ``ptr`` is a ctypes.cast result and keeps its array alive."""
+
+    def __init__(self, shapes):
+        self.hw = tuple(tuple(int(v) for v in hw) for hw in shapes)
+        self.n = len(self.hw)
+        flat = [v for hw in self.hw for v in hw]
+        self.ptr = ctypes.cast((ctypes.c_int * len(flat))(*flat), ctypes.c_void_p) if flat else None
+
+
+def _levels(shapes):
+    return shapes if isinstance(shapes, _Levels) else _Levels(shapes)
 
 
 def _query_grid(query_shapes, Nq):
-    if query_shapes is None:
-        return None, 0
-    flat = [int(v) for hw in query_shapes for v in hw]
-    assert sum(flat[i] * flat[i + 1] for i in range(0, len(flat), 2)) == Nq, (query_shapes, Nq)
-    return ctypes.cast((ctypes.c_int * len(flat))(*flat), ctypes.c_void_p), len(flat) // 2
+    """the queries as (H, W) maps in raster order; None = no grid (streaming kernels)"""
+    grid = _levels(() if query_shapes is None else query_shapes)
+    assert query_shapes is None or sum(h * w for h, w in grid.hw) == Nq, (query_shapes, Nq)
+    return grid
+
+
+def _raw_ref(raw, ref, nH, L, P):
+    """-> (the eight-value argument run ``off_raw, off_ld, logit_raw, logit_ld, ref, ref_sb, ref_sq, ref_sl`` of the entry points that read the raw
+    projections, the reference points it addresses).  raw (B, Nq, [nH*L*P*2 offsets | nH*L*P logits]) contiguous: both column ranges of one GEMM
+    output; ref (B, Nq, L, 2), may be an expanded view (stride 0 = broadcast): made fp32 with xy adjacent."""
+    B, Nq, ld = raw.shape
+    ref = ref.to(_f32)
+    assert ref.is_cuda and tuple(ref.shape) == (B, Nq, L, 2), 'reference points (B, Nq, L, 2), may be an expanded view'
+    if ref.stride(3) != 1:
+        ref = ref.contiguous()
+    base = hip.ptr(raw, name='raw')
+    return (base, ld, base + nH * L * P * 2 * _es(raw), ld, ref.data_ptr(), ref.stride(0), ref.stride(1), ref.stride(2)), ref
 
 
 def msda_mode(mode=-1):
@@ -179,17 +205,14 @@ class _MSDeformAttn(torch.autograd.Function):
         B, Nv, nH, D = value.shape
         assert D == 64, 'ge_msda: 64 channels per head'
         _, Nq, _, L, P, _ = loc.shape
-        arr, nl = _levels(spatial_shapes)
-        assert nl == L
-        qarr, nq = _query_grid(query_shapes, Nq)
+        lv, grid = _levels(spatial_shapes), _query_grid(query_shapes, Nq)
+        assert lv.n == L
         out = torch.empty(B, Nq, nH * D, device=value.device, dtype=value.dtype)
         nbytes = value.numel() * _es(value) + loc.numel() * 4 + attw.numel() * 4 + out.numel() * _es(out)
-        PROFILER.run(f'msda_fwd[B{B} Nq{Nq} Nv{Nv} {_tag(value)}{" win" if nq else ""}]', nbytes, lambda: hip.check(
-            hip.lib().ge_msda_fwd(hip.ptr(value, name='value'), ctypes.cast(arr, ctypes.c_void_p), qarr, nq, hip.ptr(loc), hip.ptr(attw),
-                                  hip.ptr(out), B, Nv, Nq, nH, L, P, hip.dtype_code(value), hip.stream()), 'ge_msda_fwd'))
+        _launch(f'msda_fwd[B{B} Nq{Nq} Nv{Nv} {_tag(value)}{" win" if grid.n else ""}]', nbytes, 'ge_msda_fwd', hip.ptr(value, name='value'), lv.ptr,
+                grid.ptr, grid.n, hip.ptr(loc), hip.ptr(attw), hip.ptr(out), B, Nv, Nq, nH, L, P, hip.dtype_code(value), hip.stream())
         ctx.save_for_backward(value, loc, attw)
-        ctx.shapes = tuple(tuple(int(v) for v in hw) for hw in spatial_shapes)
-        ctx.qshapes = None if query_shapes is None else tuple(tuple(int(v) for v in hw) for hw in query_shapes)
+        ctx.geom = (lv, grid)
         return out
 
     @staticmethod
@@ -198,25 +221,21 @@ class _MSDeformAttn(torch.autograd.Function):
         B, Nv, nH, D = value.shape
         _, Nq, _, L, P, _ = loc.shape
         d_out = _c(d_out.to(value.dtype))
-        arr, _ = _levels(ctx.shapes)
-        qarr, nq = _query_grid(ctx.qshapes, Nq)
+        lv, grid = ctx.geom
         d_value = torch.zeros(B, Nv, nH, D, device=value.device, dtype=_f32)
         d_loc = torch.empty_like(loc)
         d_attw = torch.empty_like(attw)
         nbytes = (value.numel() * _es(value) + 2 * loc.numel() * 4 + 2 * attw.numel() * 4 + d_out.numel() * _es(d_out)
                   + d_value.numel() * 4)
-        lib = hip.lib()
-        shapes_p = ctypes.cast(arr, ctypes.c_void_p)
-        ws_bytes = int(lib.ge_msda_bwd_workspace(shapes_p, B, Nv, Nq, nH, L, P)) if MSDA_BINNED_BACKWARD else 0
+        ws_bytes = int(hip.lib().ge_msda_bwd_workspace(lv.ptr, B, Nv, Nq, nH, L, P)) if MSDA_BINNED_BACKWARD else 0
         ws = torch.empty(ws_bytes, device=value.device, dtype=torch.uint8) if ws_bytes else None
         if PROFILER.on and ws_bytes:
             lw_b = value.numel() * _es(value) + 2 * (loc.numel() + attw.numel()) * 4 + d_out.numel() * _es(d_out)
             la_b = (loc.numel() + attw.numel()) * 4
             PROFILER.add_stage_bytes((lw_b, la_b, 0, la_b, d_out.numel() * _es(d_out) + d_value.numel() * 4))
-        PROFILER.run(f'msda_bwd[B{B} Nq{Nq} Nv{Nv} {_tag(value)}{" binned" if ws_bytes else ""}]', nbytes, lambda: hip.check(
-            lib.ge_msda_bwd(hip.ptr(value), shapes_p, qarr, nq, hip.ptr(loc), hip.ptr(attw), hip.ptr(d_out),
-                            hip.ptr(d_value), hip.ptr(d_loc), hip.ptr(d_attw), hip.ptr(ws), ws_bytes, B, Nv, Nq, nH, L, P,
-                            hip.dtype_code(value), hip.stream()), 'ge_msda_bwd'))
+        _launch(f'msda_bwd[B{B} Nq{Nq} Nv{Nv} {_tag(value)}{" binned" if ws_bytes else ""}]', nbytes, 'ge_msda_bwd', hip.ptr(value), lv.ptr, grid.ptr,
+                grid.n, hip.ptr(loc), hip.ptr(attw), hip.ptr(d_out), hip.ptr(d_value), hip.ptr(d_loc), hip.ptr(d_attw), hip.ptr(ws), ws_bytes,
+                B, Nv, Nq, nH, L, P, hip.dtype_code(value), hip.stream())
         return d_value.to(value.dtype), d_loc, d_attw, None, None
 
 
@@ -238,44 +257,32 @@ class _MSDAPrep(torch.autograd.Function):
     def forward(ctx, raw, ref, spatial_shapes, nH, L, P):
         raw = _c(raw)
         B, Nq, ld = raw.shape
-        n_off, n_log = nH * L * P * 2, nH * L * P
-        assert ld == n_off + n_log, 'raw = [sampling_offsets | attention_weights] columns of one GEMM'
-        ref = ref.to(_f32)
-        assert ref.is_cuda and tuple(ref.shape) == (B, Nq, L, 2), 'reference points (B, Nq, L, 2), may be an expanded view'
-        if ref.stride(3) != 1:
-            ref = ref.contiguous()
-        arr, nl = _levels(spatial_shapes)
-        assert nl == L
+        assert ld == nH * L * P * 3, 'raw = [sampling_offsets | attention_weights] columns of one GEMM'
+        lv = _levels(spatial_shapes)
+        assert lv.n == L
+        raw_ref, ref = _raw_ref(raw, ref, nH, L, P)
         loc = torch.empty(B, Nq, nH, L, P, 2, device=raw.device, dtype=_f32)
         attw = torch.empty(B, Nq, nH, L, P, device=raw.device, dtype=_f32)
-        es = _es(raw)
-        base = hip.ptr(raw, name='raw')
-        PROFILER.run(f'msda_prep_fwd[B{B} Nq{Nq} {_tag(raw)}]', raw.numel() * es + (loc.numel() + attw.numel()) * 4, lambda: hip.check(
-            hip.lib().ge_msda_prep_fwd(base, ld, base + n_off * es, ld, ref.data_ptr(), ref.stride(0), ref.stride(1), ref.stride(2),
-                                       ctypes.cast(arr, ctypes.c_void_p), hip.ptr(loc), hip.ptr(attw), B, Nq, nH, L, P,
-                                       hip.dtype_code(raw), hip.stream()), 'ge_msda_prep_fwd'))
+        _launch(f'msda_prep_fwd[B{B} Nq{Nq} {_tag(raw)}]', raw.numel() * _es(raw) + (loc.numel() + attw.numel()) * 4, 'ge_msda_prep_fwd', *raw_ref,
+                lv.ptr, hip.ptr(loc), hip.ptr(attw), B, Nq, nH, L, P, hip.dtype_code(raw), hip.stream())
         ctx.save_for_backward(attw)
-        ctx.meta = (tuple(tuple(int(v) for v in hw) for hw in spatial_shapes), nH, L, P, ld, raw.dtype)
+        ctx.meta = (lv, nH, L, P, ld, raw.dtype)
         return loc, attw
 
     @staticmethod
     def backward(ctx, d_loc, d_attw):
         attw, = ctx.saved_tensors
-        shapes, nH, L, P, ld, dtype = ctx.meta
+        lv, nH, L, P, ld, dtype = ctx.meta
         B, Nq = attw.shape[:2]
         d_loc, d_attw = _c(d_loc.to(_f32)), _c(d_attw.to(_f32))
-        arr, _ = _levels(shapes)
         d_raw = torch.empty(B, Nq, ld, device=attw.device, dtype=dtype)
         fused_ref = ctx.needs_input_grad[1] and nH in (1, 2, 4, 8, 16)
         d_ref = torch.empty(B, Nq, L, 2, device=attw.device, dtype=_f32) if fused_ref else None
         es = _es(d_raw)
         base = hip.ptr(d_raw)
-        n_off = nH * L * P * 2
-        PROFILER.run(f'msda_prep_bwd[B{B} Nq{Nq} {_tag(d_raw)}]', d_raw.numel() * es + (d_loc.numel() + 2 * attw.numel()) * 4,
-                     lambda: hip.check(hip.lib().ge_msda_prep_bwd(
-                         hip.ptr(d_loc), hip.ptr(d_attw), hip.ptr(attw), ctypes.cast(arr, ctypes.c_void_p), base, ld,
-                         base + n_off * es, ld, hip.ptr(d_ref), B, Nq, nH, L, P, hip.dtype_code(d_raw), hip.stream()),
-                         'ge_msda_prep_bwd'))
+        _launch(f'msda_prep_bwd[B{B} Nq{Nq} {_tag(d_raw)}]', d_raw.numel() * es + (d_loc.numel() + 2 * attw.numel()) * 4, 'ge_msda_prep_bwd',
+                hip.ptr(d_loc), hip.ptr(d_attw), hip.ptr(attw), lv.ptr, base, ld, base + nH * L * P * 2 * es, ld, hip.ptr(d_ref), B, Nq, nH, L, P,
+                hip.dtype_code(d_raw), hip.stream())
         if ctx.needs_input_grad[1] and not fused_ref:
             d_ref = d_loc.sum((2, 4))
         return d_raw, d_ref, None, None, None, None
@@ -286,42 +293,76 @@ def msda_prepare(raw, reference_points, spatial_shapes, num_heads, num_levels, n
     return _MSDAPrep.apply(raw, reference_points, spatial_shapes, num_heads, num_levels, num_points)
 
 
+def _window_fwd_raw(value, raw, ref, lv, grid, nH, L, P):
+    """ge_msda_fwd_raw on the query grid ``grid``: -> (out, loc, attw, the fp32 reference points it read); loc / attw are what its backward takes."""
+    B, Nv, _, D = value.shape
+    Nq = raw.shape[1]
+    raw_ref, ref = _raw_ref(raw, ref, nH, L, P)
+    loc = torch.empty(B, Nq, nH, L, P, 2, device=raw.device, dtype=_f32)
+    attw = torch.empty(B, Nq, nH, L, P, device=raw.device, dtype=_f32)
+    out = torch.empty(B, Nq, nH * D, device=value.device, dtype=value.dtype)
+    nbytes = value.numel() * _es(value) + raw.numel() * _es(raw) + (loc.numel() + attw.numel()) * 4 + out.numel() * _es(out)
+    _launch(f'msda_fwd_raw[B{B} Nq{Nq} Nv{Nv} {_tag(value)}]', nbytes, 'ge_msda_fwd_raw', hip.ptr(value, name='value'), lv.ptr, grid.ptr, grid.n,
+            *raw_ref, hip.ptr(loc), hip.ptr(attw), hip.ptr(out), B, Nv, Nq, nH, L, P, hip.dtype_code(value), hip.stream())
+    return out, loc, attw, ref
+
+
+def _window_bwd_raw(value, loc, attw, d_out, lv, grid, d_value=None, want_ref=False):
+    """ge_msda_bwd_raw, the backward of ``_window_fwd_raw`` straight to the gradient of the raw projections: -> (d_raw, d_ref or None).
+    ``d_value`` (fp32, zero-filled) receives the scatter; None skips it (the caller takes d_value from ``_bwd_value_records``)."""
+    B, Nv, nH, _ = value.shape
+    _, Nq, _, L, P, _ = loc.shape
+    ld = nH * L * P * 3
+    d_raw = torch.empty(B, Nq, ld, device=value.device, dtype=value.dtype)
+    d_ref = torch.empty(B, Nq, L, 2, device=value.device, dtype=_f32) if want_ref else None
+    ws_bytes = int(hip.lib().ge_msda_bwd_workspace(lv.ptr, B, Nv, Nq, nH, L, P))
+    ws = torch.empty(ws_bytes, device=value.device, dtype=torch.uint8)
+    es = _es(d_raw)
+    base = hip.ptr(d_raw)
+    nbytes = (value.numel() * _es(value) + (loc.numel() + attw.numel()) * 4 + d_raw.numel() * es + d_out.numel() * _es(d_out)
+              + (0 if d_value is None else d_value.numel() * 4))
+    _launch(f'msda_bwd_raw[B{B} Nq{Nq} Nv{Nv} {_tag(value)}{" lw" if d_value is None else ""}]', nbytes, 'ge_msda_bwd_raw', hip.ptr(value), lv.ptr,
+            grid.ptr, grid.n, hip.ptr(loc), hip.ptr(attw), hip.ptr(d_out), hip.ptr(d_value), base, ld, base + nH * L * P * 2 * es, ld, hip.ptr(d_ref),
+            hip.ptr(ws), ws_bytes, B, Nv, Nq, nH, L, P, hip.dtype_code(value), hip.stream())
+    return d_raw, d_ref
+
+
+def _bwd_value_records(raw, raw_ref, d_out, d_value, lv, nH, L, P, level_mask=15):
+    """d_value through the count / scan / fill / drain record pipeline, binned straight from the raw projections with 8-byte records
+    (ge_msda_bwd_value_raw_levels; bf16, L == 4, P == 8; ``raw_ref``: the argument run of ``_raw_ref``), for the value levels of ``level_mask`` (15: all of them, which is what
+    ge_msda_bwd_value_raw does).  d_value (B, Nv, nH, 64) fp32 is accumulated into; the workspace is this call's own."""
+    B, Nq, _ = raw.shape
+    Nv = d_value.shape[1]
+    n_off = nH * L * P * 2
+    ws_bytes = int(hip.lib().ge_msda_bwd_workspace(lv.ptr, B, Nv, Nq, nH, L, P))
+    ws = torch.empty(ws_bytes, device=raw.device, dtype=torch.uint8)
+    frac = bin(level_mask).count('1') / 4
+    if PROFILER.on:       # algorithmic bytes per stage: count reads the offsets, fill offsets + logits, drain d_out + d_value
+        PROFILER.add_stage_bytes((0, B * Nq * n_off * 2, 0, raw.numel() * 2, int(frac * d_out.numel() * 2) + d_value.numel() * 4))
+    _launch(f'msda_bwd_value_raw[B{B} Nq{Nq} Nv{Nv}{"" if level_mask == 15 else f" levels {level_mask:04b}"}]',
+            B * Nq * n_off * 2 + raw.numel() * 2 + d_out.numel() * 2 + d_value.numel() * 4, 'ge_msda_bwd_value_raw_levels', lv.ptr,
+            *raw_ref, hip.ptr(d_out), hip.ptr(d_value), hip.ptr(ws), ws_bytes, level_mask, B, Nv, Nq, nH, L, P,
+            hip.dtype_code(d_out), hip.stream())
+
+
 class _MSDeformAttnRaw(torch.autograd.Function):
     """prepare + sampling in one kernel each way (ge_msda_fwd_raw / ge_msda_bwd_raw)."""
 
     @staticmethod
     def forward(ctx, value, raw, ref, spatial_shapes, query_shapes, nH, L, P):
         value, raw = _c(value), _c(raw)
-        B, Nv, _, D = value.shape
-        _, Nq, ld = raw.shape
-        n_off, n_log = nH * L * P * 2, nH * L * P
-        assert D == 64 and ld == n_off + n_log and raw.dtype == value.dtype
-        ref = ref.to(_f32)
-        assert ref.is_cuda and tuple(ref.shape) == (B, Nq, L, 2)
-        if ref.stride(3) != 1:
-            ref = ref.contiguous()
-        arr, _ = _levels(spatial_shapes)
-        qarr, nq = _query_grid(query_shapes, Nq)
-        loc = torch.empty(B, Nq, nH, L, P, 2, device=raw.device, dtype=_f32)
-        attw = torch.empty(B, Nq, nH, L, P, device=raw.device, dtype=_f32)
-        out = torch.empty(B, Nq, nH * D, device=value.device, dtype=value.dtype)
-        es = _es(raw)
-        base = hip.ptr(raw, name='raw')
-        nbytes = value.numel() * _es(value) + raw.numel() * es + (loc.numel() + attw.numel()) * 4 + out.numel() * _es(out)
-        PROFILER.run(f'msda_fwd_raw[B{B} Nq{Nq} Nv{Nv} {_tag(value)}]', nbytes, lambda: hip.check(hip.lib().ge_msda_fwd_raw(
-            hip.ptr(value, name='value'), ctypes.cast(arr, ctypes.c_void_p), qarr, nq, base, ld, base + n_off * es, ld, ref.data_ptr(),
-            ref.stride(0), ref.stride(1), ref.stride(2), hip.ptr(loc), hip.ptr(attw), hip.ptr(out), B, Nv, Nq, nH, L, P,
-            hip.dtype_code(value), hip.stream()), 'ge_msda_fwd_raw'))
+        assert value.shape[3] == 64 and raw.shape[2] == nH * L * P * 3 and raw.dtype == value.dtype
+        lv, grid = _levels(spatial_shapes), _query_grid(query_shapes, raw.shape[1])
+        out, loc, attw, ref = _window_fwd_raw(value, raw, ref, lv, grid, nH, L, P)
         # bf16: d_value is binned straight from the raw projections with 8-byte records (ge_msda_bwd_value_raw: half the record bytes
         # of the fp32 loc / attw path in fill and drain), so the backward needs them too
         ctx.value_from_raw = (value.dtype == torch.bfloat16 and L == 4 and P == 8 and 'msda_value_raw' not in DISABLED
-                              and max(max(hw) for hw in spatial_shapes) <= 8191)
+                              and max(max(hw) for hw in lv.hw) <= 8191)
         if ctx.value_from_raw:
             ctx.save_for_backward(value, loc, attw, raw, ref)
         else:
             ctx.save_for_backward(value, loc, attw)
-        ctx.meta = (tuple(tuple(int(v) for v in hw) for hw in spatial_shapes), tuple(tuple(int(v) for v in hw) for hw in query_shapes),
-                    nH, L, P, ld, raw.dtype)
+        ctx.meta = (lv, grid, nH, L, P)
         ctx.last_loc = loc
         return out
 
@@ -329,42 +370,17 @@ class _MSDeformAttnRaw(torch.autograd.Function):
     def backward(ctx, d_out):
         value, loc, attw = ctx.saved_tensors[:3]
         split = ctx.value_from_raw
-        shapes, qshapes, nH, L, P, ld, dtype = ctx.meta
-        B, Nv, _, D = value.shape
-        Nq = loc.shape[1]
+        lv, grid, nH, L, P = ctx.meta
         d_out = _c(d_out.to(value.dtype))
-        arr, _ = _levels(shapes)
-        qarr, nq = _query_grid(qshapes, Nq)
-        shapes_p = ctypes.cast(arr, ctypes.c_void_p)
-        lib = hip.lib()
-        d_value = torch.zeros(B, Nv, nH, D, device=value.device, dtype=_f32)
-        d_raw = torch.empty(B, Nq, ld, device=value.device, dtype=dtype)
-        d_ref = torch.empty(B, Nq, L, 2, device=value.device, dtype=_f32) if ctx.needs_input_grad[2] else None
-        ws_bytes = int(lib.ge_msda_bwd_workspace(shapes_p, B, Nv, Nq, nH, L, P))
-        ws = torch.empty(ws_bytes, device=value.device, dtype=torch.uint8)
-        es = _es(d_raw)
-        base = hip.ptr(d_raw)
-        n_off = nH * L * P * 2
+        d_value = torch.zeros(value.shape, device=value.device, dtype=_f32)
+        d_raw, d_ref = _window_bwd_raw(value, loc, attw, d_out, lv, grid, None if split else d_value, ctx.needs_input_grad[2])
         if PROFILER.on:
-            lw_b = value.numel() * _es(value) + (loc.numel() + attw.numel()) * 4 + d_raw.numel() * es + d_out.numel() * _es(d_out)
+            lw_b = value.numel() * _es(value) + (loc.numel() + attw.numel()) * 4 + d_raw.numel() * _es(d_raw) + d_out.numel() * _es(d_out)
             la_b = (loc.numel() + attw.numel()) * 4
             PROFILER.add_stage_bytes((lw_b, 0, 0, 0, 0) if split else (lw_b, la_b, 0, la_b, d_out.numel() * _es(d_out) + d_value.numel() * 4))
-        nbytes = (value.numel() * _es(value) + (loc.numel() + attw.numel()) * 4 + d_raw.numel() * es + d_out.numel() * _es(d_out)
-                  + (0 if split else d_value.numel() * 4))
-        PROFILER.run(f'msda_bwd_raw[B{B} Nq{Nq} Nv{Nv} {_tag(value)}{" lw" if split else ""}]', nbytes, lambda: hip.check(lib.ge_msda_bwd_raw(
-            hip.ptr(value), shapes_p, qarr, nq, hip.ptr(loc), hip.ptr(attw), hip.ptr(d_out), None if split else hip.ptr(d_value), base, ld,
-            base + n_off * es, ld, hip.ptr(d_ref), hip.ptr(ws), ws_bytes, B, Nv, Nq, nH, L, P, hip.dtype_code(value), hip.stream()),
-            'ge_msda_bwd_raw'))
         if split:
             raw, ref = ctx.saved_tensors[3:]
-            rbase = hip.ptr(raw)
-            if PROFILER.on:
-                PROFILER.add_stage_bytes((0, B * Nq * n_off * 2, 0, raw.numel() * 2, d_out.numel() * 2 + d_value.numel() * 4))
-            PROFILER.run(f'msda_bwd_value_raw[B{B} Nq{Nq} Nv{Nv}]', B * Nq * n_off * 2 + raw.numel() * 2 + d_out.numel() * 2 + d_value.numel() * 4,
-                         lambda: hip.check(lib.ge_msda_bwd_value_raw(
-                             shapes_p, rbase, ld, rbase + n_off * 2, ld, ref.data_ptr(), ref.stride(0), ref.stride(1), ref.stride(2),
-                             hip.ptr(d_out), hip.ptr(d_value), hip.ptr(ws), ws_bytes, B, Nv, Nq, nH, L, P, hip.dtype_code(value),
-                             hip.stream()), 'ge_msda_bwd_value_raw'))
+            _bwd_value_records(raw, _raw_ref(raw, ref, nH, L, P)[0], d_out, d_value, lv, nH, L, P)
         return d_value.to(value.dtype), d_raw, d_ref, None, None, None, None, None
 
 
@@ -378,10 +394,9 @@ def ms_deform_attn_raw(value, raw, reference_points, spatial_shapes, query_shape
     fused = ('msda_raw' not in DISABLED and query_shapes is not None and MSDA_BINNED_BACKWARD and value.is_cuda and raw.dtype == value.dtype
              and value.dtype in (_f32, torch.bfloat16))
     if fused:
-        arr, _ = _levels(spatial_shapes)
-        qarr, nq = _query_grid(query_shapes, Nq)
-        fused = bool(hip.lib().ge_msda_raw_supported(ctypes.cast(arr, ctypes.c_void_p), qarr, nq, B, Nv, Nq, num_heads, num_levels, num_points))
-        fused = fused and int(hip.lib().ge_msda_bwd_workspace(ctypes.cast(arr, ctypes.c_void_p), B, Nv, Nq, num_heads, num_levels, num_points)) > 0
+        lv, grid = _levels(spatial_shapes), _query_grid(query_shapes, Nq)
+        fused = bool(hip.lib().ge_msda_raw_supported(lv.ptr, grid.ptr, grid.n, B, Nv, Nq, num_heads, num_levels, num_points))
+        fused = fused and int(hip.lib().ge_msda_bwd_workspace(lv.ptr, B, Nv, Nq, num_heads, num_levels, num_points)) > 0
     if not fused:
         loc, attw = msda_prepare(raw, reference_points, spatial_shapes, num_heads, num_levels, num_points)
         return ms_deform_attn(value, spatial_shapes, loc, attw, query_shapes)
@@ -430,24 +445,17 @@ def msda_fwd_mm(value, raw, ref, spatial_shapes, order=None, want_loc=False, nH=
     value, raw = _c(value), _c(raw)
     B, Nv, _, D = value.shape
     _, Nq, ld = raw.shape
-    n_off = nH * L * P * 2
-    assert D == 64 and ld == n_off + nH * L * P and raw.dtype == value.dtype == torch.bfloat16
-    ref = ref.to(_f32)
-    assert ref.is_cuda and tuple(ref.shape) == (B, Nq, L, 2)
-    if ref.stride(3) != 1:
-        ref = ref.contiguous()
-    arr, _ = _levels(spatial_shapes)
+    assert D == 64 and ld == nH * L * P * 3 and raw.dtype == value.dtype == torch.bfloat16
+    raw_ref, ref = _raw_ref(raw, ref, nH, L, P)
+    lv = _levels(spatial_shapes)
     out = torch.empty(B, Nq, nH * D, device=value.device, dtype=value.dtype)
     loc = torch.empty(B, Nq, nH, L, P, 2, device=raw.device, dtype=_f32) if want_loc else None
     attw = torch.empty(B, Nq, nH, L, P, device=raw.device, dtype=_f32) if want_loc else None
     if order is not None:
         assert order.dtype == torch.int32 and order.is_cuda and order.numel() == Nq and order.is_contiguous()
-    base = hip.ptr(raw, name='raw')
     nbytes = value.numel() * 2 + raw.numel() * 2 + out.numel() * 2 + ((loc.numel() + attw.numel()) * 4 if want_loc else 0)
-    PROFILER.run(f'msda_mm_fwd_k[B{B} Nq{Nq} Nv{Nv}]', nbytes, lambda: hip.check(hip.lib().ge_msda_fwd_mm(
-        hip.ptr(value, name='value'), ctypes.cast(arr, ctypes.c_void_p), base, ld, base + n_off * 2, ld, ref.data_ptr(),
-        ref.stride(0), ref.stride(1), ref.stride(2), hip.ptr(order), hip.ptr(loc), hip.ptr(attw), hip.ptr(out), B, Nv, Nq, nH, L, P,
-        hip.dtype_code(value), hip.stream()), 'ge_msda_fwd_mm'))
+    _launch(f'msda_mm_fwd_k[B{B} Nq{Nq} Nv{Nv}]', nbytes, 'ge_msda_fwd_mm', hip.ptr(value, name='value'), lv.ptr, *raw_ref, hip.ptr(order), hip.ptr(loc),
+            hip.ptr(attw), hip.ptr(out), B, Nv, Nq, nH, L, P, hip.dtype_code(value), hip.stream())
     return (out, loc, attw) if want_loc else out
 
 
@@ -528,28 +536,24 @@ class _MSDeformAttnMM(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, value, raw, ref, order, spatial_shapes, nH, L, P):
-        out = msda_fwd_mm(value, raw, ref, spatial_shapes, order, want_loc=False, nH=nH, L=L, P=P)    # no fp32 loc / attw tensors exist
+        lv = _levels(spatial_shapes)
+        out = msda_fwd_mm(value, raw, ref, lv, order, want_loc=False, nH=nH, L=L, P=P)    # no fp32 loc / attw tensors exist
         ctx.save_for_backward(value, raw, ref, order)
-        ctx.meta = (tuple(tuple(int(v) for v in hw) for hw in spatial_shapes), nH, L, P)
+        ctx.meta = (lv, nH, L, P)
         return out
 
     @staticmethod
     def backward(ctx, d_out):
         value, raw, ref, order = ctx.saved_tensors
-        shapes, nH, L, P = ctx.meta
+        lv, nH, L, P = ctx.meta
         value, raw = _c(value), _c(raw)
         B, Nv, _, D = value.shape
         _, Nq, ld = raw.shape
-        n_off = nH * L * P * 2
         d_out = _c(d_out.to(value.dtype))
-        ref = ref.to(_f32)
-        if ref.stride(3) != 1:
-            ref = ref.contiguous()
-        arr, _ = _levels(shapes)
-        shapes_p = ctypes.cast(arr, ctypes.c_void_p)
+        raw_ref, ref = _raw_ref(raw, ref, nH, L, P)
         lib = hip.lib()
         d_raw = torch.empty(B, Nq, ld, device=value.device, dtype=raw.dtype)
-        base, dbase = hip.ptr(raw), hip.ptr(d_raw)
+        dbase = hip.ptr(d_raw)
         nb_lw = value.numel() * 2 + raw.numel() * 2 + d_raw.numel() * 2 + d_out.numel() * 2
         # round 5: d_value as the transposed contraction dV_window = C^T dO (ge_msda_bwd_value_mm); the d_raw kernel leaves the per-tile
         # tap boxes in the shared workspace.  Its cost depends on the geometry (how compact the windows of consecutive query tiles are), the
@@ -563,57 +567,44 @@ class _MSDeformAttnMM(torch.autograd.Function):
         # (its kernel addresses rows with 32-bit byte offsets: tensors of 4 GB and more keep the other two kernels)
         use_vs = (want_dv and os.environ.get('GE_MSDA_VALUE') == 'vs' and B * Nq * ld * 2 < 2 ** 32 and B * Nq * nH * D * 2 < 2 ** 32
                   and 0 <= ref.stride(1) and Nq * ref.stride(1) * 4 < 2 ** 32)
-        vs_ws_bytes = int(lib.ge_msda_bwd_vs_workspace(shapes_p, B, Nv, Nq, nH, L, P)) if use_vs else 0
+        vs_ws_bytes = int(lib.ge_msda_bwd_vs_workspace(lv.ptr, B, Nv, Nq, nH, L, P)) if use_vs else 0
         mm_ws_bytes = int(lib.ge_msda_bwd_mm_workspace(B, Nq, nH, L)) if (want_dv and 'msda_value_mm' not in DISABLED) else 0
         if vs_ws_bytes:
             mm_ws_bytes = vs_ws_bytes                 # its head is the ge_msda_bwd_mm_workspace layout (tap boxes, run lists)
         mm_ws = torch.empty(mm_ws_bytes, device=value.device, dtype=torch.uint8) if mm_ws_bytes else None
-        PROFILER.run(f'msda_mm_bwd_lw_k[B{B} Nq{Nq} Nv{Nv}]', nb_lw, lambda: hip.check(lib.ge_msda_bwd_lw_mm(
-            hip.ptr(value), shapes_p, base, ld, base + n_off * 2, ld, ref.data_ptr(), ref.stride(0), ref.stride(1), ref.stride(2),
-            hip.ptr(order), hip.ptr(d_out), dbase, ld, dbase + n_off * 2, ld, hip.ptr(mm_ws), B, Nv, Nq, nH, L, P, hip.dtype_code(value),
-            hip.stream()), 'ge_msda_bwd_lw_mm'))
+        _launch(f'msda_mm_bwd_lw_k[B{B} Nq{Nq} Nv{Nv}]', nb_lw, 'ge_msda_bwd_lw_mm', hip.ptr(value), lv.ptr, *raw_ref, hip.ptr(order), hip.ptr(d_out),
+                dbase, ld, dbase + nH * L * P * 2 * 2, ld, hip.ptr(mm_ws), B, Nv, Nq, nH, L, P, hip.dtype_code(value), hip.stream())
         d_ref = None
         if ctx.needs_input_grad[2]:
             d_ref = torch.empty(B, Nq, L, 2, device=value.device, dtype=_f32)
-            hip.check(lib.ge_msda_dref(dbase, ld, shapes_p, hip.ptr(d_ref), B * Nq, nH, L, P, hip.dtype_code(value), hip.stream()), 'ge_msda_dref')
+            hip.call('ge_msda_dref', dbase, ld, lv.ptr, hip.ptr(d_ref), B * Nq, nH, L, P, hip.dtype_code(value), hip.stream())
         d_value = None
         if want_dv:
             d_value = torch.zeros(B, Nv, nH, D, device=value.device, dtype=_f32)
             if vs_ws_bytes:
-                PROFILER.run(f'msda_mm_bwd_vs_k[B{B} Nq{Nq} Nv{Nv}]', raw.numel() * 2 + d_out.numel() * 2 + d_value.numel() * 4, lambda: hip.check(
-                    lib.ge_msda_bwd_value_vs(shapes_p, base, ld, base + n_off * 2, ld, ref.data_ptr(), ref.stride(0), ref.stride(1), ref.stride(2), hip.ptr(order),
-                                             hip.ptr(d_out), hip.ptr(d_value), hip.ptr(mm_ws), mm_ws_bytes, B, Nv, Nq, nH, L, P, hip.dtype_code(value), hip.stream()),
-                    'ge_msda_bwd_value_vs'))
+                _launch(f'msda_mm_bwd_vs_k[B{B} Nq{Nq} Nv{Nv}]', raw.numel() * 2 + d_out.numel() * 2 + d_value.numel() * 4, 'ge_msda_bwd_value_vs', lv.ptr,
+                        *raw_ref, hip.ptr(order), hip.ptr(d_out), hip.ptr(d_value), hip.ptr(mm_ws), mm_ws_bytes, B, Nv, Nq, nH, L, P,
+                        hip.dtype_code(value), hip.stream())
                 return d_value.to(value.dtype), d_raw, d_ref, None, None, None, None, None
-            rec_ws_bytes = int(lib.ge_msda_bwd_workspace(shapes_p, B, Nv, Nq, nH, L, P))
-            choice, mm_mask = _mm_value_choice((B, Nq, Nv, nH, shapes, str(value.device)), mm_ws is not None, rec_ws_bytes > 0)
+            rec_ws_bytes = int(lib.ge_msda_bwd_workspace(lv.ptr, B, Nv, Nq, nH, L, P))
+            choice, mm_mask = _mm_value_choice((B, Nq, Nv, nH, lv.hw, str(value.device)), mm_ws is not None, rec_ws_bytes > 0)
             rec_mask = 15 & ~mm_mask
 
-            def value_mm(dv, mask):
-                return hip.check(lib.ge_msda_bwd_value_mm(
-                    shapes_p, base, ld, base + n_off * 2, ld, ref.data_ptr(), ref.stride(0), ref.stride(1), ref.stride(2), hip.ptr(order),
-                    hip.ptr(d_out), hip.ptr(dv), hip.ptr(mm_ws), mm_ws_bytes, mask, B, Nv, Nq, nH, L, P, hip.dtype_code(value), hip.stream()),
-                    'ge_msda_bwd_value_mm')
+            def value_mm(dv, mask):         # the argument list of ge_msda_bwd_value_mm
+                return (lv.ptr, *raw_ref, hip.ptr(order), hip.ptr(d_out), hip.ptr(dv), hip.ptr(mm_ws), mm_ws_bytes, mask, B, Nv, Nq, nH, L, P,
+                        hip.dtype_code(value), hip.stream())
             if mm_mask:
                 # algorithmic bytes: the raw projections + d_out read once per level, those levels' d_value rows written once
-                lv_rows = sum(h * w for l, (h, w) in enumerate(shapes) if (mm_mask >> l) & 1)
-                PROFILER.run(f'msda_mm_bwd_v_k[B{B} Nq{Nq} Nv{Nv} levels {mm_mask:04b}]',
-                             bin(mm_mask).count('1') * (raw.numel() // 2 + d_out.numel() * 2 // 4) + B * lv_rows * nH * D * 4, lambda: value_mm(d_value, mm_mask))
+                lv_rows = sum(h * w for l, (h, w) in enumerate(lv.hw) if (mm_mask >> l) & 1)
+                _launch(f'msda_mm_bwd_v_k[B{B} Nq{Nq} Nv{Nv} levels {mm_mask:04b}]',
+                        bin(mm_mask).count('1') * (raw.numel() // 2 + d_out.numel() * 2 // 4) + B * lv_rows * nH * D * 4, 'ge_msda_bwd_value_mm',
+                        *value_mm(d_value, mm_mask))
             elif mm_ws is not None and choice.wants_stats():
-                value_mm(None, 0)                   # run statistics only (~50 us): keeps the choice informed while the record path runs
+                hip.call('ge_msda_bwd_value_mm', *value_mm(None, 0))     # run statistics only (~50 us): keeps the choice informed while the record path runs
             if rec_mask:
                 if rec_ws_bytes <= 0:
                     raise RuntimeError('ms_deform_attn_mm backward: neither the MFMA d_value kernel nor the binned path covers this geometry')
-                ws = torch.empty(rec_ws_bytes, device=value.device, dtype=torch.uint8)
-                frac = bin(rec_mask).count('1') / 4
-                if PROFILER.on:       # algorithmic bytes per stage: count reads the offsets, fill offsets + logits, drain d_out + d_value
-                    PROFILER.add_stage_bytes((0, B * Nq * n_off * 2, 0, raw.numel() * 2, int(frac * d_out.numel() * 2) + d_value.numel() * 4))
-                PROFILER.run(f'msda_bwd_value_raw[B{B} Nq{Nq} Nv{Nv}{"" if rec_mask == 15 else f" levels {rec_mask:04b}"}]',
-                             B * Nq * n_off * 2 + raw.numel() * 2 + d_out.numel() * 2 + d_value.numel() * 4,
-                             lambda: hip.check(lib.ge_msda_bwd_value_raw_levels(
-                                 shapes_p, base, ld, base + n_off * 2, ld, ref.data_ptr(), ref.stride(0), ref.stride(1), ref.stride(2),
-                                 hip.ptr(d_out), hip.ptr(d_value), hip.ptr(ws), rec_ws_bytes, rec_mask, B, Nv, Nq, nH, L, P, hip.dtype_code(value),
-                                 hip.stream()), 'ge_msda_bwd_value_raw_levels'))
+                _bwd_value_records(raw, raw_ref, d_out, d_value, lv, nH, L, P, rec_mask)
             if mm_ws is not None:
                 choice.observe(mm_ws, int(lib.ge_msda_bwd_mm_stats_offset(B, Nq, nH, L)), B * Nq * nH)
             d_value = d_value.to(value.dtype)
@@ -623,9 +614,8 @@ class _MSDeformAttnMM(torch.autograd.Function):
 def msda_mm_supported(value, raw, spatial_shapes, nH, L, P):
     if not (value.is_cuda and value.dtype == torch.bfloat16 and raw.dtype == torch.bfloat16 and value.shape[-1] == 64):
         return False
-    arr, _ = _levels(spatial_shapes)
     B, Nv = value.shape[:2]
-    return bool(hip.lib().ge_msda_mm_supported(ctypes.cast(arr, ctypes.c_void_p), B, Nv, raw.shape[1], nH, L, P, hip.GE_BF16))
+    return bool(hip.lib().ge_msda_mm_supported(_levels(spatial_shapes).ptr, B, Nv, raw.shape[1], nH, L, P, hip.GE_BF16))
 
 
 def ms_deform_attn_mm(value, raw, reference_points, spatial_shapes, order, num_heads=8, num_levels=4, num_points=8):
@@ -647,83 +637,45 @@ class _MSDeformAttnSelfSplit(torch.autograd.Function):
         value, raw = _c(value), _c(raw)
         B, Nv, _, D = value.shape
         _, Nq, ld = raw.shape
-        n_off = nH * L * P * 2
-        assert D == 64 and ld == n_off + nH * L * P and raw.dtype == value.dtype == torch.bfloat16 and 0 < n_fine < Nq
-        ref = ref.to(_f32)
-        if ref.stride(3) != 1:
-            ref = ref.contiguous()
-        shapes = tuple(tuple(int(v) for v in hw) for hw in spatial_shapes)
-        arr, _ = _levels(shapes)
-        shapes_p = ctypes.cast(arr, ctypes.c_void_p)
-        lib = hip.lib()
+        assert D == 64 and ld == nH * L * P * 3 and raw.dtype == value.dtype == torch.bfloat16 and 0 < n_fine < Nq
+        raw_ref, ref = _raw_ref(raw, ref, nH, L, P)
+        lv = _levels(spatial_shapes)
         out = torch.empty(B, Nq, nH * D, device=value.device, dtype=value.dtype)
-        base = hip.ptr(raw, name='raw')
         nc = Nq - n_fine
-        PROFILER.run(f'msda_mm_fwd_k[B{B} Nq{n_fine}/{Nq} Nv{Nv}]', value.numel() * 2 + B * n_fine * (ld + nH * D) * 2, lambda: hip.check(lib.ge_msda_fwd_mm_part(
-            hip.ptr(value, name='value'), shapes_p, base, ld, base + n_off * 2, ld, ref.data_ptr(), ref.stride(0), ref.stride(1), ref.stride(2),
-            hip.ptr(order_fine), hip.ptr(out), B, Nv, n_fine, Nq, nH, L, P, hip.GE_BF16, hip.stream()), 'ge_msda_fwd_mm_part'))
+        _launch(f'msda_mm_fwd_k[B{B} Nq{n_fine}/{Nq} Nv{Nv}]', value.numel() * 2 + B * n_fine * (ld + nH * D) * 2, 'ge_msda_fwd_mm_part',
+                hip.ptr(value, name='value'), lv.ptr, *raw_ref, hip.ptr(order_fine), hip.ptr(out), B, Nv, n_fine, Nq, nH, L, P, hip.GE_BF16, hip.stream())
         # coarse-level queries: contiguous copies of their rows for the window kernels (whose row addressing is B * Nq)
         coarse_shapes = []
         acc = 0
-        for hw in shapes:
+        for hw in lv.hw:
             acc += hw[0] * hw[1]
             if acc > n_fine:
                 coarse_shapes.append(hw)
         assert sum(h * w for h, w in coarse_shapes) == nc, 'n_fine must end on a level boundary'
-        raw_c = raw[:, n_fine:].contiguous()
-        ref_c = ref[:, n_fine:]
-        qarr, nq = _query_grid(coarse_shapes, nc)
-        loc = torch.empty(B, nc, nH, L, P, 2, device=raw.device, dtype=_f32)
-        attw = torch.empty(B, nc, nH, L, P, device=raw.device, dtype=_f32)
-        out_c = torch.empty(B, nc, nH * D, device=value.device, dtype=value.dtype)
-        cbase = hip.ptr(raw_c)
-        PROFILER.run(f'msda_fwd_raw[B{B} Nq{nc} Nv{Nv} bf16]', value.numel() * 2 + raw_c.numel() * 2 + (loc.numel() + attw.numel()) * 4 + out_c.numel() * 2,
-                     lambda: hip.check(lib.ge_msda_fwd_raw(hip.ptr(value), shapes_p, qarr, nq, cbase, ld, cbase + n_off * 2, ld, ref_c.data_ptr(), ref_c.stride(0),
-                                                           ref_c.stride(1), ref_c.stride(2), hip.ptr(loc), hip.ptr(attw), hip.ptr(out_c), B, Nv, nc, nH, L, P,
-                                                           hip.GE_BF16, hip.stream()), 'ge_msda_fwd_raw'))
-        out[:, n_fine:] = out_c
+        grid = _query_grid(coarse_shapes, nc)
+        out[:, n_fine:], loc, attw, _ = _window_fwd_raw(value, raw[:, n_fine:].contiguous(), ref[:, n_fine:], lv, grid, nH, L, P)
         ctx.save_for_backward(value, raw, ref, order_fine, loc, attw)
-        ctx.meta = (shapes, tuple(coarse_shapes), n_fine, nH, L, P)
+        ctx.meta = (lv, grid, n_fine, nH, L, P)
         return out
 
     @staticmethod
     def backward(ctx, d_out):
         value, raw, ref, order_fine, loc, attw = ctx.saved_tensors
-        shapes, coarse_shapes, n_fine, nH, L, P = ctx.meta
+        lv, grid, n_fine, nH, L, P = ctx.meta
         B, Nv, _, D = value.shape
         _, Nq, ld = raw.shape
-        nc = Nq - n_fine
-        n_off = nH * L * P * 2
         d_out = _c(d_out.to(value.dtype))
-        arr, _ = _levels(shapes)
-        shapes_p = ctypes.cast(arr, ctypes.c_void_p)
-        lib = hip.lib()
+        raw_ref, _ = _raw_ref(raw, ref, nH, L, P)
         d_raw = torch.empty(B, Nq, ld, device=value.device, dtype=raw.dtype)
-        base, dbase = hip.ptr(raw), hip.ptr(d_raw)
-        PROFILER.run(f'msda_mm_bwd_lw_k[B{B} Nq{n_fine}/{Nq} Nv{Nv}]', value.numel() * 2 + B * n_fine * (2 * ld + nH * D) * 2, lambda: hip.check(lib.ge_msda_bwd_lw_mm_part(
-            hip.ptr(value), shapes_p, base, ld, base + n_off * 2, ld, ref.data_ptr(), ref.stride(0), ref.stride(1), ref.stride(2), hip.ptr(order_fine),
-            hip.ptr(d_out), dbase, ld, dbase + n_off * 2, ld, B, Nv, n_fine, Nq, nH, L, P, hip.GE_BF16, hip.stream()), 'ge_msda_bwd_lw_mm_part'))
-        d_out_c = d_out[:, n_fine:].contiguous()
-        d_raw_c = torch.empty(B, nc, ld, device=value.device, dtype=raw.dtype)
-        qarr, nq = _query_grid(coarse_shapes, nc)
-        ws_bytes = int(lib.ge_msda_bwd_workspace(shapes_p, B, Nv, nc, nH, L, P))
-        ws = torch.empty(ws_bytes, device=value.device, dtype=torch.uint8)
-        cb = hip.ptr(d_raw_c)
-        PROFILER.run(f'msda_bwd_raw[B{B} Nq{nc} Nv{Nv} bf16 lw]', value.numel() * 2 + (loc.numel() + attw.numel()) * 4 + d_raw_c.numel() * 2 + d_out_c.numel() * 2,
-                     lambda: hip.check(lib.ge_msda_bwd_raw(hip.ptr(value), shapes_p, qarr, nq, hip.ptr(loc), hip.ptr(attw), hip.ptr(d_out_c), None, cb, ld, cb + n_off * 2, ld,
-                                                           None, hip.ptr(ws), ws_bytes, B, Nv, nc, nH, L, P, hip.GE_BF16, hip.stream()), 'ge_msda_bwd_raw'))
-        d_raw[:, n_fine:] = d_raw_c
+        dbase = hip.ptr(d_raw)
+        _launch(f'msda_mm_bwd_lw_k[B{B} Nq{n_fine}/{Nq} Nv{Nv}]', value.numel() * 2 + B * n_fine * (2 * ld + nH * D) * 2, 'ge_msda_bwd_lw_mm_part',
+                hip.ptr(value), lv.ptr, *raw_ref, hip.ptr(order_fine), hip.ptr(d_out), dbase, ld, dbase + nH * L * P * 2 * 2, ld, B, Nv, n_fine, Nq,
+                nH, L, P, hip.GE_BF16, hip.stream())
+        d_raw[:, n_fine:], _ = _window_bwd_raw(value, loc, attw, d_out[:, n_fine:].contiguous(), lv, grid)
         d_value = None
         if ctx.needs_input_grad[0]:
             d_value = torch.zeros(B, Nv, nH, D, device=value.device, dtype=_f32)
-            ws_bytes = int(lib.ge_msda_bwd_workspace(shapes_p, B, Nv, Nq, nH, L, P))
-            ws = torch.empty(ws_bytes, device=value.device, dtype=torch.uint8)
-            if PROFILER.on:
-                PROFILER.add_stage_bytes((0, B * Nq * n_off * 2, 0, raw.numel() * 2, d_out.numel() * 2 + d_value.numel() * 4))
-            PROFILER.run(f'msda_bwd_value_raw[B{B} Nq{Nq} Nv{Nv}]', B * Nq * n_off * 2 + raw.numel() * 2 + d_out.numel() * 2 + d_value.numel() * 4,
-                         lambda: hip.check(lib.ge_msda_bwd_value_raw(shapes_p, base, ld, base + n_off * 2, ld, ref.data_ptr(), ref.stride(0), ref.stride(1), ref.stride(2),
-                                                                     hip.ptr(d_out), hip.ptr(d_value), hip.ptr(ws), ws_bytes, B, Nv, Nq, nH, L, P, hip.GE_BF16, hip.stream()),
-                                           'ge_msda_bwd_value_raw'))
+            _bwd_value_records(raw, raw_ref, d_out, d_value, lv, nH, L, P)
             d_value = d_value.to(value.dtype)
         return d_value, d_raw, None, None, None, None, None, None, None
 
@@ -733,30 +685,29 @@ def msda_self_split_ok(value, raw, spatial_shapes, query_shapes, nH, L, P):
     kernel involved supports the geometry.  ``GE_DISABLE=msda_self_split`` keeps all queries on the window kernels."""
     if 'msda_self_split' in DISABLED or 'msda_mm' in DISABLED or 'msda_raw' in DISABLED or 'msda_value_raw' in DISABLED or not MSDA_BINNED_BACKWARD:
         return False
-    shapes = [tuple(int(v) for v in hw) for hw in spatial_shapes]
-    if query_shapes is None or [tuple(int(v) for v in hw) for hw in query_shapes] != shapes or len(shapes) < 2 or L != 4 or P != 8:
+    lv = _levels(spatial_shapes)
+    shapes = lv.hw
+    if query_shapes is None or _levels(query_shapes).hw != shapes or len(shapes) < 2 or L != 4 or P != 8:
         return False
     if not (value.is_cuda and value.dtype == torch.bfloat16 and raw.dtype == torch.bfloat16 and value.shape[-1] == 64 and max(max(hw) for hw in shapes) <= 8191):
         return False
     B, Nv = value.shape[:2]
     Nq = raw.shape[1]
     n_fine = shapes[0][0] * shapes[0][1]
-    if Nq != Nv or not msda_mm_supported(value, raw, shapes, nH, L, P):
+    if Nq != Nv or not msda_mm_supported(value, raw, lv, nH, L, P):
         return False
     lib = hip.lib()
-    arr, _ = _levels(shapes)
-    sp = ctypes.cast(arr, ctypes.c_void_p)
-    qarr, nq = _query_grid(shapes[1:], Nq - n_fine)
-    return (bool(lib.ge_msda_raw_supported(sp, qarr, nq, B, Nv, Nq - n_fine, nH, L, P)) and int(lib.ge_msda_bwd_workspace(sp, B, Nv, Nq - n_fine, nH, L, P)) > 0
-            and int(lib.ge_msda_bwd_workspace(sp, B, Nv, Nq, nH, L, P)) > 0)
+    grid = _query_grid(shapes[1:], Nq - n_fine)
+    return (bool(lib.ge_msda_raw_supported(lv.ptr, grid.ptr, grid.n, B, Nv, Nq - n_fine, nH, L, P)) and int(lib.ge_msda_bwd_workspace(lv.ptr, B, Nv, Nq - n_fine, nH, L, P)) > 0
+            and int(lib.ge_msda_bwd_workspace(lv.ptr, B, Nv, Nq, nH, L, P)) > 0)
 
 
 def ms_deform_attn_self_split(value, raw, reference_points, spatial_shapes, num_heads=8, num_levels=4, num_points=8):
     """``ms_deform_attn_raw`` for the self-attention (queries = the value levels) with the level split of ``_MSDeformAttnSelfSplit``."""
-    shapes = [tuple(int(v) for v in hw) for hw in spatial_shapes]
-    n_fine = shapes[0][0] * shapes[0][1]
-    order = msda_tile_order(shapes[:1], value.device)
-    return _MSDeformAttnSelfSplit.apply(value, raw, reference_points, shapes, n_fine, order, int(num_heads), int(num_levels), int(num_points))
+    lv = _levels(spatial_shapes)
+    n_fine = lv.hw[0][0] * lv.hw[0][1]
+    order = msda_tile_order(lv.hw[:1], value.device)
+    return _MSDeformAttnSelfSplit.apply(value, raw, reference_points, lv, n_fine, order, int(num_heads), int(num_levels), int(num_points))
 
 
 # ---------------------------------------------------------------------------- channels-last helpers
@@ -817,10 +768,9 @@ class _TokensFromMap(torch.autograd.Function):
             assert not pos.requires_grad and pos.numel() == C * N
             pos = _c(pos.to(_f32))
         tok = torch.empty(B, N, C, device=fmap.device, dtype=fmap.dtype)
-        PROFILER.run(f'tokens_from_map[{B}x{C}x{N} {_tag(fmap)}]', 2 * tok.numel() * _es(tok) + (C * N * 4 if pos is not None else 0),
-                     lambda: hip.check(hip.lib().ge_tokens_from_map(
-                         _raw_ptr(fmap, 'map'), fmap.stride(0), hip.ptr(pos), hip.ptr(tok), N * C, B, C, N, 0.0, 0,
-                         hip.dtype_code(fmap), hip.stream()), 'ge_tokens_from_map'))
+        _launch(f'tokens_from_map[{B}x{C}x{N} {_tag(fmap)}]', 2 * tok.numel() * _es(tok) + (C * N * 4 if pos is not None else 0),
+                'ge_tokens_from_map', _raw_ptr(fmap, 'map'), fmap.stride(0), hip.ptr(pos), hip.ptr(tok), N * C, B, C, N, 0.0, 0, hip.dtype_code(fmap),
+                hip.stream())
         ctx.geom = (B, C, H, W)
         return tok
 
@@ -830,9 +780,8 @@ class _TokensFromMap(torch.autograd.Function):
         N = H * W
         d_tok = _rows(d_tok)
         d_map = torch.empty(B, C, H, W, device=d_tok.device, dtype=d_tok.dtype)
-        PROFILER.run(f'map_from_tokens[{B}x{C}x{N} {_tag(d_tok)}]', 2 * d_map.numel() * _es(d_map), lambda: hip.check(
-            hip.lib().ge_map_from_tokens(_raw_ptr(d_tok, 'd_tok'), d_tok.stride(0), None, 0, hip.ptr(d_map), C * N, B, C, N, 0.0, 0,
-                                         hip.dtype_code(d_tok), hip.stream()), 'ge_map_from_tokens'))
+        _launch(f'map_from_tokens[{B}x{C}x{N} {_tag(d_tok)}]', 2 * d_map.numel() * _es(d_map), 'ge_map_from_tokens', _raw_ptr(d_tok, 'd_tok'),
+                d_tok.stride(0), None, 0, hip.ptr(d_map), C * N, B, C, N, 0.0, 0, hip.dtype_code(d_tok), hip.stream())
         return d_map, None
 
 
@@ -844,9 +793,8 @@ class _AddRows(torch.autograd.Function):
         tok = _c(tok)
         B, N, C = tok.shape
         out = torch.empty_like(tok)
-        PROFILER.run(f'add_rows[{B}x{N}x{C} {_tag(tok)}]', 2 * tok.numel() * _es(tok) + N * C * 4, lambda: hip.check(
-            hip.lib().ge_add_rows(hip.ptr(tok, name='tokens'), hip.ptr(pos_rows, _f32), hip.ptr(out), B, N, C, hip.dtype_code(tok),
-                                  hip.stream()), 'ge_add_rows'))
+        _launch(f'add_rows[{B}x{N}x{C} {_tag(tok)}]', 2 * tok.numel() * _es(tok) + N * C * 4, 'ge_add_rows', hip.ptr(tok, name='tokens'),
+                hip.ptr(pos_rows, _f32), hip.ptr(out), B, N, C, hip.dtype_code(tok), hip.stream())
         return out
 
     @staticmethod
@@ -875,9 +823,8 @@ class _ResidualDropout(torch.autograd.Function):
         B, N, C = tok.shape
         res = _c(identity.to(tok.dtype))
         out = torch.empty(B, N, C, device=tok.device, dtype=tok.dtype)
-        PROFILER.run(f'residual_dropout[{B}x{N}x{C} {_tag(tok)}]', 3 * tok.numel() * _es(tok), lambda: hip.check(hip.lib().ge_concat_rows_fwd(
-            _raw_ptr(tok, 'tokens'), N, tok.stride(0), _raw_ptr(res, 'identity'), None, _raw_ptr(out, 'out'), B * N, C, 0, 1, p, seed,
-            hip.dtype_code(tok), hip.stream()), 'ge_concat_rows_fwd'))
+        _launch(f'residual_dropout[{B}x{N}x{C} {_tag(tok)}]', 3 * tok.numel() * _es(tok), 'ge_concat_rows_fwd', _raw_ptr(tok, 'tokens'), N,
+                tok.stride(0), _raw_ptr(res, 'identity'), None, _raw_ptr(out, 'out'), B * N, C, 0, 1, p, seed, hip.dtype_code(tok), hip.stream())
         ctx.meta = (B, N, C, p, seed, identity.dtype)
         return out
 
@@ -886,9 +833,8 @@ class _ResidualDropout(torch.autograd.Function):
         B, N, C, p, seed, id_dtype = ctx.meta
         d_out = _c(d_out)
         d_tok = torch.empty_like(d_out)
-        PROFILER.run(f'slice_rows_drop[{B}x{N}x{C} {_tag(d_out)}]', 2 * d_tok.numel() * _es(d_out), lambda: hip.check(
-            hip.lib().ge_slice_rows_drop(_raw_ptr(d_out, 'd_out'), hip.ptr(d_tok), B * N, C, C, 0, p, seed, hip.dtype_code(d_out), hip.stream()),
-            'ge_slice_rows_drop'))
+        _launch(f'slice_rows_drop[{B}x{N}x{C} {_tag(d_out)}]', 2 * d_tok.numel() * _es(d_out), 'ge_slice_rows_drop', _raw_ptr(d_out, 'd_out'),
+                hip.ptr(d_tok), B * N, C, C, 0, p, seed, hip.dtype_code(d_out), hip.stream())
         return d_tok, d_out.to(id_dtype), None, None
 
 
@@ -941,11 +887,10 @@ class _ConcatTokensMap(torch.autograd.Function):
             res = _planes(identity.to(tok.dtype))
             assert tuple(res.shape) == (B, C, H, W)
         es = _es(tok)
-        PROFILER.run(f'map_from_tokens[{B}x{C}x{N} {_tag(tok)}{" +res" if res is not None else ""}{" drop" if p > 0 else ""}]',
-                     (2 + (res is not None)) * tok.numel() * es, lambda: hip.check(hip.lib().ge_map_from_tokens(
-                         _raw_ptr(tok, 'tokens'), tok.stride(0), None if res is None else _raw_ptr(res, 'identity'),
-                         0 if res is None else res.stride(0), hip.ptr(out) + t0 * N * es, out.stride(0), B, C, N, p, seed,
-                         hip.dtype_code(tok), hip.stream()), 'ge_map_from_tokens'))
+        _launch(f'map_from_tokens[{B}x{C}x{N} {_tag(tok)}{" +res" if res is not None else ""}{" drop" if p > 0 else ""}]',
+                (2 + (res is not None)) * tok.numel() * es, 'ge_map_from_tokens', _raw_ptr(tok, 'tokens'), tok.stride(0),
+                None if res is None else _raw_ptr(res, 'identity'), 0 if res is None else res.stride(0), hip.ptr(out) + t0 * N * es, out.stride(0), B,
+                C, N, p, seed, hip.dtype_code(tok), hip.stream())
         out[:, m0:m0 + Cm].copy_(fmap)
         ctx.meta = (B, N, C, Cm, t0, m0, p, seed, identity is not None)
         return out
@@ -956,10 +901,8 @@ class _ConcatTokensMap(torch.autograd.Function):
         d_out = _c(d_out)
         es = _es(d_out)
         d_tok = torch.empty(B, N, C, device=d_out.device, dtype=d_out.dtype)
-        PROFILER.run(f'tokens_from_map[{B}x{C}x{N} {_tag(d_out)}{" drop" if p > 0 else ""}]', 2 * d_tok.numel() * es,
-                     lambda: hip.check(hip.lib().ge_tokens_from_map(
-                         hip.ptr(d_out) + t0 * N * es, d_out.stride(0), None, hip.ptr(d_tok), N * C, B, C, N, p, seed,
-                         hip.dtype_code(d_out), hip.stream()), 'ge_tokens_from_map'))
+        _launch(f'tokens_from_map[{B}x{C}x{N} {_tag(d_out)}{" drop" if p > 0 else ""}]', 2 * d_tok.numel() * es, 'ge_tokens_from_map',
+                hip.ptr(d_out) + t0 * N * es, d_out.stride(0), None, hip.ptr(d_tok), N * C, B, C, N, p, seed, hip.dtype_code(d_out), hip.stream())
         d_slice = d_out[:, t0:t0 + C]
         return d_tok, d_out[:, m0:m0 + Cm], (d_slice if has_id else None), None, None, None
 
@@ -976,10 +919,10 @@ class _ConcatRows(torch.autograd.Function):
         fmap = _cl(fmap)
         res = None if identity is None else _cl(identity.to(tok.dtype))
         out = torch.empty((B, C + Cm, H, W), device=tok.device, dtype=tok.dtype, memory_format=_CL)
-        PROFILER.run(f'concat_rows[{B}x{N}x({C}+{Cm}) {_tag(tok)}{" +res" if res is not None else ""}{" drop" if p > 0 else ""}]',
-                     ((2 + (res is not None)) * tok.numel() + 2 * fmap.numel()) * _es(tok), lambda: hip.check(hip.lib().ge_concat_rows_fwd(
-                         _raw_ptr(tok, 'tokens'), N, tok.stride(0), None if res is None else _raw_ptr(res, 'identity'), _raw_ptr(fmap, 'map'),
-                         _raw_ptr(out, 'out'), B * N, C, Cm, int(tokens_first), p, seed, hip.dtype_code(tok), hip.stream()), 'ge_concat_rows_fwd'))
+        _launch(f'concat_rows[{B}x{N}x({C}+{Cm}) {_tag(tok)}{" +res" if res is not None else ""}{" drop" if p > 0 else ""}]',
+                ((2 + (res is not None)) * tok.numel() + 2 * fmap.numel()) * _es(tok), 'ge_concat_rows_fwd', _raw_ptr(tok, 'tokens'), N,
+                tok.stride(0), None if res is None else _raw_ptr(res, 'identity'), _raw_ptr(fmap, 'map'), _raw_ptr(out, 'out'), B * N, C, Cm,
+                int(tokens_first), p, seed, hip.dtype_code(tok), hip.stream())
         ctx.meta = (B, N, C, Cm, tokens_first, p, seed, identity is not None)
         return out
 
@@ -991,9 +934,8 @@ class _ConcatRows(torch.autograd.Function):
         d_slice = d_out[:, t0:t0 + C]
         if p > 0:
             d_tok = torch.empty(B, N, C, device=d_out.device, dtype=d_out.dtype)
-            PROFILER.run(f'slice_rows_drop[{B}x{N}x{C} {_tag(d_out)}]', 2 * d_tok.numel() * _es(d_out), lambda: hip.check(
-                hip.lib().ge_slice_rows_drop(_raw_ptr(d_out, 'd_out'), hip.ptr(d_tok), B * N, C, C + Cm, t0, p, seed, hip.dtype_code(d_out),
-                                             hip.stream()), 'ge_slice_rows_drop'))
+            _launch(f'slice_rows_drop[{B}x{N}x{C} {_tag(d_out)}]', 2 * d_tok.numel() * _es(d_out), 'ge_slice_rows_drop', _raw_ptr(d_out, 'd_out'),
+                    hip.ptr(d_tok), B * N, C, C + Cm, t0, p, seed, hip.dtype_code(d_out), hip.stream())
         else:
             d_tok = d_slice.permute(0, 2, 3, 1).reshape(B, N, C)               # a strided view: the consumer packs it
         return d_tok, d_out[:, m0:m0 + Cm], (d_slice if has_id else None), None, None, None
@@ -1022,15 +964,13 @@ class _Bilinear(torch.autograd.Function):
         ctx.geom = (N, C, Hi, Wi, Ho, Wo, int(align_corners))
         if ctx.cl:
             out = torch.empty((N, C, Ho, Wo), device=x.device, dtype=x.dtype, memory_format=_CL)
-            PROFILER.run(f'bilinear_nhwc_fwd[{N}x{C} {Hi}x{Wi}->{Ho}x{Wo} {_tag(x)}]', (x.numel() + out.numel()) * _es(x), lambda: hip.check(
-                hip.lib().ge_bilinear_nhwc_fwd(_raw_ptr(x, 'input'), _raw_ptr(out, 'out'), N, C, Hi, Wi, Ho, Wo, int(align_corners),
-                                               hip.dtype_code(x), hip.stream()), 'ge_bilinear_nhwc_fwd'))
+            _launch(f'bilinear_nhwc_fwd[{N}x{C} {Hi}x{Wi}->{Ho}x{Wo} {_tag(x)}]', (x.numel() + out.numel()) * _es(x), 'ge_bilinear_nhwc_fwd',
+                    _raw_ptr(x, 'input'), _raw_ptr(out, 'out'), N, C, Hi, Wi, Ho, Wo, int(align_corners), hip.dtype_code(x), hip.stream())
             return out
         x = _c(x)
         out = torch.empty(N, C, Ho, Wo, device=x.device, dtype=x.dtype)
-        PROFILER.run(f'bilinear_fwd[{N}x{C} {Hi}x{Wi}->{Ho}x{Wo} {_tag(x)}]', (x.numel() + out.numel()) * _es(x), lambda: hip.check(
-            hip.lib().ge_bilinear_fwd(hip.ptr(x, name='input'), hip.ptr(out), N, C, Hi, Wi, Ho, Wo, int(align_corners),
-                                      hip.dtype_code(x), hip.stream()), 'ge_bilinear_fwd'))
+        _launch(f'bilinear_fwd[{N}x{C} {Hi}x{Wi}->{Ho}x{Wo} {_tag(x)}]', (x.numel() + out.numel()) * _es(x), 'ge_bilinear_fwd',
+                hip.ptr(x, name='input'), hip.ptr(out), N, C, Hi, Wi, Ho, Wo, int(align_corners), hip.dtype_code(x), hip.stream())
         return out
 
     @staticmethod
@@ -1040,16 +980,14 @@ class _Bilinear(torch.autograd.Function):
             d_out = _cl(d_out)
             d_in = torch.empty((N, C, Hi, Wi), device=d_out.device, dtype=d_out.dtype, memory_format=_CL)
             ws = torch.empty(N * Ho * Wi * C, device=d_out.device, dtype=_f32) if (Ho > 3 * Hi or Wo > 3 * Wi) else None
-            PROFILER.run(f'bilinear_nhwc_bwd[{N}x{C} {Hi}x{Wi}<-{Ho}x{Wo} {_tag(d_out)}]', (d_out.numel() + d_in.numel()) * _es(d_out),
-                         lambda: hip.check(hip.lib().ge_bilinear_nhwc_bwd(_raw_ptr(d_out, 'd_out'), _raw_ptr(d_in, 'd_in'), hip.ptr(ws),
-                                                                          0 if ws is None else ws.numel() * 4, N, C, Hi, Wi, Ho, Wo, ac,
-                                                                          hip.dtype_code(d_out), hip.stream()), 'ge_bilinear_nhwc_bwd'))
+            _launch(f'bilinear_nhwc_bwd[{N}x{C} {Hi}x{Wi}<-{Ho}x{Wo} {_tag(d_out)}]', (d_out.numel() + d_in.numel()) * _es(d_out),
+                    'ge_bilinear_nhwc_bwd', _raw_ptr(d_out, 'd_out'), _raw_ptr(d_in, 'd_in'), hip.ptr(ws), 0 if ws is None else ws.numel() * 4, N, C,
+                    Hi, Wi, Ho, Wo, ac, hip.dtype_code(d_out), hip.stream())
             return d_in, None, None, None
         d_out = _c(d_out)
         d_in = torch.empty(N, C, Hi, Wi, device=d_out.device, dtype=d_out.dtype)
-        PROFILER.run(f'bilinear_bwd[{N}x{C} {Hi}x{Wi}<-{Ho}x{Wo} {_tag(d_out)}]', (d_out.numel() + d_in.numel()) * _es(d_out),
-                     lambda: hip.check(hip.lib().ge_bilinear_bwd(hip.ptr(d_out), hip.ptr(d_in), N, C, Hi, Wi, Ho, Wo, ac,
-                                                                 hip.dtype_code(d_out), hip.stream()), 'ge_bilinear_bwd'))
+        _launch(f'bilinear_bwd[{N}x{C} {Hi}x{Wi}<-{Ho}x{Wo} {_tag(d_out)}]', (d_out.numel() + d_in.numel()) * _es(d_out), 'ge_bilinear_bwd',
+                hip.ptr(d_out), hip.ptr(d_in), N, C, Hi, Wi, Ho, Wo, ac, hip.dtype_code(d_out), hip.stream())
         return d_in, None, None, None
 
 
@@ -1067,10 +1005,9 @@ def _conv3x3_launch(x, w_ohwi, bias, act, slope):
     Co = w_ohwi.shape[0]
     y = torch.empty((N, Co, H, W), device=x.device, dtype=torch.bfloat16, memory_format=_CL)
     flops = 2 * N * H * W * C * Co * 9
-    PROFILER.run(f'conv3x3[{N}x{C}->{Co} {H}x{W}{" +b" if bias is not None else ""}{" act" if act else ""}]',
-                 (x.numel() + y.numel() + w_ohwi.numel()) * 2, lambda: hip.check(hip.lib().ge_conv3x3_nhwc_fwd(
-                     _raw_ptr(x, 'x'), hip.ptr(w_ohwi, torch.bfloat16), hip.ptr(bias, _f32), _raw_ptr(y, 'y'), N, H, W, C, Co, int(act), float(slope),
-                     hip.GE_BF16, hip.stream()), 'ge_conv3x3_nhwc_fwd'), flops=flops)
+    _launch(f'conv3x3[{N}x{C}->{Co} {H}x{W}{" +b" if bias is not None else ""}{" act" if act else ""}]', (x.numel() + y.numel() + w_ohwi.numel()) * 2,
+            'ge_conv3x3_nhwc_fwd', _raw_ptr(x, 'x'), hip.ptr(w_ohwi, torch.bfloat16), hip.ptr(bias, _f32), _raw_ptr(y, 'y'), N, H, W, C, Co, int(act),
+            float(slope), hip.GE_BF16, hip.stream(), flops=flops)
     return y
 
 
@@ -1106,9 +1043,8 @@ class _Conv3x3(torch.autograd.Function):
                 dyp = torch.empty_like(dy)
                 dbf = torch.empty(Co, device=dy.device, dtype=_f32)
                 ws = torch.empty(int(hip.lib().ge_nhwc_workspace(Co, 1)), device=dy.device, dtype=torch.uint8)
-                PROFILER.run(f'bias_act_nhwc_bwd[{N}x{Co}x{H}x{W} bf16]', 3 * dy.numel() * 2, lambda: hip.check(hip.lib().ge_bias_act_nhwc_bwd(
-                    _raw_ptr(dy, 'dy'), _raw_ptr(y, 'y'), _raw_ptr(dyp, 'dx'), hip.ptr(dbf), hip.ptr(ws), N * H * W, Co, slope, hip.GE_BF16,
-                    hip.stream()), 'ge_bias_act_nhwc_bwd'))
+                _launch(f'bias_act_nhwc_bwd[{N}x{Co}x{H}x{W} bf16]', 3 * dy.numel() * 2, 'ge_bias_act_nhwc_bwd', _raw_ptr(dy, 'dy'), _raw_ptr(y, 'y'),
+                        _raw_ptr(dyp, 'dx'), hip.ptr(dbf), hip.ptr(ws), N * H * W, Co, slope, hip.GE_BF16, hip.stream())
                 dy = dyp
                 db = dbf if has_bias else None
             elif has_bias and ctx.needs_input_grad[2]:
@@ -1133,9 +1069,9 @@ class _Conv3x3(torch.autograd.Function):
                     if dw_ohwi is None or tuple(dw_ohwi.shape) != (Co, 3, 3, Ci):
                         dw_ohwi = torch.empty(Co, 3, 3, Ci, device=dy.device, dtype=_f32)
                     dw_ohwi.zero_()
-                    PROFILER.run(f'conv3x3_wgrad[{N}x{Ci}->{Co} {H}x{W}]', (x.numel() + dy.numel()) * 2 + dw_ohwi.numel() * 4, lambda: hip.check(
-                        hip.lib().ge_conv3x3_nhwc_wgrad(_raw_ptr(x, 'x'), _raw_ptr(dy, 'dy'), hip.ptr(dw_ohwi), N, H, W, Ci, Co, hip.GE_BF16, hip.stream()),
-                        'ge_conv3x3_nhwc_wgrad'), flops=2 * N * H * W * Ci * Co * 9)
+                    _launch(f'conv3x3_wgrad[{N}x{Ci}->{Co} {H}x{W}]', (x.numel() + dy.numel()) * 2 + dw_ohwi.numel() * 4, 'ge_conv3x3_nhwc_wgrad',
+                            _raw_ptr(x, 'x'), _raw_ptr(dy, 'dy'), hip.ptr(dw_ohwi), N, H, W, Ci, Co, hip.GE_BF16, hip.stream(),
+                            flops=2 * N * H * W * Ci * Co * 9)
                     dw = dw_ohwi.permute(0, 3, 1, 2)
                 else:
                     dw = torch.ops.aten.convolution_backward(dy, x, wb, None, (1, 1), (1, 1), (1, 1), False, (0, 0), 1, (False, True, False))[1]
@@ -1222,9 +1158,8 @@ def conv1x1_wgrad(x, dy):
     Co = dy.shape[1]
     M = N * H * W
     dw = torch.zeros(Co, Ci, device=x.device, dtype=_f32)
-    PROFILER.run(f'conv1x1_wgrad[{N}x{Ci}->{Co} {H}x{W}]', (x.numel() + dy.numel()) * 2 + dw.numel() * 4, lambda: hip.check(
-        hip.lib().ge_conv1x1_nhwc_wgrad(_raw_ptr(x, 'x'), _raw_ptr(dy, 'dy'), hip.ptr(dw), M, Ci, Co, hip.GE_BF16, hip.stream()),
-        'ge_conv1x1_nhwc_wgrad'), flops=2 * M * Ci * Co)
+    _launch(f'conv1x1_wgrad[{N}x{Ci}->{Co} {H}x{W}]', (x.numel() + dy.numel()) * 2 + dw.numel() * 4, 'ge_conv1x1_nhwc_wgrad', _raw_ptr(x, 'x'),
+            _raw_ptr(dy, 'dy'), hip.ptr(dw), M, Ci, Co, hip.GE_BF16, hip.stream(), flops=2 * M * Ci * Co)
     return dw
 
 
@@ -1318,9 +1253,8 @@ class _Conv3x3C1(torch.autograd.Function):
             w = w.contiguous()
         b = None if bias is None else bias.detach()
         y = torch.empty((N, 1, H, W), device=x.device, dtype=_f32 if out_fp32 else torch.bfloat16)
-        PROFILER.run(f'conv3x3_c1[{N}x{C}->1 {H}x{W}]', x.numel() * 2 + y.numel() * y.element_size(), lambda: hip.check(hip.lib().ge_conv3x3_c1_fwd(
-            _raw_ptr(x, 'x'), hip.ptr(w, _f32), hip.ptr(b, _f32), hip.ptr(y), N, H, W, C, hip.GE_F32 if out_fp32 else hip.GE_BF16, hip.stream()),
-            'ge_conv3x3_c1_fwd'))
+        _launch(f'conv3x3_c1[{N}x{C}->1 {H}x{W}]', x.numel() * 2 + y.numel() * y.element_size(), 'ge_conv3x3_c1_fwd', _raw_ptr(x, 'x'),
+                hip.ptr(w, _f32), hip.ptr(b, _f32), hip.ptr(y), N, H, W, C, hip.GE_F32 if out_fp32 else hip.GE_BF16, hip.stream())
         ctx.save_for_backward(x, w)
         ctx.has_bias = bias is not None
         return y
@@ -1335,9 +1269,9 @@ class _Conv3x3C1(torch.autograd.Function):
         dx = torch.empty_like(x)
         dw = torch.empty((1, 3, 3, C), device=x.device, dtype=_f32)
         db = torch.empty(1, device=x.device, dtype=_f32) if ctx.has_bias else None
-        PROFILER.run(f'conv3x3_c1_bwd[{N}x{C}->1 {H}x{W}]', 2 * x.numel() * 2 + dy.numel() * dy.element_size(), lambda: hip.check(hip.lib().ge_conv3x3_c1_bwd(
-            _raw_ptr(x, 'x'), hip.ptr(dy), hip.ptr(w, _f32), _raw_ptr(dx, 'dx'), hip.ptr(dw), hip.ptr(db, _f32), N, H, W, C,
-            hip.GE_F32 if dy.dtype == _f32 else hip.GE_BF16, hip.stream()), 'ge_conv3x3_c1_bwd'))
+        _launch(f'conv3x3_c1_bwd[{N}x{C}->1 {H}x{W}]', 2 * x.numel() * 2 + dy.numel() * dy.element_size(), 'ge_conv3x3_c1_bwd', _raw_ptr(x, 'x'),
+                hip.ptr(dy), hip.ptr(w, _f32), _raw_ptr(dx, 'dx'), hip.ptr(dw), hip.ptr(db, _f32), N, H, W, C,
+                hip.GE_F32 if dy.dtype == _f32 else hip.GE_BF16, hip.stream())
         return dx, dw.permute(0, 3, 1, 2), db, None
 
 
@@ -1368,9 +1302,9 @@ class _UpCat(torch.autograd.Function):
         _, Cs, H, W = skip.shape
         coarse, skip = _cl(coarse), _cl(skip)
         out = torch.empty((N, Cu + Cs, H, W), device=coarse.device, dtype=coarse.dtype, memory_format=_CL)
-        PROFILER.run(f'upcat_fwd[{N}x({Cu}^+{Cs}) {Hc}x{Wc}->{H}x{W} {_tag(coarse)}]', (coarse.numel() + skip.numel() + out.numel()) * _es(out),
-                     lambda: hip.check(hip.lib().ge_upcat_nhwc_fwd(_raw_ptr(coarse, 'coarse'), _raw_ptr(skip, 'skip'), _raw_ptr(out, 'out'), N, Cu, Hc, Wc,
-                                                                    Cs, H, W, int(align_corners), hip.dtype_code(out), hip.stream()), 'ge_upcat_nhwc_fwd'))
+        _launch(f'upcat_fwd[{N}x({Cu}^+{Cs}) {Hc}x{Wc}->{H}x{W} {_tag(coarse)}]', (coarse.numel() + skip.numel() + out.numel()) * _es(out),
+                'ge_upcat_nhwc_fwd', _raw_ptr(coarse, 'coarse'), _raw_ptr(skip, 'skip'), _raw_ptr(out, 'out'), N, Cu, Hc, Wc, Cs, H, W,
+                int(align_corners), hip.dtype_code(out), hip.stream())
         ctx.geom = (N, Cu, Hc, Wc, Cs, H, W, int(align_corners))
         return out
 
@@ -1379,9 +1313,8 @@ class _UpCat(torch.autograd.Function):
         N, Cu, Hc, Wc, Cs, H, W, ac = ctx.geom
         d_out = _cl(d_out)
         d_coarse = torch.empty((N, Cu, Hc, Wc), device=d_out.device, dtype=d_out.dtype, memory_format=_CL)
-        PROFILER.run(f'upcat_bwd[{N}x{Cu} {Hc}x{Wc}<-{H}x{W} {_tag(d_out)}]', (N * H * W * Cu + d_coarse.numel()) * _es(d_out),
-                     lambda: hip.check(hip.lib().ge_upcat_nhwc_bwd(_raw_ptr(d_out, 'd_out'), _raw_ptr(d_coarse, 'd_coarse'), N, Cu, Hc, Wc, Cs, H, W, ac,
-                                                                    hip.dtype_code(d_out), hip.stream()), 'ge_upcat_nhwc_bwd'))
+        _launch(f'upcat_bwd[{N}x{Cu} {Hc}x{Wc}<-{H}x{W} {_tag(d_out)}]', (N * H * W * Cu + d_coarse.numel()) * _es(d_out), 'ge_upcat_nhwc_bwd',
+                _raw_ptr(d_out, 'd_out'), _raw_ptr(d_coarse, 'd_coarse'), N, Cu, Hc, Wc, Cs, H, W, ac, hip.dtype_code(d_out), hip.stream())
         return d_coarse, d_out[:, Cu:], None
 
 
@@ -1405,10 +1338,9 @@ class _UpSum(torch.autograd.Function):
         out = torch.empty_like(fine)
         ptrs = (ctypes.c_void_p * len(srcs))(*[_raw_ptr(t, 'src') for t in srcs])
         hw = (ctypes.c_int * (2 * len(srcs)))(*[v for t in srcs for v in t.shape[2:]])
-        PROFILER.run(f'upsum_fwd[{N}x{C}x{H}x{W} <- {len(srcs)} maps {_tag(fine)}]', (2 * fine.numel() + sum(t.numel() for t in srcs)) * _es(fine),
-                     lambda: hip.check(hip.lib().ge_upsum_nhwc_fwd(ctypes.cast(ptrs, ctypes.c_void_p), ctypes.cast(hw, ctypes.c_void_p), len(srcs),
-                                                                    _raw_ptr(fine, 'fine'), _raw_ptr(out, 'out'), N, C, H, W, int(align_corners),
-                                                                    hip.dtype_code(fine), hip.stream()), 'ge_upsum_nhwc_fwd'))
+        _launch(f'upsum_fwd[{N}x{C}x{H}x{W} <- {len(srcs)} maps {_tag(fine)}]', (2 * fine.numel() + sum(t.numel() for t in srcs)) * _es(fine),
+                'ge_upsum_nhwc_fwd', ctypes.cast(ptrs, ctypes.c_void_p), ctypes.cast(hw, ctypes.c_void_p), len(srcs), _raw_ptr(fine, 'fine'),
+                _raw_ptr(out, 'out'), N, C, H, W, int(align_corners), hip.dtype_code(fine), hip.stream())
         ctx.geom = (N, C, H, W, int(align_corners), [tuple(t.shape[2:]) for t in srcs])
         return out
 
@@ -1420,10 +1352,9 @@ class _UpSum(torch.autograd.Function):
         for (Hi, Wi) in sizes:                               # the transpose of each interpolation reads the same d_out
             d_in = torch.empty((N, C, Hi, Wi), device=d_out.device, dtype=d_out.dtype, memory_format=_CL)
             ws = torch.empty(N * H * Wi * C, device=d_out.device, dtype=_f32) if (H > 3 * Hi or W > 3 * Wi) else None
-            PROFILER.run(f'bilinear_nhwc_bwd[{N}x{C} {Hi}x{Wi}<-{H}x{W} {_tag(d_out)}]', (d_out.numel() + d_in.numel()) * _es(d_out),
-                         lambda: hip.check(hip.lib().ge_bilinear_nhwc_bwd(_raw_ptr(d_out, 'd_out'), _raw_ptr(d_in, 'd_in'), hip.ptr(ws),
-                                                                          0 if ws is None else ws.numel() * 4, N, C, Hi, Wi, H, W, ac,
-                                                                          hip.dtype_code(d_out), hip.stream()), 'ge_bilinear_nhwc_bwd'))
+            _launch(f'bilinear_nhwc_bwd[{N}x{C} {Hi}x{Wi}<-{H}x{W} {_tag(d_out)}]', (d_out.numel() + d_in.numel()) * _es(d_out),
+                    'ge_bilinear_nhwc_bwd', _raw_ptr(d_out, 'd_out'), _raw_ptr(d_in, 'd_in'), hip.ptr(ws), 0 if ws is None else ws.numel() * 4, N, C,
+                    Hi, Wi, H, W, ac, hip.dtype_code(d_out), hip.stream())
             grads.append(d_in)
         return (None, d_out) + tuple(grads)
 
@@ -1480,7 +1411,7 @@ def _ln_bwd_and_fold(launch_multi, dwb, C):
 
 def _ln_fold(dwb, C):
     out = torch.empty(2, C, device=dwb.device, dtype=_f32)
-    hip.check(hip.lib().ge_layernorm_fold(hip.ptr(dwb), hip.ptr(out), _LN_COPIES, C, hip.stream()), 'ge_layernorm_fold')
+    hip.call('ge_layernorm_fold', hip.ptr(dwb), hip.ptr(out), _LN_COPIES, C, hip.stream())
     return out
 
 
@@ -1495,10 +1426,8 @@ class _LayerNorm(torch.autograd.Function):
         y = torch.empty(x.shape, device=x.device, dtype=out_dtype)
         mean = torch.empty(rows, device=x.device, dtype=_f32)
         rstd = torch.empty(rows, device=x.device, dtype=_f32)
-        PROFILER.run(f'layernorm_fwd[{rows}x{C} {_tag(x)}->{_tag(y)}]', x.numel() * _es(x) + y.numel() * _es(y), lambda: hip.check(
-            hip.lib().ge_layernorm_fwd(hip.ptr(x, name='x'), hip.dtype_code(x), hip.ptr(w), hip.ptr(b), hip.ptr(y),
-                                       hip.dtype_code(y), hip.ptr(mean), hip.ptr(rstd), rows, C, eps, hip.stream()),
-            'ge_layernorm_fwd'))
+        _launch(f'layernorm_fwd[{rows}x{C} {_tag(x)}->{_tag(y)}]', x.numel() * _es(x) + y.numel() * _es(y), 'ge_layernorm_fwd', hip.ptr(x, name='x'),
+                hip.dtype_code(x), hip.ptr(w), hip.ptr(b), hip.ptr(y), hip.dtype_code(y), hip.ptr(mean), hip.ptr(rstd), rows, C, eps, hip.stream())
         ctx.save_for_backward(x, w, mean, rstd)
         return y
 
@@ -1512,10 +1441,9 @@ class _LayerNorm(torch.autograd.Function):
             dy = dy.to(_f32)
         dx = torch.empty_like(x)
         dwb = _ln_accumulators(x.device, C)                                                    # see ge_layernorm_bwd_multi
-        dwb = _ln_bwd_and_fold(lambda: PROFILER.run(f'layernorm_bwd[{rows}x{C} {_tag(x)}<-{_tag(dy)}]', 2 * x.numel() * _es(x) + dy.numel() * _es(dy), lambda: hip.check(
-            hip.lib().ge_layernorm_bwd_multi(hip.ptr(dy), hip.dtype_code(dy), hip.ptr(x), hip.dtype_code(x), hip.ptr(w), hip.ptr(mean),
-                                             hip.ptr(rstd), None, hip.ptr(dx), hip.ptr(dwb), _LN_COPIES, rows, C, hip.stream()),
-            'ge_layernorm_bwd_multi')), dwb, C)
+        dwb = _ln_bwd_and_fold(lambda: _launch(f'layernorm_bwd[{rows}x{C} {_tag(x)}<-{_tag(dy)}]', 2 * x.numel() * _es(x) + dy.numel() * _es(dy),
+                                               'ge_layernorm_bwd_multi', hip.ptr(dy), hip.dtype_code(dy), hip.ptr(x), hip.dtype_code(x), hip.ptr(w),
+                                               hip.ptr(mean), hip.ptr(rstd), None, hip.ptr(dx), hip.ptr(dwb), _LN_COPIES, rows, C, hip.stream()), dwb, C)
         return dx, dwb[0], dwb[1], None, None
 
 
@@ -1533,10 +1461,8 @@ class _LayerNormRes(torch.autograd.Function):
         y = torch.empty(x.shape, device=x.device, dtype=out_dtype)
         mean = torch.empty(rows, device=x.device, dtype=_f32)
         rstd = torch.empty(rows, device=x.device, dtype=_f32)
-        PROFILER.run(f'layernorm_fwd[{rows}x{C} {_tag(x)}->{_tag(y)}]', x.numel() * _es(x) + y.numel() * _es(y), lambda: hip.check(
-            hip.lib().ge_layernorm_fwd(hip.ptr(x, name='x'), hip.dtype_code(x), hip.ptr(w), hip.ptr(b), hip.ptr(y),
-                                       hip.dtype_code(y), hip.ptr(mean), hip.ptr(rstd), rows, C, eps, hip.stream()),
-            'ge_layernorm_fwd'))
+        _launch(f'layernorm_fwd[{rows}x{C} {_tag(x)}->{_tag(y)}]', x.numel() * _es(x) + y.numel() * _es(y), 'ge_layernorm_fwd', hip.ptr(x, name='x'),
+                hip.dtype_code(x), hip.ptr(w), hip.ptr(b), hip.ptr(y), hip.dtype_code(y), hip.ptr(mean), hip.ptr(rstd), rows, C, eps, hip.stream())
         ctx.save_for_backward(x, w, mean, rstd)
         return y, x.view_as(x)
 
@@ -1554,11 +1480,10 @@ class _LayerNormRes(torch.autograd.Function):
             dres = _c(dres.to(x.dtype))
         dx = torch.empty_like(x)
         dwb = _ln_accumulators(x.device, C)
-        dwb = _ln_bwd_and_fold(lambda: PROFILER.run(f'layernorm_bwd[{rows}x{C} {_tag(x)}<-{_tag(dy)}{" +res" if dres is not None else ""}]',
-                     (2 + (dres is not None)) * x.numel() * _es(x) + dy.numel() * _es(dy), lambda: hip.check(
-            hip.lib().ge_layernorm_bwd_multi(hip.ptr(dy), hip.dtype_code(dy), hip.ptr(x), hip.dtype_code(x), hip.ptr(w), hip.ptr(mean),
-                                             hip.ptr(rstd), hip.ptr(dres), hip.ptr(dx), hip.ptr(dwb), _LN_COPIES, rows, C, hip.stream()),
-            'ge_layernorm_bwd_multi')), dwb, C)
+        dwb = _ln_bwd_and_fold(lambda: _launch(f'layernorm_bwd[{rows}x{C} {_tag(x)}<-{_tag(dy)}{" +res" if dres is not None else ""}]',
+                                               (2 + (dres is not None)) * x.numel() * _es(x) + dy.numel() * _es(dy), 'ge_layernorm_bwd_multi',
+                                               hip.ptr(dy), hip.dtype_code(dy), hip.ptr(x), hip.dtype_code(x), hip.ptr(w), hip.ptr(mean),
+                                               hip.ptr(rstd), hip.ptr(dres), hip.ptr(dx), hip.ptr(dwb), _LN_COPIES, rows, C, hip.stream()), dwb, C)
         return dx, dwb[0], dwb[1], None, None
 
 
@@ -1582,8 +1507,8 @@ def colsum(x):
     if ws is None:                                      # launches are stream-ordered: one workspace per (width, stream) is enough
         ws = _COLSUM_WS[key] = torch.empty(int(hip.lib().ge_nhwc_workspace(C, 1)), device=x.device, dtype=torch.uint8)
     out = torch.empty(C, device=x.device, dtype=_f32)
-    PROFILER.run(f'colsum[{R}x{C} {_tag(x)}]', x.numel() * _es(x), lambda: hip.check(
-        hip.lib().ge_colsum(hip.ptr(x, name='x'), R, C, hip.ptr(out), hip.ptr(ws), 0, hip.dtype_code(x), hip.stream()), 'ge_colsum'))
+    _launch(f'colsum[{R}x{C} {_tag(x)}]', x.numel() * _es(x), 'ge_colsum', hip.ptr(x, name='x'), R, C, hip.ptr(out), hip.ptr(ws), 0,
+            hip.dtype_code(x), hip.stream())
     return out
 
 
@@ -1620,9 +1545,8 @@ def gemm_nt(x2, w, bias=None):
     if bias is not None:
         assert bias.dtype == _f32 and bias.numel() == N and bias.is_contiguous()
     out = torch.empty(M, N, device=x2.device, dtype=torch.bfloat16)
-    PROFILER.run(f'gemm_nt[{M}x{K}->{N}]', 2 * (M * K + N * K + M * N), lambda: hip.check(hip.lib().ge_gemm_nt(
-        hip.ptr(x2, name='x'), K, hip.ptr(w, name='weight'), K, hip.ptr(bias), hip.ptr(out), N, M, N, K, hip.GE_BF16, hip.stream()), 'ge_gemm_nt'),
-        flops=2.0 * M * N * K)
+    _launch(f'gemm_nt[{M}x{K}->{N}]', 2 * (M * K + N * K + M * N), 'ge_gemm_nt', hip.ptr(x2, name='x'), K, hip.ptr(w, name='weight'), K,
+            hip.ptr(bias), hip.ptr(out), N, M, N, K, hip.GE_BF16, hip.stream(), flops=2.0 * M * N * K)
     return out
 
 
@@ -1631,8 +1555,8 @@ def bias_gelu_fwd(y0, bias):
     C = y0.shape[-1]
     R = y0.numel() // C
     out = torch.empty_like(y0)
-    PROFILER.run(f'bias_gelu_fwd[{R}x{C} {_tag(y0)}]', 2 * y0.numel() * _es(y0), lambda: hip.check(hip.lib().ge_bias_gelu_fwd(
-        hip.ptr(y0, name='y0'), hip.ptr(bias, _f32), hip.ptr(out), R, C, hip.dtype_code(y0), hip.stream()), 'ge_bias_gelu_fwd'))
+    _launch(f'bias_gelu_fwd[{R}x{C} {_tag(y0)}]', 2 * y0.numel() * _es(y0), 'ge_bias_gelu_fwd', hip.ptr(y0, name='y0'), hip.ptr(bias, _f32),
+            hip.ptr(out), R, C, hip.dtype_code(y0), hip.stream())
     return out
 
 
@@ -1646,9 +1570,8 @@ def bias_gelu_bwd(dg, y0, bias):
     ws = _COLSUM_WS.get(key)
     if ws is None:
         ws = _COLSUM_WS[key] = torch.empty(int(hip.lib().ge_nhwc_workspace(C, 1)), device=y0.device, dtype=torch.uint8)
-    PROFILER.run(f'bias_gelu_bwd[{R}x{C} {_tag(y0)}]', 3 * y0.numel() * _es(y0), lambda: hip.check(hip.lib().ge_bias_gelu_bwd(
-        hip.ptr(dg, name='dg'), hip.ptr(y0), hip.ptr(bias, _f32), hip.ptr(dy), hip.ptr(db), hip.ptr(ws), R, C, hip.dtype_code(y0),
-        hip.stream()), 'ge_bias_gelu_bwd'))
+    _launch(f'bias_gelu_bwd[{R}x{C} {_tag(y0)}]', 3 * y0.numel() * _es(y0), 'ge_bias_gelu_bwd', hip.ptr(dg, name='dg'), hip.ptr(y0),
+            hip.ptr(bias, _f32), hip.ptr(dy), hip.ptr(db), hip.ptr(ws), R, C, hip.dtype_code(y0), hip.stream())
     return dy, db
 
 
@@ -1666,11 +1589,9 @@ class _ResidualDropPath(torch.autograd.Function):
         B = identity.shape[0]
         n = identity.numel() // max(B, 1)
         out = torch.empty_like(identity)
-        PROFILER.run(f'residual_drop_path[{B}x{n} {_tag(identity)}+{_tag(branch)}]',
-                     2 * identity.numel() * _es(identity) + branch.numel() * _es(branch), lambda: hip.check(
-            hip.lib().ge_residual_scale_add(hip.ptr(identity, name='identity'), hip.dtype_code(identity), hip.ptr(branch),
-                                            hip.dtype_code(branch), hip.ptr(scale, _f32), hip.ptr(out), B, n, hip.stream()),
-            'ge_residual_scale_add'))
+        _launch(f'residual_drop_path[{B}x{n} {_tag(identity)}+{_tag(branch)}]', 2 * identity.numel() * _es(identity) + branch.numel() * _es(branch),
+                'ge_residual_scale_add', hip.ptr(identity, name='identity'), hip.dtype_code(identity), hip.ptr(branch), hip.dtype_code(branch),
+                hip.ptr(scale, _f32), hip.ptr(out), B, n, hip.stream())
         ctx.save_for_backward(scale)
         ctx.branch_dtype = branch.dtype
         return out
@@ -1682,9 +1603,8 @@ class _ResidualDropPath(torch.autograd.Function):
         B = dy.shape[0]
         n = dy.numel() // max(B, 1)
         d_branch = torch.empty(dy.shape, device=dy.device, dtype=ctx.branch_dtype)
-        PROFILER.run(f'scale_rows[{B}x{n} {_tag(dy)}->{_tag(d_branch)}]', dy.numel() * _es(dy) + d_branch.numel() * _es(d_branch),
-                     lambda: hip.check(hip.lib().ge_scale_rows(hip.ptr(dy), hip.dtype_code(dy), hip.ptr(scale), hip.ptr(d_branch),
-                                                               hip.dtype_code(d_branch), B, n, hip.stream()), 'ge_scale_rows'))
+        _launch(f'scale_rows[{B}x{n} {_tag(dy)}->{_tag(d_branch)}]', dy.numel() * _es(dy) + d_branch.numel() * _es(d_branch), 'ge_scale_rows',
+                hip.ptr(dy), hip.dtype_code(dy), hip.ptr(scale), hip.ptr(d_branch), hip.dtype_code(d_branch), B, n, hip.stream())
         return dy, d_branch, None
 
 
@@ -1707,17 +1627,15 @@ class _BNAct(torch.autograd.Function):
         stats = torch.empty(2, C, device=x.device, dtype=_f32)
         ws = torch.empty(int(hip.lib().ge_nhwc_workspace(C, 2) if ctx.cl else hip.lib().ge_bn_workspace(C)), device=x.device, dtype=torch.uint8)
         if ctx.cl:
-            PROFILER.run(f'bn_act_nhwc_fwd[{N}x{C}x{H}x{W} {_tag(x)}]', 3 * x.numel() * _es(x), lambda: hip.check(
-                hip.lib().ge_bn_act_nhwc_fwd(_raw_ptr(x, 'x'), hip.ptr(w), hip.ptr(b), _raw_ptr(y, 'y'), hip.ptr(stats[0]), hip.ptr(stats[1]),
-                                             hip.ptr(running_mean, _f32), hip.ptr(running_var, _f32), hip.ptr(ws), N * H * W, C, eps,
-                                             momentum, slope, hip.dtype_code(x), hip.stream()), 'ge_bn_act_nhwc_fwd'))
+            _launch(f'bn_act_nhwc_fwd[{N}x{C}x{H}x{W} {_tag(x)}]', 3 * x.numel() * _es(x), 'ge_bn_act_nhwc_fwd', _raw_ptr(x, 'x'), hip.ptr(w),
+                    hip.ptr(b), _raw_ptr(y, 'y'), hip.ptr(stats[0]), hip.ptr(stats[1]), hip.ptr(running_mean, _f32), hip.ptr(running_var, _f32),
+                    hip.ptr(ws), N * H * W, C, eps, momentum, slope, hip.dtype_code(x), hip.stream())
             ctx.save_for_backward(x, b, w, stats)            # not y: the backward recomputes the activation decision from x
             ctx.slope = slope
             return y
-        PROFILER.run(f'bn_act_fwd[{N}x{C}x{H}x{W} {_tag(x)}]', 3 * x.numel() * _es(x), lambda: hip.check(
-            hip.lib().ge_bn_act_fwd(hip.ptr(x, name='x'), hip.ptr(w), hip.ptr(b), hip.ptr(y), hip.ptr(stats[0]), hip.ptr(stats[1]),
-                                    hip.ptr(running_mean, _f32), hip.ptr(running_var, _f32), hip.ptr(ws), N, C, H * W, eps,
-                                    momentum, slope, hip.dtype_code(x), hip.stream()), 'ge_bn_act_fwd'))
+        _launch(f'bn_act_fwd[{N}x{C}x{H}x{W} {_tag(x)}]', 3 * x.numel() * _es(x), 'ge_bn_act_fwd', hip.ptr(x, name='x'), hip.ptr(w), hip.ptr(b),
+                hip.ptr(y), hip.ptr(stats[0]), hip.ptr(stats[1]), hip.ptr(running_mean, _f32), hip.ptr(running_var, _f32), hip.ptr(ws), N, C, H * W,
+                eps, momentum, slope, hip.dtype_code(x), hip.stream())
         ctx.save_for_backward(x, y, w, stats)
         ctx.slope = slope
         return y
@@ -1731,16 +1649,14 @@ class _BNAct(torch.autograd.Function):
         ws = torch.empty(int(hip.lib().ge_nhwc_workspace(C, 2) if ctx.cl else hip.lib().ge_bn_workspace(C)), device=x.device, dtype=torch.uint8)
         if ctx.cl:
             dy = _cl(dy.to(x.dtype))
-            PROFILER.run(f'bn_act_nhwc_bwd[{N}x{C}x{H}x{W} {_tag(x)}]', 5 * x.numel() * _es(x), lambda: hip.check(
-                hip.lib().ge_bn_act_nhwc_bwd(_raw_ptr(dy, 'dy'), None, _raw_ptr(x, 'x'), hip.ptr(w), hip.ptr(y, _f32), hip.ptr(stats[0]), hip.ptr(stats[1]),
-                                             _raw_ptr(dx, 'dx'), hip.ptr(dwb[0]), hip.ptr(dwb[1]), hip.ptr(ws), N * H * W, C, ctx.slope,
-                                             hip.dtype_code(x), hip.stream()), 'ge_bn_act_nhwc_bwd'))
+            _launch(f'bn_act_nhwc_bwd[{N}x{C}x{H}x{W} {_tag(x)}]', 5 * x.numel() * _es(x), 'ge_bn_act_nhwc_bwd', _raw_ptr(dy, 'dy'), None,
+                    _raw_ptr(x, 'x'), hip.ptr(w), hip.ptr(y, _f32), hip.ptr(stats[0]), hip.ptr(stats[1]), _raw_ptr(dx, 'dx'), hip.ptr(dwb[0]),
+                    hip.ptr(dwb[1]), hip.ptr(ws), N * H * W, C, ctx.slope, hip.dtype_code(x), hip.stream())
             return dx, dwb[0], dwb[1], None, None, None, None, None
         dy = _c(dy.to(x.dtype))
-        PROFILER.run(f'bn_act_bwd[{N}x{C}x{H}x{W} {_tag(x)}]', 7 * x.numel() * _es(x), lambda: hip.check(
-            hip.lib().ge_bn_act_bwd(hip.ptr(dy), hip.ptr(y), hip.ptr(x), hip.ptr(w), hip.ptr(stats[0]), hip.ptr(stats[1]), hip.ptr(dx),
-                                    hip.ptr(dwb[0]), hip.ptr(dwb[1]), hip.ptr(ws), N, C, H * W, ctx.slope, hip.dtype_code(x),
-                                    hip.stream()), 'ge_bn_act_bwd'))
+        _launch(f'bn_act_bwd[{N}x{C}x{H}x{W} {_tag(x)}]', 7 * x.numel() * _es(x), 'ge_bn_act_bwd', hip.ptr(dy), hip.ptr(y), hip.ptr(x), hip.ptr(w),
+                hip.ptr(stats[0]), hip.ptr(stats[1]), hip.ptr(dx), hip.ptr(dwb[0]), hip.ptr(dwb[1]), hip.ptr(ws), N, C, H * W, ctx.slope,
+                hip.dtype_code(x), hip.stream())
         return dx, dwb[0], dwb[1], None, None, None, None, None
 
 
@@ -1775,13 +1691,13 @@ class _Conv1x1BNActPos(torch.autograd.Function):
         coef = torch.empty(2, Cout, device=dev, dtype=_f32)
         y = torch.empty((B, Cout, H, W), device=dev, dtype=x.dtype, memory_format=_CL)
         q = torch.empty(B, HW, Cout, device=dev, dtype=x.dtype) if pos_rows is not None else None
-        PROFILER.run(f'conv1x1_bn_stats[{B}x{Cin}->{Cout} {H}x{W}]', x.numel() * 2, lambda: hip.check(lib.ge_conv1x1_bn_stats(
-            _raw_ptr(x, 'x'), rows, Cin, hip.ptr(wc), Cout, hip.ptr(g32), hip.ptr(b32), hip.ptr(running_mean, _f32), hip.ptr(running_var, _f32),
-            eps, momentum, hip.ptr(gram), hip.ptr(stats[0]), hip.ptr(stats[1]), hip.ptr(coef), hip.ptr(ws), hip.stream()), 'ge_conv1x1_bn_stats'))
-        PROFILER.run(f'conv1x1_bn_act_fwd[{B}x{Cin}->{Cout} {H}x{W}{" +pos" if q is not None else ""}]',
-                     x.numel() * 2 + y.numel() * 2 * (1 + (q is not None)) + (HW * Cout * 4 if q is not None else 0), lambda: hip.check(
-            lib.ge_conv1x1_bn_act_fwd(_raw_ptr(x, 'x'), hip.ptr(wc), hip.ptr(coef), hip.ptr(pos_rows, _f32), _raw_ptr(y, 'y'), hip.ptr(q), B, HW, Cin, Cout,
-                                      slope, hip.stream()), 'ge_conv1x1_bn_act_fwd'))
+        _launch(f'conv1x1_bn_stats[{B}x{Cin}->{Cout} {H}x{W}]', x.numel() * 2, 'ge_conv1x1_bn_stats', _raw_ptr(x, 'x'), rows, Cin, hip.ptr(wc), Cout,
+                hip.ptr(g32), hip.ptr(b32), hip.ptr(running_mean, _f32), hip.ptr(running_var, _f32), eps, momentum, hip.ptr(gram), hip.ptr(stats[0]),
+                hip.ptr(stats[1]), hip.ptr(coef), hip.ptr(ws), hip.stream())
+        _launch(f'conv1x1_bn_act_fwd[{B}x{Cin}->{Cout} {H}x{W}{" +pos" if q is not None else ""}]',
+                x.numel() * 2 + y.numel() * 2 * (1 + (q is not None)) + (HW * Cout * 4 if q is not None else 0), 'ge_conv1x1_bn_act_fwd',
+                _raw_ptr(x, 'x'), hip.ptr(wc), hip.ptr(coef), hip.ptr(pos_rows, _f32), _raw_ptr(y, 'y'), hip.ptr(q), B, HW, Cin, Cout, slope,
+                hip.stream())
         ctx.save_for_backward(x, wc, g32, stats, gram, y)
         ctx.meta = (slope, weight.dtype, gamma.dtype, beta.dtype)
         ctx.weight_ref = weight if isinstance(weight, torch.nn.Parameter) else None
@@ -1812,26 +1728,25 @@ class _Conv1x1BNActPos(torch.autograd.Function):
         ws = torch.empty(int(lib.ge_conv1x1_bn_workspace(Cin, Cout)), device=dev, dtype=torch.uint8)
         g = torch.empty(rows, Cout, device=dev, dtype=x.dtype)
         m1 = torch.empty(Cout, device=dev, dtype=_f32)
-        PROFILER.run(f'conv1x1_bn_bwd_mask[{B}x{Cout} {H}x{W}]', g.numel() * 2 * (2 + (dy is not None) + (dq is not None)), lambda: hip.check(
-            lib.ge_conv1x1_bn_bwd_mask(hip.ptr(dq), Cout, None if dy is None else _raw_ptr(dy, 'dy'), ld_y, _raw_ptr(y, 'y'), hip.ptr(g), hip.ptr(m1),
-                                       hip.ptr(ws), rows, Cout, slope, hip.stream()), 'ge_conv1x1_bn_bwd_mask'))
+        _launch(f'conv1x1_bn_bwd_mask[{B}x{Cout} {H}x{W}]', g.numel() * 2 * (2 + (dy is not None) + (dq is not None)), 'ge_conv1x1_bn_bwd_mask',
+                hip.ptr(dq), Cout, None if dy is None else _raw_ptr(dy, 'dy'), ld_y, _raw_ptr(y, 'y'), hip.ptr(g), hip.ptr(m1), hip.ptr(ws), rows,
+                Cout, slope, hip.stream())
         GT = torch.zeros(Cout, Cin, device=dev, dtype=_f32)
-        PROFILER.run(f'conv1x1_wgrad[{B}x{Cin}->{Cout} {H}x{W}]', (x.numel() + g.numel()) * 2 + GT.numel() * 4, lambda: hip.check(
-            lib.ge_conv1x1_nhwc_wgrad(_raw_ptr(x, 'x'), hip.ptr(g), hip.ptr(GT), rows, Cin, Cout, hip.GE_BF16, hip.stream()), 'ge_conv1x1_nhwc_wgrad'))
+        _launch(f'conv1x1_wgrad[{B}x{Cin}->{Cout} {H}x{W}]', (x.numel() + g.numel()) * 2 + GT.numel() * 4, 'ge_conv1x1_nhwc_wgrad', _raw_ptr(x, 'x'),
+                hip.ptr(g), hip.ptr(GT), rows, Cin, Cout, hip.GE_BF16, hip.stream())
         small = torch.empty(2 * Cout + Cout * Cin + 2 * Cout, device=dev, dtype=_f32)
         dgamma, dbeta, dW, scratch = small[:Cout], small[Cout:2 * Cout], small[2 * Cout:2 * Cout + Cout * Cin].view(Cout, Cin), small[2 * Cout + Cout * Cin:]
         Wd = torch.empty(Cin, Cout + Cin, device=dev, dtype=x.dtype)
         c0 = torch.empty(Cin, device=dev, dtype=_f32)
-        hip.check(lib.ge_conv1x1_bn_bwd_finalize(hip.ptr(GT), hip.ptr(m1), hip.ptr(gram), hip.ptr(wc), hip.ptr(g32), hip.ptr(stats[0]), hip.ptr(stats[1]),
-                                                 rows, Cin, Cout, hip.ptr(dgamma), hip.ptr(dbeta), hip.ptr(dW), hip.ptr(Wd), hip.ptr(c0),
-                                                 hip.ptr(scratch), hip.stream()), 'ge_conv1x1_bn_bwd_finalize')
+        hip.call('ge_conv1x1_bn_bwd_finalize', hip.ptr(GT), hip.ptr(m1), hip.ptr(gram), hip.ptr(wc), hip.ptr(g32), hip.ptr(stats[0]),
+                 hip.ptr(stats[1]), rows, Cin, Cout, hip.ptr(dgamma), hip.ptr(dbeta), hip.ptr(dW), hip.ptr(Wd), hip.ptr(c0), hip.ptr(scratch),
+                 hip.stream())
         dx = None
         if ctx.needs_input_grad[0]:
             # the convolution's data gradient with the BatchNorm scale folded into the weights + the rank-64 corrections of the BatchNorm backward
             dx = torch.empty_like(x)
-            PROFILER.run(f'conv1x1_bn_dgrad[{B}x{Cout}->{Cin} {H}x{W}]', (g.numel() + 2 * x.numel()) * 2, lambda: hip.check(
-                lib.ge_conv1x1_bn_dgrad(hip.ptr(g), _raw_ptr(x, 'x'), hip.ptr(Wd), hip.ptr(c0), _raw_ptr(dx, 'dx'), rows, Cin, Cout, hip.stream()),
-                'ge_conv1x1_bn_dgrad'))
+            _launch(f'conv1x1_bn_dgrad[{B}x{Cout}->{Cin} {H}x{W}]', (g.numel() + 2 * x.numel()) * 2, 'ge_conv1x1_bn_dgrad', hip.ptr(g),
+                    _raw_ptr(x, 'x'), hip.ptr(Wd), hip.ptr(c0), _raw_ptr(dx, 'dx'), rows, Cin, Cout, hip.stream())
         dw = dW.view(Cout, Cin, 1, 1)
         if ctx.weight_ref is not None:
             from .mmrt.optim import grad_into_arena
@@ -1874,16 +1789,14 @@ class _BiasAct(torch.autograd.Function):
         N, C, H, W = x.shape
         b = _c(bias.detach().to(_f32))
         if ctx.cl:
-            PROFILER.run(f'bias_act_nhwc_fwd[{N}x{C}x{H}x{W} {_tag(x)}]', 2 * x.numel() * _es(x), lambda: hip.check(
-                hip.lib().ge_bias_act_nhwc_fwd(_raw_ptr(x, 'x'), hip.ptr(b), N * H * W, C, slope, hip.dtype_code(x), hip.stream()),
-                'ge_bias_act_nhwc_fwd'))
+            _launch(f'bias_act_nhwc_fwd[{N}x{C}x{H}x{W} {_tag(x)}]', 2 * x.numel() * _es(x), 'ge_bias_act_nhwc_fwd', _raw_ptr(x, 'x'), hip.ptr(b),
+                    N * H * W, C, slope, hip.dtype_code(x), hip.stream())
             ctx.mark_dirty(x)
             ctx.save_for_backward(x)
             ctx.slope = slope
             return x
-        PROFILER.run(f'bias_act_fwd[{N}x{C}x{H}x{W} {_tag(x)}]', 2 * x.numel() * _es(x), lambda: hip.check(
-            hip.lib().ge_bias_act_fwd(hip.ptr(x, name='x'), hip.ptr(b), N, C, H * W, slope, hip.dtype_code(x), hip.stream()),
-            'ge_bias_act_fwd'))
+        _launch(f'bias_act_fwd[{N}x{C}x{H}x{W} {_tag(x)}]', 2 * x.numel() * _es(x), 'ge_bias_act_fwd', hip.ptr(x, name='x'), hip.ptr(b), N, C, H * W,
+                slope, hip.dtype_code(x), hip.stream())
         ctx.mark_dirty(x)
         ctx.save_for_backward(x)
         ctx.slope = slope
@@ -1898,15 +1811,13 @@ class _BiasAct(torch.autograd.Function):
             dy = _cl(dy.to(y.dtype))
             db = torch.empty(C, device=y.device, dtype=_f32)
             ws = torch.empty(int(hip.lib().ge_nhwc_workspace(C, 1)), device=y.device, dtype=torch.uint8)
-            PROFILER.run(f'bias_act_nhwc_bwd[{N}x{C}x{H}x{W} {_tag(y)}]', 3 * y.numel() * _es(y), lambda: hip.check(
-                hip.lib().ge_bias_act_nhwc_bwd(_raw_ptr(dy, 'dy'), _raw_ptr(y, 'y'), _raw_ptr(dx, 'dx'), hip.ptr(db), hip.ptr(ws), N * H * W, C,
-                                               ctx.slope, hip.dtype_code(y), hip.stream()), 'ge_bias_act_nhwc_bwd'))
+            _launch(f'bias_act_nhwc_bwd[{N}x{C}x{H}x{W} {_tag(y)}]', 3 * y.numel() * _es(y), 'ge_bias_act_nhwc_bwd', _raw_ptr(dy, 'dy'),
+                    _raw_ptr(y, 'y'), _raw_ptr(dx, 'dx'), hip.ptr(db), hip.ptr(ws), N * H * W, C, ctx.slope, hip.dtype_code(y), hip.stream())
             return dx, db, None
         dy = _c(dy.to(y.dtype))
         db = torch.zeros(C, device=y.device, dtype=_f32)
-        PROFILER.run(f'bias_act_bwd[{N}x{C}x{H}x{W} {_tag(y)}]', 3 * y.numel() * _es(y), lambda: hip.check(
-            hip.lib().ge_bias_act_bwd(hip.ptr(dy), hip.ptr(y), hip.ptr(dx), hip.ptr(db), N, C, H * W, ctx.slope,
-                                      hip.dtype_code(y), hip.stream()), 'ge_bias_act_bwd'))
+        _launch(f'bias_act_bwd[{N}x{C}x{H}x{W} {_tag(y)}]', 3 * y.numel() * _es(y), 'ge_bias_act_bwd', hip.ptr(dy), hip.ptr(y), hip.ptr(dx),
+                hip.ptr(db), N, C, H * W, ctx.slope, hip.dtype_code(y), hip.stream())
         return dx, db, None
 
 
@@ -1940,10 +1851,8 @@ class _GroundEmbedAdaptive(torch.autograd.Function):
         valid = torch.empty(B, H, W, device=dev, dtype=torch.uint8)
         height = None if height is None else _c(height.to(_f32))
         nbytes = B * H * W * (4 + 4 + 44 + 4 + 1) + B * h * w * 12 * 4
-        PROFILER.run(f'ground_embed_fwd[{B}x{H}x{W}]', nbytes, lambda: hip.check(hip.lib().ge_ground_embed_fwd(
-            hip.ptr(logits_lr), hip.ptr(y_lr), pe.data_ptr(), bs, hip.ptr(height), depth_scale,
-            hip.ptr(pe_mask), hip.ptr(logits_hr), hip.ptr(y_hr), hip.ptr(valid), B, h, w, H, W, hip.stream()),
-            'ge_ground_embed_fwd'))
+        _launch(f'ground_embed_fwd[{B}x{H}x{W}]', nbytes, 'ge_ground_embed_fwd', hip.ptr(logits_lr), hip.ptr(y_lr), pe.data_ptr(), bs,
+                hip.ptr(height), depth_scale, hip.ptr(pe_mask), hip.ptr(logits_hr), hip.ptr(y_hr), hip.ptr(valid), B, h, w, H, W, hip.stream())
         ctx.save_for_backward(logits_lr, y_lr, img, height)
         ctx.depth_scale = depth_scale
         ctx.mark_non_differentiable(valid)
@@ -1963,10 +1872,9 @@ class _GroundEmbedAdaptive(torch.autograd.Function):
         d_y_lr = torch.empty_like(y_lr)
         scratch = torch.empty(B, 12, H, W, device=dev, dtype=_f32)
         nbytes = B * H * W * (4 + 4 + 44 + 4) + 2 * B * h * w * 12 * 4
-        PROFILER.run(f'ground_embed_bwd[{B}x{H}x{W}]', nbytes, lambda: hip.check(hip.lib().ge_ground_embed_bwd(
-            hip.ptr(logits_lr), hip.ptr(y_lr), pe.data_ptr(), bs, hip.ptr(height), ctx.depth_scale,
-            hip.ptr(d_pe_mask), hip.ptr(d_logits_hr), hip.ptr(d_y_hr), hip.ptr(d_logits_lr), hip.ptr(d_y_lr),
-            hip.ptr(scratch), B, h, w, H, W, hip.stream()), 'ge_ground_embed_bwd'))
+        _launch(f'ground_embed_bwd[{B}x{H}x{W}]', nbytes, 'ge_ground_embed_bwd', hip.ptr(logits_lr), hip.ptr(y_lr), pe.data_ptr(), bs,
+                hip.ptr(height), ctx.depth_scale, hip.ptr(d_pe_mask), hip.ptr(d_logits_hr), hip.ptr(d_y_hr), hip.ptr(d_logits_lr), hip.ptr(d_y_lr),
+                hip.ptr(scratch), B, h, w, H, W, hip.stream())
         return d_logits_lr, d_y_lr, None, None, None
 
 
@@ -1985,8 +1893,7 @@ class _GroundEmbedVanilla(torch.autograd.Function):
         pe, bs = _plane_view(img, 3)
         pe_mask = torch.empty(B, 1, H, W, device=img.device, dtype=_f32)
         y_hr = torch.empty(B, 1, H, W, device=img.device, dtype=_f32)
-        hip.check(hip.lib().ge_ground_vanilla_fwd(hip.ptr(y_lr), pe.data_ptr(), bs, gain, hip.ptr(pe_mask), hip.ptr(y_hr),
-                                                  B, h, w, H, W, hip.stream()), 'ge_ground_vanilla_fwd')
+        hip.call('ge_ground_vanilla_fwd', hip.ptr(y_lr), pe.data_ptr(), bs, gain, hip.ptr(pe_mask), hip.ptr(y_hr), B, h, w, H, W, hip.stream())
         ctx.save_for_backward(img)
         ctx.geom = (B, h, w, H, W, gain)
         return pe_mask, y_hr
@@ -2000,8 +1907,8 @@ class _GroundEmbedVanilla(torch.autograd.Function):
         d_y_hr = None if d_y_hr is None else _c(d_y_hr.to(_f32))
         d_y_lr = torch.empty(B, 1, h, w, device=img.device, dtype=_f32)
         scratch = torch.empty(B, 1, H, W, device=img.device, dtype=_f32)
-        hip.check(hip.lib().ge_ground_vanilla_bwd(pe.data_ptr(), bs, gain, hip.ptr(d_pe_mask), hip.ptr(d_y_hr), hip.ptr(d_y_lr),
-                                                  hip.ptr(scratch), B, h, w, H, W, hip.stream()), 'ge_ground_vanilla_bwd')
+        hip.call('ge_ground_vanilla_bwd', pe.data_ptr(), bs, gain, hip.ptr(d_pe_mask), hip.ptr(d_y_hr), hip.ptr(d_y_lr), hip.ptr(scratch), B, h, w, H,
+                 W, hip.stream())
         return d_y_lr, None, None
 
 
@@ -2022,8 +1929,8 @@ class _DepthFuse(torch.autograd.Function):
         H, W = pe_mask.shape[2], pe_mask.shape[3]
         out = torch.empty_like(c)
         y_ds = torch.empty_like(c)
-        hip.check(hip.lib().ge_depth_fuse_fwd(hip.ptr(c), hip.ptr(pe_mask), hip.ptr(y_hr), min_depth, hip.ptr(out), hip.ptr(y_ds),
-                                              B, h, w, H, W, hip.stream()), 'ge_depth_fuse_fwd')
+        hip.call('ge_depth_fuse_fwd', hip.ptr(c), hip.ptr(pe_mask), hip.ptr(y_hr), min_depth, hip.ptr(out), hip.ptr(y_ds), B, h, w, H, W,
+                 hip.stream())
         ctx.save_for_backward(c, y_ds)
         ctx.geom = (B, h, w, H, W)
         ctx.mark_non_differentiable(y_ds)
@@ -2038,8 +1945,8 @@ class _DepthFuse(torch.autograd.Function):
         d_pe = torch.empty(B, 1, H, W, device=c.device, dtype=_f32)
         d_y = torch.empty(B, 1, H, W, device=c.device, dtype=_f32)
         scratch = torch.empty(B, 2, h, w, device=c.device, dtype=_f32)
-        hip.check(hip.lib().ge_depth_fuse_bwd(hip.ptr(c), hip.ptr(y_ds), hip.ptr(d_out), hip.ptr(d_c), hip.ptr(d_pe), hip.ptr(d_y),
-                                              hip.ptr(scratch), B, h, w, H, W, hip.stream()), 'ge_depth_fuse_bwd')
+        hip.call('ge_depth_fuse_bwd', hip.ptr(c), hip.ptr(y_ds), hip.ptr(d_out), hip.ptr(d_c), hip.ptr(d_pe), hip.ptr(d_y), hip.ptr(scratch), B, h, w,
+                 H, W, hip.stream())
         return d_c, d_pe, d_y, None
 
 
@@ -2056,8 +1963,7 @@ class _SiLog(torch.autograd.Function):
         pred = _c(pred.to(_f32))
         gt = _c(gt.to(_f32))
         stats = torch.zeros(3, device=pred.device, dtype=torch.float64)
-        hip.check(hip.lib().ge_silog_stats(hip.ptr(pred), hip.ptr(gt), eps, hip.ptr(stats), pred.numel(), hip.stream()),
-                  'ge_silog_stats')
+        hip.call('ge_silog_stats', hip.ptr(pred), hip.ptr(gt), eps, hip.ptr(stats), pred.numel(), hip.stream())
         n, s1, s2 = stats[0], stats[1], stats[2]
         mean = s1 / n
         var = (s2 - n * mean * mean) / (n - 1)          # torch.var: unbiased
@@ -2073,8 +1979,7 @@ class _SiLog(torch.autograd.Function):
         coef_a = (k * 2.0 / (n - 1)).to(_f32).reshape(1).contiguous()
         coef_b = (k * (-2.0 * mean / (n - 1) + 0.3 * mean / n)).to(_f32).reshape(1).contiguous()
         d_pred = torch.empty_like(pred)
-        hip.check(hip.lib().ge_silog_bwd(hip.ptr(pred), hip.ptr(gt), ctx.eps, hip.ptr(coef_a), hip.ptr(coef_b), hip.ptr(d_pred),
-                                         pred.numel(), hip.stream()), 'ge_silog_bwd')
+        hip.call('ge_silog_bwd', hip.ptr(pred), hip.ptr(gt), ctx.eps, hip.ptr(coef_a), hip.ptr(coef_b), hip.ptr(d_pred), pred.numel(), hip.stream())
         return d_pred, None, None, None
 
 
@@ -2089,8 +1994,7 @@ def ground_plane(rinv_row2, num, H, W, device='cuda', want_f64=True):
     arr = (ctypes.c_double * 3)(*[float(v) for v in rinv_row2])
     pe64 = torch.empty(H, W, device=device, dtype=torch.float64) if want_f64 else None
     pe32 = torch.empty(H, W, device=device, dtype=_f32)
-    hip.check(hip.lib().ge_ground_plane(ctypes.cast(arr, ctypes.c_void_p), float(num), hip.ptr(pe64), hip.ptr(pe32), H, W,
-                                        hip.stream()), 'ge_ground_plane')
+    hip.call('ge_ground_plane', ctypes.cast(arr, ctypes.c_void_p), float(num), hip.ptr(pe64), hip.ptr(pe32), H, W, hip.stream())
     return pe64, pe32
 
 
@@ -2099,8 +2003,7 @@ def slope_class(gt_f64, pe_f32, cam_height=1.65, mode='round'):
     pe_f32 = _c(pe_f32.to(_f32))
     H, W = gt_f64.shape
     cls = torch.empty(H, W, device=gt_f64.device, dtype=torch.int16)
-    hip.check(hip.lib().ge_slope_class(hip.ptr(gt_f64), hip.ptr(pe_f32), float(cam_height), 0 if mode == 'round' else 1,
-                                       hip.ptr(cls), H, W, hip.stream()), 'ge_slope_class')
+    hip.call('ge_slope_class', hip.ptr(gt_f64), hip.ptr(pe_f32), float(cam_height), 0 if mode == 'round' else 1, hip.ptr(cls), H, W, hip.stream())
     return cls
 
 
@@ -2110,15 +2013,14 @@ def slope_class_ddad(gt_f32, pe_f64, cam_height):
     pe_f64 = _c(pe_f64.to(torch.float64))
     H, W = gt_f32.shape
     cls = torch.empty(H, W, device=gt_f32.device, dtype=torch.int16)
-    hip.check(hip.lib().ge_slope_class_ddad(hip.ptr(gt_f32), hip.ptr(pe_f64), float(cam_height), hip.ptr(cls), H, W,
-                                            hip.stream()), 'ge_slope_class_ddad')
+    hip.call('ge_slope_class_ddad', hip.ptr(gt_f32), hip.ptr(pe_f64), float(cam_height), hip.ptr(cls), H, W, hip.stream())
     return cls
 
 
 def pe_channels(raw, depth_scale=200.0):
     raw = _c(raw.to(_f32))
     norm = torch.empty_like(raw)
-    hip.check(hip.lib().ge_pe_channels(hip.ptr(raw), hip.ptr(norm), float(depth_scale), raw.numel(), hip.stream()), 'ge_pe_channels')
+    hip.call('ge_pe_channels', hip.ptr(raw), hip.ptr(norm), float(depth_scale), raw.numel(), hip.stream())
     return norm
 
 
@@ -2136,9 +2038,9 @@ def infer_front(bgr, pe, out, top, left, mean, std, to_rgb=True, pe_max=200.0, d
     assert C == 5
     m = (ctypes.c_double * 3)(*[float(v) for v in mean])
     s = (ctypes.c_double * 3)(*[float(v) for v in std])
-    hip.check(hip.lib().ge_infer_front(hip.ptr(bgr, torch.uint8, 'bgr'), hip.ptr(pe, _f32, 'pe'), hip.ptr(out, _f32, 'out'), H, W, int(top),
-                                       int(left), Hc, Wc, views, float(pe_max), ctypes.cast(m, ctypes.c_void_p), ctypes.cast(s, ctypes.c_void_p),
-                                       float(depth_scale), int(bool(to_rgb)), hip.stream()), 'ge_infer_front')
+    hip.call('ge_infer_front', hip.ptr(bgr, torch.uint8, 'bgr'), hip.ptr(pe, _f32, 'pe'), hip.ptr(out, _f32, 'out'), H, W, int(top), int(left), Hc,
+             Wc, views, float(pe_max), ctypes.cast(m, ctypes.c_void_p), ctypes.cast(s, ctypes.c_void_p), float(depth_scale), int(bool(to_rgb)),
+             hip.stream())
     return out
 
 
@@ -2148,7 +2050,7 @@ def tta_merge(pred, out=None):
     assert V == 2 and C == 1
     if out is None:
         out = torch.empty(1, H, W, device=pred.device, dtype=_f32)
-    hip.check(hip.lib().ge_tta_merge(hip.ptr(pred, _f32, 'pred'), hip.ptr(out, _f32, 'out'), H, W, hip.stream()), 'ge_tta_merge')
+    hip.call('ge_tta_merge', hip.ptr(pred, _f32, 'pred'), hip.ptr(out, _f32, 'out'), H, W, hip.stream())
     return out
 
 
@@ -2190,7 +2092,6 @@ def depth_colorize(value, vmin, vmax, lut):
     if flags & (hip.GE_COLORIZE_VMIN_DATA | hip.GE_COLORIZE_VMAX_DATA):
         ws = torch.empty(512, device=value.device, dtype=_f32)       # partial (min, max) pairs, from the caching allocator
     out = torch.empty(tuple(value.shape) + (3,), device=value.device, dtype=torch.uint8)
-    hip.check(hip.lib().ge_depth_colorize(hip.ptr(value, _f32, 'value'), value.numel(), lo, hi, den, flags, hip.ptr(ws, _f32, 'ws'),
-                                          hip.ptr(_c(lut), torch.uint8, 'lut'), lut.shape[0] - 3, hip.ptr(out, torch.uint8, 'out'),
-                                          hip.stream()), 'ge_depth_colorize')
+    hip.call('ge_depth_colorize', hip.ptr(value, _f32, 'value'), value.numel(), lo, hi, den, flags, hip.ptr(ws, _f32, 'ws'),
+             hip.ptr(_c(lut), torch.uint8, 'lut'), lut.shape[0] - 3, hip.ptr(out, torch.uint8, 'out'), hip.stream())
     return out

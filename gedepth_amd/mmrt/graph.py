@@ -132,7 +132,7 @@ class GraphedTrainStep:
         # the dropout kernels read the registered counter address at LAUNCH time, so it is baked into the captured kernel arguments: it only
         # has to be registered while this capture runs (a process-wide slot that outlived the capture could be cleared under a newer object,
         # or point at another device's counter)
-        hip.check(lib.ge_rng_salt(self.salt.data_ptr()), 'ge_rng_salt')
+        hip.call('ge_rng_salt', self.salt.data_ptr())
         ddp_on = self.ddp is not None and getattr(self.ddp, 'active', False)
         rec0 = _fr_last_record_id() if ddp_on else -1
         try:

@@ -309,19 +309,17 @@ class FusedAdamW(torch.optim.Optimizer):
     @torch.no_grad()
     def launch(self):
         """Device half of a step: gradient norm + clip + AdamW (+ bf16 shadow) over the arenas.  Capturable."""
-        lib, a = hip.lib(), self.arena
+        a = self.arena
         a.collect()                            # gradients autograd handed over (not yet brought in by FlatDDP) -> arena
         self.gnorm_sq.zero_()
-        hip.check(lib.ge_sumsq(hip.ptr(a.flat_grad), a.numel, hip.ptr(self.gnorm_sq), hip.stream()), 'ge_sumsq')
+        hip.call('ge_sumsq', hip.ptr(a.flat_grad), a.numel, hip.ptr(self.gnorm_sq), hip.stream())
         shadow = getattr(a, 'flat_shadow', None)
         if shadow is None:
-            hip.check(lib.ge_adamw_step(hip.ptr(a.flat_param), hip.ptr(a.flat_grad), hip.ptr(self.exp_avg), hip.ptr(self.exp_avg_sq),
-                                        hip.ptr(self.wd_mask), hip.ptr(self.hyper), hip.ptr(self.gnorm_sq), a.numel,
-                                        hip.stream()), 'ge_adamw_step')
+            hip.call('ge_adamw_step', hip.ptr(a.flat_param), hip.ptr(a.flat_grad), hip.ptr(self.exp_avg), hip.ptr(self.exp_avg_sq),
+                     hip.ptr(self.wd_mask), hip.ptr(self.hyper), hip.ptr(self.gnorm_sq), a.numel, hip.stream())
         else:
-            hip.check(lib.ge_adamw_step_shadow(hip.ptr(a.flat_param), hip.ptr(a.flat_grad), hip.ptr(self.exp_avg),
-                                               hip.ptr(self.exp_avg_sq), hip.ptr(self.wd_mask), hip.ptr(self.hyper),
-                                               hip.ptr(self.gnorm_sq), a.numel, hip.ptr(shadow), hip.stream()), 'ge_adamw_step_shadow')
+            hip.call('ge_adamw_step_shadow', hip.ptr(a.flat_param), hip.ptr(a.flat_grad), hip.ptr(self.exp_avg), hip.ptr(self.exp_avg_sq),
+                     hip.ptr(self.wd_mask), hip.ptr(self.hyper), hip.ptr(self.gnorm_sq), a.numel, hip.ptr(shadow), hip.stream())
             a.refresh_shadow(copy=False)
 
     @torch.no_grad()

@@ -159,6 +159,41 @@ def test_library_exports_every_declared_symbol():
     assert hip.lib().ge_window_attn_bwd_workspace(2, 11, 35, 3) > 0
 
 
+def test_signatures_parsed_from_the_header():
+    """hip.SIGNATURES is derived from include/gedepth_hip.h: hand-written (restype, argtypes) of entry points that together use every
+    scalar type the parser maps (double; long, float, uint64_t; a size_t return and a host int*; a size_t argument; (void))."""
+    c = ctypes
+    vp, i, l, f, d, sz, u64 = c.c_void_p, c.c_int, c.c_long, c.c_float, c.c_double, c.c_size_t, c.c_ulonglong
+    expected = {
+        'ge_ground_plane': (i, [vp, d, vp, vp, i, i, vp]),
+        'ge_tokens_from_map': (i, [vp, l, vp, vp, l, i, i, l, f, u64, i, vp]),
+        'ge_msda_bwd_workspace': (sz, [vp, i, i, i, i, i, i]),
+        'ge_msda_bwd_value_mm': (i, [vp, vp, l, vp, l, vp, l, l, l, vp, vp, vp, vp, sz, i, i, i, i, i, i, i, i, vp]),
+        'ge_abi_version': (i, []),
+    }
+    for name, (res, args) in expected.items():
+        got_res, got_args = hip.SIGNATURES[name]
+        assert got_res is res and list(got_args) == args, name
+    assert len(hip.SIGNATURES) == 102
+
+
+def test_header_parser_is_strict():
+    """A parameter type the binding does not map, or a ``ge_`` declaration the pattern cannot read, raises (and names the function)
+    instead of binding something else."""
+    ok = '/* ge_note(1) in a comment */ int ge_a(const void* x, unsigned long long seed, void* stream);\nsize_t ge_b(void);  // ge_c(\n'
+    assert hip.parse_header(ok) == {'ge_a': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_ulonglong, ctypes.c_void_p]), 'ge_b': (ctypes.c_size_t, [])}
+    with pytest.raises(TypeError, match='ge_a'):
+        hip.parse_header('int ge_a(const void* x, short n, void* stream);')
+    with pytest.raises(TypeError, match='ge_a'):
+        hip.parse_header('int ge_a(unsigned n);')
+    with pytest.raises(TypeError, match='ge_b'):
+        hip.parse_header('int ge_a(int n);\nvoid ge_b(int n);')                       # a return type outside int | size_t
+    with pytest.raises(TypeError, match='ge_cb'):
+        hip.parse_header('int ge_cb(int (*fn)(int), void* stream);')                  # nested parentheses
+    with pytest.raises(TypeError, match='ge_a'):
+        hip.parse_header('int ge_a(int n)')                                           # no terminating semicolon
+
+
 def test_msda_mm_location_division_is_ieee_division(tmp_path):
     """csrc/msda_mm.hip forms `offset / W` as q0 = off * RN(1/W), q = fma(fma(-q0, W, off), RN(1/W), q0).  The kink decisions of
     floor() in the sampling kernels hang on the last bit of that quotient, so the claim "bit-identical to IEEE division" is checked
