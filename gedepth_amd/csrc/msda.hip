@@ -579,12 +579,41 @@ __device__ __forceinline__ float msda_half_sum(float v) {
   const float a = readlane_f(v, 31), b = readlane_f(v, 63);
   return (threadIdx.x & 32) ? b : a;
 }
-template <bool FILL>
-__global__ void __launch_bounds__(1024) msda_hist_raw_k(MsdaLevels lv, MsdaBins bins, MsdaRawIn in, MsdaWs ws, int Nq, int nH, int R, int B,
+// Memory-level parallelism inside the lane (the CU is full at two 1024-thread workgroups, so it cannot come from more threads): a lane
+// takes U sampling points per trip — points j0 + t * 1024 + lane, t < U — and issues the offset, reference-point and logit loads of all
+// U before it consumes the first, so a wave has U independent request chains in flight instead of one.  The level of a lane's points
+// never changes (1024 % 32 == 0), so everything indexed by the level is read once per kernel, not once per point.  FILL: the LDS
+// atomics of S points are issued together and their record stores follow, so that no store waits behind the LDS round trip of the
+// next point; a point's (up to 4) slots stay in registers meanwhile.
+// Measured per launch, cross / self attention of the bench step (us; before: one point per trip, 35 / 55 VGPRs count / fill; none of
+// the variants below uses scratch; profiles/hist_pipeline_ab.txt):
+//   count  before 595 / 222 | U = 1: 432 / 155 (35 VGPRs: the hoisted level constants alone) | 2: 393 / 138 (40) | 4: 384 / 136 (50)
+//          | 8: 419 / 148 (70 VGPRs: one workgroup per CU)
+//   fill   before 1602 / 510 | U = 1: 1537 / 470 (55) | 2, S = 2: 1502 / 470 (64) | 4, S = 2 or 4: 1650 / 460 (78 / 86 VGPRs, one workgroup
+//          per CU) | 8, S = 2: 1460 / 457 (117 VGPRs, one workgroup per CU); forced into 64 VGPRs, U = 4 spills (52 - 92 bytes of scratch)
+//   fill with the record stores removed: 390 / 143 (U = 1), 339 / 122 (U = 4): three quarters of the fill pass are the scattered 8-byte
+//   stores, not the loads — batching can only shorten the rest.  U = 8 gains more from its 8 chains than it loses with half the threads.
+#ifndef MSDA_HIST_UC
+#define MSDA_HIST_UC 4         // count pass: two workgroups per CU
+#endif
+#ifndef MSDA_HIST_UF
+#define MSDA_HIST_UF 8         // fill pass: one workgroup per CU (up to 128 VGPRs)
+#endif
+#ifndef MSDA_HIST_S
+#define MSDA_HIST_S 2
+#endif
+template <bool FILL, int U, int S>
+__global__ void __launch_bounds__(1024, (FILL && U > 2) ? 4 : 8) msda_hist_raw_k(MsdaLevels lv, MsdaBins bins, MsdaRawIn in, MsdaWs ws, int Nq, int nH, int R, int B,
                                                         int level_mask) {
+  static_assert(U % S == 0, "whole groups of S points");
   extern __shared__ int hist[];
   const int ntiles = bins.first_tile[4];
   const int nunits = B * nH * R;
+  const int lp = threadIdx.x & 31, l = lp >> 3;                   // the lane's point of the (query, head) group and its level
+  const float fW = in.fW[l], fH = in.fH[l], rW = in.rW[l], rH = in.rH[l];
+  const int Hl = lv.H[l], Wl = lv.W[l];
+  const int ntx = bins.ntx[l], lb0 = bins.first_tile[l];
+  const bool level_on = (level_mask >> l) & 1;                    // levels whose d_value another kernel produces (ge_msda_bwd_value_mm) leave no records here
   for (int u = blockIdx.x; u < nunits; u += gridDim.x) {          // u = (b * nH + head) * R + r
     const int r = u % R, bh = u / R;
     const int head = bh % nH, b = bh / nH;
@@ -593,47 +622,77 @@ __global__ void __launch_bounds__(1024) msda_hist_raw_k(MsdaLevels lv, MsdaBins 
     __syncthreads();
     const int q_lo = (int)((long)Nq * r / R), q_hi = (int)((long)Nq * (r + 1) / R);
     const int n = (q_hi - q_lo) * 32;
-    for (int j0 = 0; j0 < n; j0 += 1024) {                        // uniform trip count per wave: the softmax needs whole half waves
-      const int j = j0 + threadIdx.x;
-      const bool live = j < n;
-      const int qi = live ? j >> 5 : 0, lp = j & 31, l = lp >> 3;
-      const int q = q_lo + qi;
-      const long row = (long)b * Nq + q;
-      const uint32_t o = *(const uint32_t*)(in.off + row * in.off_ld + head * 64 + lp * 2);
-      const float* rp = in.ref + (long)b * in.ref_sb + (long)q * in.ref_sq + (long)l * in.ref_sl;
-      const float fW = in.fW[l], fH = in.fH[l];
-      const float lx = rp[0] + msda_div(__uint_as_float(o << 16), fW, in.rW[l]);
-      const float ly = rp[1] + msda_div(__uint_as_float(o & 0xffff0000u), fH, in.rH[l]);
-      const float x = lx * fW - 0.5f, y = ly * fH - 0.5f;
-      float wgt = 0.f;
-      if (FILL) {
-        const float lg = bf2f(in.logit[row * in.logit_ld + head * 32 + lp]);
-        const float e = __expf(lg - msda_half_max(lg));
-        wgt = e * (1.f / msda_half_sum(e));
+    const long row0 = (long)b * Nq + q_lo;
+    const bf16_t* offp = in.off + row0 * in.off_ld + head * 64 + lp * 2;
+    const bf16_t* logp = in.logit + row0 * in.logit_ld + head * 32 + lp;
+    const float* refp = in.ref + (long)b * in.ref_sb + (long)q_lo * in.ref_sq + (long)l * in.ref_sl;
+    for (int j0 = 0; j0 < n; j0 += 1024 * U) {                    // uniform trip count per wave: the softmax needs whole half waves
+      uint32_t o[U];
+      float rx[U], ry[U];
+      bf16_t lgr[U];
+#pragma unroll
+      for (int t = 0; t < U; ++t) {                               // all loads of the batch first; a lane past the end reads query q_lo
+        const int j = j0 + t * 1024 + (int)threadIdx.x;
+        const long qi = j < n ? j >> 5 : 0;
+        o[t] = *(const uint32_t*)(offp + qi * in.off_ld);
+        const float* rp = refp + qi * in.ref_sq;
+        rx[t] = rp[0]; ry[t] = rp[1];
+        if (FILL) lgr[t] = logp[qi * in.logit_ld];
       }
-      // level_mask: levels whose d_value another kernel produces (ge_msda_bwd_value_mm) leave no records here
-      if (!(live && ((level_mask >> l) & 1) && y > -1.f && x > -1.f && y < fH && x < fW)) continue;
-      const int Hl = lv.H[l], Wl = lv.W[l];
-      const float xf = floorf(x), yf = floorf(y);
-      const int x0 = (int)xf, y0 = (int)yf;
-      const float ax = x - xf, ay = y - yf;
-      const int ntx = bins.ntx[l];
-      const int lb0 = bins.first_tile[l];
-      const bool xa = x0 >= 0, xb = x0 + 1 < Wl, ya = y0 >= 0, yb = y0 + 1 < Hl;
-      const int txa = x0 >> 3, txb = (x0 + 1) >> 3, tya = y0 >> 2, tyb = (y0 + 1) >> 2;
-      const int tx_first = xa ? txa : txb, ty_first = ya ? tya : tyb;
-      const int two_x = (xa && xb && txb != txa) ? 1 : 0, two_y = (ya && yb && tyb != tya) ? 1 : 0;
-      // bf16 weight, fractions at 8 bits (floor: the drain reads them back at the centre of the step)
-      const uint32_t packed = (uint32_t)f2bf(wgt) | ((uint32_t)min((int)(ax * 256.f), 255) << 16) | ((uint32_t)min((int)(ay * 256.f), 255) << 24);
-      for (int jy = 0; jy <= two_y; ++jy)
-        for (int jx = 0; jx <= two_x; ++jx) {
-          const int tx = jx ? txb : tx_first, ty = jy ? tyb : ty_first;
-          const int slot = atomicAdd(&hist[lb0 + mul24(ty, ntx) + tx], 1);        // LDS
+#pragma unroll
+      for (int g = 0; g < U; g += S) {
+        int slot[S][4], key[S];
+        uint32_t packed[S];
+#pragma unroll
+        for (int s = 0; s < S; ++s) {
+          const int t = g + s;
+          const int j = j0 + t * 1024 + (int)threadIdx.x;
+          const bool live = j < n;
+          const float lx = rx[t] + msda_div(__uint_as_float(o[t] << 16), fW, rW);
+          const float ly = ry[t] + msda_div(__uint_as_float(o[t] & 0xffff0000u), fH, rH);
+          const float x = lx * fW - 0.5f, y = ly * fH - 0.5f;
+          float wgt = 0.f;
           if (FILL) {
-            const int lx1 = x0 - tx * MSDA_TW + 1, ly1 = y0 - ty * MSDA_TH + 1;
-            ((int2*)ws.entries)[slot] = make_int2((q << 7) | (ly1 << 4) | lx1, (int)packed);
+            const float lg = bf2f(lgr[t]);
+            const float e = __expf(lg - msda_half_max(lg));
+            wgt = e * (1.f / msda_half_sum(e));
+          }
+          slot[s][0] = slot[s][1] = slot[s][2] = slot[s][3] = -1;
+          key[s] = 0; packed[s] = 0;
+          if (live && level_on && y > -1.f && x > -1.f && y < fH && x < fW) {
+            const float xf = floorf(x), yf = floorf(y);
+            const int x0 = (int)xf, y0 = (int)yf;
+            const float ax = x - xf, ay = y - yf;
+            // tile columns / rows that hold an in-image corner: the left column x0 (if >= 0) and the right column x0+1 (if < W); the
+            // second tile of a direction, if any, is the next one and the corner sits at its position 0
+            const bool xa = x0 >= 0, xb = x0 + 1 < Wl, ya = y0 >= 0, yb = y0 + 1 < Hl;
+            const int txa = x0 >> 3, txb = (x0 + 1) >> 3, tya = y0 >> 2, tyb = (y0 + 1) >> 2;
+            const int tx = xa ? txa : txb, ty = ya ? tya : tyb;
+            const bool two_x = xa && xb && txb != txa, two_y = ya && yb && tyb != tya;
+            int* h0 = hist + lb0 + mul24(ty, ntx) + tx;
+            const int lx1 = x0 - tx * MSDA_TW + 1, ly1 = y0 - ty * MSDA_TH + 1;       // top-left corner relative to the tile, +1: [0,8] x [0,4]
+            key[s] = ((q_lo + (j >> 5)) << 7) | (ly1 << 4) | lx1;
+            // bf16 weight, fractions at 8 bits (floor: the drain reads them back at the centre of the step)
+            packed[s] = (uint32_t)f2bf(wgt) | ((uint32_t)min((int)(ax * 256.f), 255) << 16) | ((uint32_t)min((int)(ay * 256.f), 255) << 24);
+            slot[s][0] = atomicAdd(h0, 1);                                            // LDS
+            if (two_x) slot[s][1] = atomicAdd(h0 + 1, 1);
+            if (two_y) {
+              slot[s][2] = atomicAdd(h0 + ntx, 1);
+              if (two_x) slot[s][3] = atomicAdd(h0 + ntx + 1, 1);
+            }
           }
         }
+        if (FILL) {
+          int2* rec = (int2*)ws.entries;
+#pragma unroll
+          for (int s = 0; s < S; ++s) {
+            if (slot[s][0] >= 0) rec[slot[s][0]] = make_int2(key[s], (int)packed[s]);
+            if (slot[s][1] >= 0) rec[slot[s][1]] = make_int2(key[s] & ~15, (int)packed[s]);
+            if (slot[s][2] >= 0) rec[slot[s][2]] = make_int2(key[s] & ~0x70, (int)packed[s]);
+            if (slot[s][3] >= 0) rec[slot[s][3]] = make_int2(key[s] & ~0x7f, (int)packed[s]);
+          }
+        }
+      }
     }
     __syncthreads();
     if (!FILL) {
@@ -1309,7 +1368,7 @@ extern "C" int ge_msda_bwd_value_raw_levels(const int* spatial_hw, const void* o
   if (he != hipSuccess) return (int)he;
   const unsigned hgrid = (unsigned)std::min((long)MSDA_HIST_WGS, (long)B * nH * pl.R);
   const size_t hsmem = (size_t)pl.ntiles * 4;
-  msda_hist_raw_k<false><<<hgrid, 1024, hsmem, s>>>(lv, bins, in, ws, Nq, nH, pl.R, B, level_mask);
+  msda_hist_raw_k<false, MSDA_HIST_UC, 1><<<hgrid, 1024, hsmem, s>>>(lv, bins, in, ws, Nq, nH, pl.R, B, level_mask);
   GE_LAUNCH_CHECK();
   msda_mark(ev, 2, s);
   msda_scan_k<<<1, 1024, 0, s>>>(ws, nbins);
@@ -1321,7 +1380,7 @@ extern "C" int ge_msda_bwd_value_raw_levels(const int* spatial_hw, const void* o
     GE_LAUNCH_CHECK();
   } else ws.order = nullptr;                               // bin order
   msda_mark(ev, 3, s);
-  msda_hist_raw_k<true><<<hgrid, 1024, hsmem, s>>>(lv, bins, in, ws, Nq, nH, pl.R, B, level_mask);
+  msda_hist_raw_k<true, MSDA_HIST_UF, MSDA_HIST_S><<<hgrid, 1024, hsmem, s>>>(lv, bins, in, ws, Nq, nH, pl.R, B, level_mask);
   GE_LAUNCH_CHECK();
   msda_mark(ev, 4, s);
   g_msda_drain_mfma_used = true;
