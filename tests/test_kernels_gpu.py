@@ -35,8 +35,9 @@ def close(a, b, rtol=RTOL, atol=ATOL, what=''):
     assert a.shape == b.shape, (what, a.shape, b.shape)
     err = (a - b).abs()
     tol = atol + rtol * b.abs()
-    bad = err > tol
-    assert not bool(bad.any()), (f'{what}: {int(bad.sum())}/{bad.numel()} off; max abs err {err.max():.3e} '
+    bad = ~(err <= tol)                      # a NaN / infinite error is not <= tol: a non-finite product value where the reference is finite fails
+    nonfinite = int((~torch.isfinite(a)).sum())
+    assert not bool(bad.any()), (f'{what}: {int(bad.sum())}/{bad.numel()} off ({nonfinite} non-finite); max abs err {err.nan_to_num(nan=float("inf")).max():.3e} '
                                  f'(ref scale {b.abs().max():.3e})')
 
 
@@ -2063,8 +2064,8 @@ def test_gemm_nt_vs_float64(dev, shape, with_bias):
         ref = ref + b.double()
     err = (y.double() - ref).abs()
     tol = 2.0 ** -8 * ref.abs() + 1e-2 * (K ** 0.5) * 2.0 ** -12 + 1e-6
-    bad = err > tol
-    assert not bool(bad.any()), (shape, int(bad.sum()), float(err.max()))
+    bad = ~(err <= tol)                      # NaN-strict, like close()
+    assert not bool(bad.any()), (shape, int(bad.sum()), f'{int((~torch.isfinite(y)).sum())} non-finite', float(err.nan_to_num(nan=float('inf')).max()))
     assert torch.equal(y, kernels.gemm_nt(x, w, b))
     # padding rows / columns of the last tiles must not leak: a sentinel-framed output buffer stays intact
     from gedepth_amd import hip

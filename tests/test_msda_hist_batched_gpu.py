@@ -115,17 +115,17 @@ def test_msda_hist_batched_records_vs_oracle(dev, case, level_mask, monkeypatch)
     raw_d, go_d = raw.to(dev), go.to(dev)
     raw_ref, _ = K._raw_ref(raw_d, ref.to(dev), NH, L, P)
     d_value = torch.zeros(B, Nv, NH, 64, device=dev)
-    real_empty, kept = torch.empty, []
+    real_empty, kept = K.torch.empty, []                               # the allocator the wrapper itself looks up (a guard harness may have replaced it)
 
     def keeping_empty(*a, **kw):
         t = real_empty(*a, **kw)
         if kw.get('dtype') is torch.uint8:
             kept.append(t)
         return t
-    monkeypatch.setattr(torch, 'empty', keeping_empty)
+    monkeypatch.setattr(K.torch, 'empty', keeping_empty)
     K._bwd_value_records(raw_d, raw_ref, go_d, d_value, lv, NH, L, P, level_mask)
     torch.cuda.synchronize()
-    monkeypatch.setattr(torch, 'empty', real_empty)
+    monkeypatch.setattr(K.torch, 'empty', real_empty)
     assert len(kept) == 1
     counted = int(kept[0][:nbins * 4].view(torch.int32).sum().item())   # MsdaWs.cnt is the first block of the workspace
     print(f'\n[msda hist {case} mask {level_mask:04b}] R {R} points per unit {per_unit} records {counted} (CPU {int(tiles.sum())})')
