@@ -562,18 +562,19 @@ __global__ void __launch_bounds__(256) adamw_k(float* __restrict__ p, const floa
                                                float* __restrict__ v, const uint8_t* __restrict__ wdm,
                                                const float* __restrict__ hyper, const double* __restrict__ gnorm_sq, long n,
                                                bf16_t* __restrict__ shadow) {
-  const float lr = hyper[0], b1 = hyper[1], b2 = hyper[2], eps = hyper[3], wd = hyper[4], bc1 = hyper[5], bc2 = hyper[6],
+  const float lr = hyper[0], b2 = hyper[2], eps = hyper[3], wd = hyper[4], bc1 = hyper[5], bc2 = hyper[6],
               max_norm = hyper[7], omb1 = hyper[8], omb2 = hyper[9];
   float clip = 1.f;
   if (max_norm > 0.f && gnorm_sq) {
     float total = (float)sqrt(gnorm_sq[0]);
     clip = fminf(max_norm / (total + 1e-6f), 1.f);   // torch.nn.utils.clip_grad_norm_
+    if (total != total) clip = total;                // fminf drops a NaN operand; torch's clamp propagates it: a NaN norm poisons every element
   }
   const float step = lr / bc1, rs2 = 1.f / sqrtf(bc2);
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
     float gi = g[i] * clip, pi = p[i], mi = m[i], vi = v[i];
     if (wdm[i]) pi *= 1.f - lr * wd;
-    mi = b1 * mi + omb1 * gi;
+    mi += omb1 * (gi - mi);                          // torch's lerp_: b1 * mi + omb1 * gi carries the rounding of b1 (0.9f + 0.1f != 1) into every step
     vi = b2 * vi + omb2 * gi * gi;
     float denom = sqrtf(vi) * rs2 + eps;
     pi -= step * (mi / denom);

@@ -241,7 +241,18 @@ class FusedAdamW(torch.optim.Optimizer):
     """AdamW (torch.optim.AdamW arithmetic) with clip_grad_norm_ folded in, one HIP launch per step.
 
     All groups must share lr / betas / eps; ``weight_decay`` may be the base value or 0 per group
-    (that is what ``paramwise_cfg.custom_keys`` with ``decay_mult=0`` produces)."""
+    (that is what ``paramwise_cfg.custom_keys`` with ``decay_mult=0`` produces).  Groups with unequal ``lr`` (``lr_mult``) are refused with
+    ``NotImplementedError``, at construction and again at any later step that finds them.
+
+    Non-finite gradients behave as under ``clip_grad_norm_`` + ``torch.optim.AdamW``: an ``inf`` element makes the clip factor 0 and poisons
+    its own element only; a NaN element makes the norm and the clip factor NaN and poisons every parameter.  ``last_grad_norm`` is
+    non-finite in both cases, which is how a runner detects such a step.
+
+    One deliberate difference from torch: a parameter whose ``.grad`` is ``None`` at the step is treated as having a ZERO gradient (its
+    arena slice is zeroed): it still takes weight decay and its moments decay, where torch skips it entirely.  The step is one launch over
+    the whole arena with one step counter, so there is no per-parameter "skip"; every trainable parameter of the GEDepth models receives a
+    gradient in every step (tests/test_optim_gpu.py checks that on the Swin-T models), so the difference shows only with frozen-by-omission
+    parameters, which belong under ``requires_grad=False`` here."""
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, max_grad_norm=0.0, bf16_shadow=True):
         defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
@@ -251,6 +262,7 @@ class FusedAdamW(torch.optim.Optimizer):
         if len(nz) > 1:
             raise NotImplementedError('FusedAdamW supports one non-zero weight decay (decay_mult in {0, 1})')
         self.base_wd = nz[0] if nz else 0.0
+        self._check_shared_lr()
         all_params = [p for g in self.param_groups for p in g['params'] if p.requires_grad]
         self.arena = GradArena(all_params)
         dev = self.arena.flat_param.device
@@ -274,6 +286,12 @@ class FusedAdamW(torch.optim.Optimizer):
             self.arena.refresh_shadow(copy=True)
         self.arena.on_permute(self._arena_permuted)
 
+    def _check_shared_lr(self):
+        lrs = {g['lr'] for g in self.param_groups}
+        if len(lrs) > 1:
+            raise NotImplementedError(f'FusedAdamW applies one learning rate to the whole arena; the parameter groups have {sorted(lrs)} '
+                                      '(lr_mult is not supported)')
+
     def _arena_permuted(self, remap):
         """The arena changed its slice order (FlatDDP: arrival order): the moments and the decay mask follow their parameters."""
         self.exp_avg, self.exp_avg_sq, self.wd_mask = remap(self.exp_avg), remap(self.exp_avg_sq), remap(self.wd_mask)
@@ -295,7 +313,7 @@ class FusedAdamW(torch.optim.Optimizer):
         clip norm) into the device buffer the kernels read.  Kept apart from ``launch`` so that a captured training step
         (gedepth_amd/mmrt/graph.py) holds only the kernels and the scalars are refreshed before every replay."""
         g0 = self.param_groups[0]
-        assert all(g['lr'] == g0['lr'] for g in self.param_groups), 'per-group learning rates are not supported'
+        self._check_shared_lr()
         self.step_count += 1
         b1, b2 = g0['betas']
         t = self.step_count

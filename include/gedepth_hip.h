@@ -614,6 +614,9 @@ int ge_silog_bwd(const float* pred, const float* gt, float eps, const float* coe
  *     {lr, beta1, beta2, eps, weight_decay, bias_corr1, bias_corr2, max_norm, 1-beta1, 1-beta2} (10 floats; the last two
  *     rounded from double on the host, as torch.optim does) so that the launch can
  *     be captured in a hipGraph and replayed while the host updates `hyper`.
+ *     No clipping when max_norm <= 0 or `gnorm_sq` is NULL (both entry points take NULL).  A NaN norm makes the clip factor NaN, as
+ *     torch's clamp does: every element is poisoned.  An infinite norm makes it 0 (inf * 0 = NaN for the infinite elements).
+ *     ge_sumsq takes any n >= 0 (n == 0: no launch) and a 16-byte aligned `x`; a misaligned `x` is refused (GE_ERR_BAD_ARG).
  */
 int ge_sumsq(const float* x, long n, double* out, void* stream);
 int ge_adamw_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, const uint8_t* wd_mask,
