@@ -8,7 +8,7 @@ MultiScaleFlipAug(RandomFlip, Normalize) -> ``aug_test`` — on the device, thro
   2. ``ge_infer_front`` (csrc/infer.hip) writes both flip views, normalised, into a static (2, 5, 352, 1216) buffer;
   3. ``model.encode_decode`` runs the two views as ONE batch-2 forward (clamped and rescaled, as ``inference`` does);
   4. ``ge_tta_merge`` forms (view 0 + mirror(view 1)) / 2 into a static (1, 352, 1216) output, in aug_test's order;
-  5. the output is copied to the host.
+  5. the output is copied to the host (``to_host=False``: it stays in the static device buffer, for ``single_gpu_test(device_eval=True)``).
 
 After two eager calls, steps 3-4 are captured in a hipGraph and replayed for every later frame.  KB crop makes the forward's shape
 constant, so frames of every KITTI size share one graph; only the front end's arguments change, and it stays outside the graph.
@@ -144,6 +144,7 @@ class DepthInferencer:
         self.static_out = torch.empty(1, s['height'], s['width'], device=self.device, dtype=torch.float32)
         self.stream = torch.cuda.Stream(self.device)
         self._pinned = None
+        self._uploaded = None                    # event after the last copy out of ``_pinned``
         self._pe = {}
         self.reset()
 
@@ -205,13 +206,21 @@ class DepthInferencer:
     def upload(self, bgr):
         """Host uint8 frame -> device, through a reused pinned buffer and a non-blocking copy on the current stream."""
         n = bgr.size
+        if self._uploaded is not None:
+            self._uploaded.synchronize()             # ``to_host=False`` lets the host run ahead: the last copy must have read the buffer
         if self._pinned is None or self._pinned.numel() < n:
             self._pinned = torch.empty(n, dtype=torch.uint8, pin_memory=True)
         host = self._pinned[:n].view(bgr.shape)
         host.numpy()[...] = bgr
-        return host.to(self.device, non_blocking=True)
+        dev = host.to(self.device, non_blocking=True)
+        self._uploaded = torch.cuda.Event()
+        self._uploaded.record()
+        return dev
 
-    def __call__(self, img, pe=None, calib=None, cam_height=1.65, graph=True):
+    def __call__(self, img, pe=None, calib=None, cam_height=1.65, graph=True, to_host=True):
+        """One frame -> its (1, 352, 1216) float32 map: a fresh host array, or with ``to_host=False`` the static device buffer
+        ``static_out`` itself, without synchronising: valid until the next call, and ordered on ``self.stream`` (the caller's current
+        stream waits for it, as always)."""
         bgr = _decode(img)
         H, W = bgr.shape[:2]
         s = self.spec
@@ -239,7 +248,8 @@ class DepthInferencer:
                 self._body(metas)
                 if graph:
                     self.calls[key] = self.calls.get(key, 0) + 1
-            out = self.static_out.cpu().numpy()                # synchronises the engine's stream; a fresh host array per frame
+            # to_host: synchronises the engine's stream; a fresh host array per frame
+            out = self.static_out.cpu().numpy() if to_host else self.static_out
         cur.wait_stream(self.stream)
         return out
 

@@ -1,6 +1,10 @@
 """Evaluation loops (depth/apis/test.py:32-232): run the model with ``return_loss=False`` over a data loader and either
 keep the predictions or reduce them to per-image metric tuples on the fly (``pre_eval``).  With ``show`` / ``out_dir`` each image's map
-also goes through the model's ``show_result`` (a colorized image, or the raw ``.npy`` under ``format_only``)."""
+also goes through the model's ``show_result`` (a colorized image, or the raw ``.npy`` under ``format_only``).
+
+``device_eval=True`` (opt-in, KITTI protocol only) evaluates where the prediction is: every frame goes through the graphed flip-TTA engine
+(apis/inference.py) and ``dataset.pre_eval_device`` reduces its map to ten float64 sums on the engine's stream (csrc/eval.hip); the whole
+split comes back in one copy at the end."""
 import os.path as osp
 
 import torch
@@ -41,12 +45,51 @@ def _show_batch(model, data, result_depth, show, out_dir, format_only):
         depther.show_result(name, [depth], show=show, out_file=out_file, format_only=format_only)
 
 
+def _device_eval(model, data_loader, pre_eval, format_only, show, out_dir):
+    """The ``device_eval`` loop of ``single_gpu_test``: the list of metric tuples ``pre_eval`` yields, in the sampler's order."""
+    from ..core.evaluation import metrics_from_sums
+    from .inference import DepthInferencer, _img_prefix, kitti_front_spec
+    dataset = data_loader.dataset
+    if not pre_eval or format_only:
+        raise NotImplementedError('device_eval reduces every map to metric sums on the device: it needs pre_eval=True and no format_only')
+    if show or out_dir:
+        raise NotImplementedError('device_eval with show / out_dir: the depth maps never reach the host')
+    if not hasattr(dataset, 'pre_eval_device'):
+        raise NotImplementedError(f'device_eval: {type(dataset).__name__} has no pre_eval_device (only the KITTI protocol is evaluated '
+                                  'on the device)')
+    depther = getattr(model, 'module', model)
+    cfg = getattr(depther, 'cfg', None)
+    if cfg is None:
+        raise NotImplementedError('device_eval: model.cfg is missing (the engine reads the test protocol from it): build the model with '
+                                  'init_depther or set model.cfg to its Config')
+    spec, prefix = kitti_front_spec(cfg), _img_prefix(cfg)               # NotImplementedError names what the device front end lacks
+    if (spec['height'], spec['width']) != (352, 1216):
+        raise NotImplementedError(f'device_eval: KBCrop {(spec["height"], spec["width"])}, the evaluation protocol crops (352, 1216)')
+    bf16 = bool(torch.is_autocast_enabled('cuda') and torch.get_autocast_dtype('cuda') == torch.bfloat16)      # what the caller asks for
+    engines = depther.__dict__.setdefault('_ge_inferencers', {})
+    if bf16 not in engines or engines[bf16].spec != spec or engines[bf16].prefix != prefix:
+        engines[bf16] = DepthInferencer(depther, bf16)
+    eng = engines[bf16]
+    indices = [i for batch in data_loader.batch_sampler for i in batch]
+    sums = torch.empty(max(len(indices), 1), 10, device=eng.device, dtype=torch.float64)
+    for row, i in enumerate(indices):
+        pred = eng(osp.join(dataset.img_dir, dataset.img_infos[i]['filename']), to_host=False)
+        with torch.cuda.stream(eng.stream):
+            dataset.pre_eval_device(pred, i, sums[row])
+    with torch.cuda.stream(eng.stream):
+        host = sums[:len(indices)].cpu().numpy()                       # the one copy (and the one synchronisation) of the loop
+    torch.cuda.current_stream(eng.device).wait_stream(eng.stream)
+    return [metrics_from_sums(r) for r in host]
+
+
 def single_gpu_test(model, data_loader, pre_eval=False, format_only=False, format_args=None, device=None, *, show=False,
-                    out_dir=None):
+                    out_dir=None, device_eval=False):
     """Returns a list with one entry per image: the metric tuple (``pre_eval``) or the ``(1, H, W)`` depth map.  ``show`` / ``out_dir``:
     ``show_result`` of every image's map, written to ``out_dir/replace_str(ori_filename)`` (``format_only``: the raw map as
-    ``out_dir/<ori_filename without extension>.npy``)."""
+    ``out_dir/<ori_filename without extension>.npy``).  ``device_eval`` (with ``pre_eval``, KITTI protocol): the module docstring."""
     model.eval()
+    if device_eval:
+        return _device_eval(model, data_loader, pre_eval, format_only, show, out_dir)
     dataset = data_loader.dataset
     device = device or next(model.parameters()).device
     results, idx = [], 0
@@ -66,10 +109,12 @@ def single_gpu_test(model, data_loader, pre_eval=False, format_only=False, forma
     return results
 
 
-def multi_gpu_test(model, data_loader, pre_eval=False, format_only=False, format_args=None, device=None, *, show=False, out_dir=None):
+def multi_gpu_test(model, data_loader, pre_eval=False, format_only=False, format_args=None, device=None, *, show=False, out_dir=None,
+                   device_eval=False):
     """Each rank evaluates its shard of a non-shuffled DistributedSampler; rank 0 receives the results in dataset order.  ``show`` /
-    ``out_dir`` as in ``single_gpu_test``: every rank writes the files of its own shard."""
-    part = single_gpu_test(model, data_loader, pre_eval, format_only, format_args, device, show=show, out_dir=out_dir)
+    ``out_dir`` / ``device_eval`` as in ``single_gpu_test``: every rank writes the files of its own shard."""
+    part = single_gpu_test(model, data_loader, pre_eval, format_only, format_args, device, show=show, out_dir=out_dir,
+                           device_eval=device_eval)
     rank, world = get_dist_info()
     if world == 1:
         return part

@@ -34,6 +34,21 @@ def eval_metrics(gt, pred, min_depth=1e-3, max_depth=80):
     return dict(zip(METRIC_NAMES, metrics(gt, pred, min_depth, max_depth)))
 
 
+def metrics_from_sums(sums):
+    """One image's ten float64 sums of ``kernels.depth_metric_sums`` (n, the three threshold counts, sum |d| / gt, sum d^2 / gt, sum d^2,
+    sum l, sum l^2, sum |log10 gt - log10 pred|; d = gt - pred, l = log pred - log gt) -> the tuple ``calculate`` returns."""
+    n, c1, c2, c3, s_abs, s_sq, s_d2, s_l, s_l2, s_l10 = (float(v) for v in sums)
+    if n == 0:
+        return (np.nan,) * 9
+    with np.errstate(invalid='ignore'):
+        mean_l2 = np.float64(s_l2) / n
+        rmse_log = np.sqrt(mean_l2)
+        silog = np.sqrt(mean_l2 - (np.float64(s_l) / n) ** 2) * 100
+    if np.isnan(silog):
+        silog = 0
+    return c1 / n, c2 / n, c3 / n, s_abs / n, np.sqrt(np.float64(s_d2) / n), s_l10 / n, rmse_log, silog, s_sq / n
+
+
 def pre_eval_to_metrics(pre_eval_results):
     cols = tuple(zip(*pre_eval_results))
     return OrderedDict((name, np.nanmean(cols[i])) for i, name in enumerate(METRIC_NAMES))

@@ -124,6 +124,46 @@ class KITTIDataset(Dataset):
             valid = np.logical_and(valid, crop)
         return valid[None]
 
+    def eval_rect(self, gh, gw):
+        """``(r0, r1, c0, c1)``: the rows / columns of a ``(gh, gw)`` crop that ``eval_mask`` keeps (its own ``int(...)`` expressions); the
+        whole crop when neither the Garg nor the Eigen crop is on."""
+        if self.garg_crop:
+            return int(0.40810811 * gh), int(0.99189189 * gh), int(0.03594771 * gw), int(0.96405229 * gw)
+        if self.eigen_crop:
+            return int(0.3324324 * gh), int(0.91351351 * gh), int(0.0359477 * gw), int(0.96405229 * gw)
+        return 0, gh, 0, gw
+
+    def pre_eval_device(self, pred, index, sums_row):
+        """``pre_eval`` of one image where the prediction already is: ``pred`` a CUDA ``(1, 352, 1216)`` float32 map, ``sums_row`` one row
+        of a device ``(N, 10)`` float64 buffer that receives the image's metric sums (``core.metrics_from_sums`` makes the tuple of
+        ``pre_eval`` from it).  The ground-truth PNG goes up undivided, as uint16, through a reused pinned buffer on the current stream;
+        the KB crop, the Garg / Eigen rectangle and the depth mask are applied by the kernel.  Does not synchronise: the row is valid once
+        the current stream has reached this point."""
+        import torch
+        from ... import kernels as K
+        if not (torch.is_tensor(pred) and pred.is_cuda and tuple(pred.shape) == (1, 352, 1216) and pred.dtype == torch.float32):
+            raise TypeError('pre_eval_device takes a CUDA (1, 352, 1216) float32 prediction, got '
+                            f'{tuple(pred.shape) if torch.is_tensor(pred) else type(pred)}')
+        path = osp.join(self.ann_dir, self.img_infos[index]['ann']['depth_map'])
+        raw = np.asarray(Image.open(path))
+        if raw.dtype != np.uint16 or raw.ndim != 2:
+            raise TypeError(f'{path}: the ground truth must be a 16-bit single-channel PNG, got {raw.dtype} {raw.shape}')
+        h, w = raw.shape
+        if h < 352 or w < 1216:
+            raise ValueError(f'{path}: ground truth {(h, w)} is smaller than the KB crop (352, 1216)')
+        state = self.__dict__.setdefault('_gt_upload', dict(pinned=None, done=None))
+        if state['done'] is not None:
+            state['done'].synchronize()                 # the copy that last read the pinned buffer (usually long finished)
+        if state['pinned'] is None or state['pinned'].numel() < raw.size:
+            state['pinned'] = torch.empty(raw.size, dtype=torch.uint16, pin_memory=True)
+        host = state['pinned'][:raw.size].view(h, w)
+        host.numpy()[...] = raw
+        dev = host.to(pred.device, non_blocking=True)
+        state['done'] = torch.cuda.Event()
+        state['done'].record()
+        top, left = int(h - 352), int((w - 1216) / 2)                   # eval_kb_crop
+        K.depth_metric_sums(pred, dev, top, left, self.eval_rect(352, 1216), self.depth_scale, self.min_depth, self.max_depth, sums_row)
+
     def pre_eval(self, preds, indices):
         """Per-image metric tuples for predictions ``(1, 352, 1216)`` (kitti.py:502-552)."""
         if not isinstance(indices, list):

@@ -2095,3 +2095,7 @@ def depth_colorize(value, vmin, vmax, lut):
     hip.call('ge_depth_colorize', hip.ptr(value, _f32, 'value'), value.numel(), lo, hi, den, flags, hip.ptr(ws, _f32, 'ws'),
              hip.ptr(_c(lut), torch.uint8, 'lut'), lut.shape[0] - 3, hip.ptr(out, torch.uint8, 'out'), hip.stream())
     return out
+
+
+# --------------------------------------------------------------------- evaluation metric sums (csrc/eval.hip, include/gedepth_eval.h)
+from .eval_kernels import depth_metric_sums  # noqa: E402,F401

@@ -11,6 +11,9 @@ Any of ``--out`` / ``--format-only`` / ``--show`` / ``--show-dir``, or ``--launc
 ``--show-dir DIR`` writes one colorized depth image per test image (``BaseDepther.show_result``), ``--format-only --show-dir DIR`` the
 raw maps as ``.npy``, ``--out FILE.pkl`` pickles the results list (metric tuples with ``--eval``, else the maps) on rank 0, and
 ``--launcher pytorch`` (tools/dist_test.sh) evaluates one shard per rank with ``multi_gpu_test``.
+
+``--device-eval`` (with ``--eval`` and ``--synthetic 0``, KITTI protocol) evaluates on the device: frames go through the graphed flip-TTA
+engine and each map is reduced to its metric sums by a HIP kernel, so no map is copied to the host (``single_gpu_test(device_eval=True)``).
 """
 import argparse
 import os
@@ -39,6 +42,8 @@ def parse_args(argv=None):
     p.add_argument('--synthetic', type=int, default=2, help='N synthetic inputs; 0 = evaluate cfg.data.test')
     p.add_argument('--flip-tta', action='store_true')
     p.add_argument('--bf16', action='store_true', help='bf16 autocast inference')
+    p.add_argument('--device-eval', action='store_true',
+                   help='with --eval and --synthetic 0: the graphed inference engine and the metric-sum kernel instead of the host loop')
     p.add_argument('--out', help='output result file in pickle format (.pkl / .pickle), written by rank 0')
     p.add_argument('--format-only', action='store_true',
                    help='format the results (dataset.format_results) without evaluating; with --show-dir the raw maps are saved as .npy')
@@ -55,6 +60,8 @@ def parse_args(argv=None):
         os.environ['LOCAL_RANK'] = str(args.local_rank)
     if args.eval and args.format_only:
         raise ValueError('--eval and --format-only cannot be both specified')
+    if args.device_eval and (not args.eval or args.synthetic != 0 or args.show or args.show_dir):
+        raise ValueError('--device-eval needs --eval and --synthetic 0, and cannot be combined with --show / --show-dir')
     if args.out is not None and not args.out.endswith(('.pkl', '.pickle')):
         raise ValueError('The output file must be a pkl file.')
     return args
@@ -80,10 +87,11 @@ def run_dataset(args, cfg):
     if args.checkpoint:
         load_checkpoint(model, args.checkpoint, map_location='cpu')
     model = model.cuda().eval()
+    model.cfg = cfg
     test = multi_gpu_test if distributed else single_gpu_test
     with torch.autocast('cuda', dtype=torch.bfloat16, enabled=args.bf16):
         results = test(model, loader, pre_eval=args.eval is not None, format_only=args.format_only, format_args=eval_kwargs,
-                       show=args.show, out_dir=args.show_dir)
+                       show=args.show, out_dir=args.show_dir, device_eval=args.device_eval)
     rank, _ = get_dist_info()
     if rank == 0:
         if args.out:
@@ -116,8 +124,9 @@ def main():
         from gedepth_amd.depth.datasets import build_dataloader, build_dataset
         dataset = build_dataset(cfg.data.test, dict(test_mode=True))
         loader = build_dataloader(dataset, 1, cfg.data.workers_per_gpu, dist=False, shuffle=False)
+        model.cfg = cfg
         with torch.autocast('cuda', dtype=torch.bfloat16, enabled=args.bf16):
-            results = single_gpu_test(model, loader, pre_eval=True)
+            results = single_gpu_test(model, loader, pre_eval=True, device_eval=args.device_eval)
         dataset.evaluate(results)
         return
     res = []
