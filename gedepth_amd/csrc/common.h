@@ -15,11 +15,28 @@
 typedef uint16_t bf16_t;  // raw bfloat16 bits
 
 __device__ __forceinline__ float bf2f(bf16_t h) { return __uint_as_float(((uint32_t)h) << 16); }
-__device__ __forceinline__ bf16_t f2bf(float f) {  // round-to-nearest-even, like torch
+// Short vectors: MFMA operand / accumulator fragments, packed bf16 pairs (v_dot2c_f32_bf16, v_cvt_pk_bf16_f32), raw 16-byte moves
+typedef __bf16 ge_bf16x8 __attribute__((ext_vector_type(8)));
+typedef __bf16 ge_bf16x4 __attribute__((ext_vector_type(4)));
+typedef __bf16 ge_bf16x2 __attribute__((ext_vector_type(2)));
+typedef float ge_f32x16 __attribute__((ext_vector_type(16)));
+typedef unsigned int ge_u32x4 __attribute__((ext_vector_type(4)));
+typedef short ge_s16x2 __attribute__((ext_vector_type(2)));
+#define GE_LDS(T, p) ((__attribute__((address_space(3))) T*)(p))   // generic -> LDS pointer, for the builtins that take address space 3
+
+// fp32 -> bf16, round-to-nearest-even like torch, NaN stays NaN.  f2bf_hw / ge_pack_bf16x2 are ALWAYS gfx950's conversion unit
+// (v_cvt_pk_bf16_f32): the MFMA kernels round their operand tiles with these whatever the build says.
+__device__ __forceinline__ bf16_t f2bf_hw(float f) { return __builtin_bit_cast(bf16_t, (__bf16)f); }
+__device__ __forceinline__ uint32_t ge_pack_bf16x2(float lo, float hi) {   // lo in bits 0-15, hi in bits 16-31
+  ge_bf16x2 v = {(__bf16)lo, (__bf16)hi};
+  return __builtin_bit_cast(uint32_t, v);
+}
+// f2bf is the storage rounding of the streaming kernels (Io, Vec): the conversion unit too, unless the build defines GE_SW_BF16 (A/B switch)
+__device__ __forceinline__ bf16_t f2bf(float f) {
 #ifndef GE_SW_BF16
-  // gfx950's conversion unit (v_cvt_pk_bf16_f32): same rounding, NaN stays NaN.  The integer sequence below costs ~6 VALU per value — 48 per 16-byte
-  // store of the streaming kernels: step 47.47 -> 47.12 ms same-session, conv1x1_bn_act_k 505 -> 391 us (round 5); -DGE_SW_BF16 restores it (A/B)
-  return __builtin_bit_cast(bf16_t, (__bf16)f);
+  // The integer sequence below costs ~6 VALU per value — 48 per 16-byte store of the streaming kernels: step 47.47 -> 47.12 ms same-session,
+  // conv1x1_bn_act_k 505 -> 391 us (round 5); -DGE_SW_BF16 restores it (A/B)
+  return f2bf_hw(f);
 #endif
   uint32_t u = __float_as_uint(f);
   if ((u & 0x7fffffffu) > 0x7f800000u) return (bf16_t)((u >> 16) | 0x40u);
@@ -39,10 +56,31 @@ template <> struct Io<bf16_t> {
   static __device__ __forceinline__ float rt(float v) { return bf2f(f2bf(v)); }
 };
 
-// 16-byte vectors of the storage type, widened to fp32 registers (8 bf16 or 4 f32 per lane and instruction)
-template <typename T> struct V8;
-template <> struct V8<bf16_t> {
-  static constexpr int N = 8;
+// N consecutive elements of the storage type <-> N fp32 registers, one memory instruction per 16 bytes (N = 4 or 8)
+// (st rounds with f2bf, not ge_pack_bf16x2: these stores are what GE_SW_BF16 switches)
+template <typename T, int N> struct Vec;
+template <> struct Vec<float, 4> {
+  static __device__ __forceinline__ void ld(const float* p, float v[4]) { const float4 t = *(const float4*)p; v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w; }
+  static __device__ __forceinline__ void st(float* p, const float v[4]) { *(float4*)p = make_float4(v[0], v[1], v[2], v[3]); }
+};
+template <> struct Vec<float, 8> {
+  static __device__ __forceinline__ void ld(const float* p, float v[8]) { Vec<float, 4>::ld(p, v); Vec<float, 4>::ld(p + 4, v + 4); }
+  static __device__ __forceinline__ void st(float* p, const float v[8]) { Vec<float, 4>::st(p, v); Vec<float, 4>::st(p + 4, v + 4); }
+};
+template <> struct Vec<bf16_t, 4> {
+  static __device__ __forceinline__ void ld(const bf16_t* p, float v[4]) {
+    const uint2 t = *(const uint2*)p;
+    v[0] = __uint_as_float(t.x << 16); v[1] = __uint_as_float(t.x & 0xffff0000u);
+    v[2] = __uint_as_float(t.y << 16); v[3] = __uint_as_float(t.y & 0xffff0000u);
+  }
+  static __device__ __forceinline__ void st(bf16_t* p, const float v[4]) {
+    uint2 t;
+    t.x = (uint32_t)f2bf(v[0]) | ((uint32_t)f2bf(v[1]) << 16);
+    t.y = (uint32_t)f2bf(v[2]) | ((uint32_t)f2bf(v[3]) << 16);
+    *(uint2*)p = t;
+  }
+};
+template <> struct Vec<bf16_t, 8> {
   static __device__ __forceinline__ void ld(const bf16_t* p, float v[8]) {
     const uint4 t = *(const uint4*)p; const uint32_t w[4] = {t.x, t.y, t.z, t.w};
 #pragma unroll
@@ -55,11 +93,28 @@ template <> struct V8<bf16_t> {
     *(uint4*)p = t;
   }
 };
-template <> struct V8<float> {
-  static constexpr int N = 4;
-  static __device__ __forceinline__ void ld(const float* p, float v[4]) { const float4 t = *(const float4*)p; v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w; }
-  static __device__ __forceinline__ void st(float* p, const float v[4]) { *(float4*)p = make_float4(v[0], v[1], v[2], v[3]); }
-};
+// the 16-byte member: 8 bf16 or 4 f32 per lane and instruction
+template <typename T> struct V8 : Vec<T, 16 / sizeof(T)> { static constexpr int N = 16 / sizeof(T); };
+
+// Xor-shuffle (butterfly) reduction over aligned groups of GS lanes of the wave: every lane ends up with the group's result
+template <int GS, typename V, typename Op>
+__device__ __forceinline__ V ge_group_reduce(V v, Op op) {
+#pragma unroll
+  for (int o = GS / 2; o > 0; o >>= 1) v = op(v, __shfl_xor(v, o, 64));
+  return v;
+}
+template <int GS, typename V> __device__ __forceinline__ V ge_group_sum(V v) { return ge_group_reduce<GS>(v, [](V a, V b) { return a + b; }); }
+template <typename V> __device__ __forceinline__ V ge_wave_sum(V v) { return ge_group_sum<GE_WAVE>(v); }
+template <typename V> __device__ __forceinline__ V ge_wave_min(V v) { return ge_group_reduce<GE_WAVE>(v, [](V a, V b) { return min(a, b); }); }
+template <typename V> __device__ __forceinline__ V ge_wave_max(V v) { return ge_group_reduce<GE_WAVE>(v, [](V a, V b) { return max(a, b); }); }
+
+// n / d, correctly rounded, for a bf16-valued n and an integer-valued d <= 8191, given r = RN(1 / d): one Newton step on q0 = n * r
+// (tools/ubench/divcheck.c checks every such pair against IEEE division).  The deformable-attention kernels form sampling locations with
+// it, so that every kernel of a step lands each tap in the same cell as the forward, to the bit.
+__device__ __forceinline__ float ge_div_rn(float n, float d, float r) {
+  const float q0 = n * r;
+  return __builtin_fmaf(__builtin_fmaf(-q0, d, n), r, q0);
+}
 
 // F.interpolate(mode='bilinear') source-index rule (scale from sizes, not from scale_factor).
 struct Lerp { int i0, i1; float w0, w1; };
@@ -76,6 +131,23 @@ __device__ __forceinline__ Lerp ge_lerp(int dst, int in, float scale, bool align
   r.w1 = src - (float)r.i0;
   r.w0 = 1.f - r.w1;
   return r;
+}
+
+// Bilinear backward as a gather: [lo, hi] = the output indices whose taps can touch input index X, i.e. src(o) in (X - 1, X + 1), clipped to
+// [0, out - 1].  floor / ceil of the interval's ends already leave one spare candidate per side against the rounding of the division, and the
+// kernels recompute each candidate's weights exactly, so a spare one contributes 0.  MARGIN widens the range by that many further candidates
+// per side: the generic NCHW / NHWC kernels have always run with 1, the decoder's up-sample-and-concat with 0 (5 instead of 7 candidates at
+// factor 2).  Nothing in the code shows a case that needs the second spare; the difference is preserved, not explained.
+template <int MARGIN>
+__device__ __forceinline__ void ge_cand_range(int X, int out, float scale, bool align, int& lo, int& hi) {
+  if (scale <= 0.f) { lo = 0; hi = out - 1; return; }
+  float a, b;
+  if (align) { a = ((float)X - 1.f) / scale; b = ((float)X + 1.f) / scale; }
+  else { a = ((float)X - 0.5f) / scale - 0.5f; b = ((float)X + 1.5f) / scale - 0.5f; }
+  lo = (int)floorf(a) - MARGIN;
+  hi = (int)ceilf(b) + MARGIN;
+  if (lo < 0) lo = 0;
+  if (hi > out - 1) hi = out - 1;
 }
 
 static inline hipStream_t ge_stream(void* s) { return (hipStream_t)s; }

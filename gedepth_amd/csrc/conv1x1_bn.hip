@@ -21,21 +21,10 @@
 // fp32 parity mode keeps the two-pass kernels (csrc/nhwc.hip).
 #include "common.h"
 
-typedef __bf16 cb_bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 cb_bf16x4 __attribute__((ext_vector_type(4)));
-typedef float cb_f32x16 __attribute__((ext_vector_type(16)));
-#define CB_LDS(T, p) ((__attribute__((address_space(3))) T*)(p))
-
 #define CB_K 64                         // input channels
 #define CB_LD 72                        // LDS row stride (bf16) of a staged [token][64] tile: 144 B, 8-byte aligned pieces for the transposing reads
 #define CB_GRAM (65 * CB_K)             // 64 x 64 sums of products + 64 column sums
 #define CB_GRAM_WG 256                  // partial Gram matrices (one per workgroup)
-
-// fp32 -> bf16 on the conversion unit (v_cvt_pk_bf16_f32, round to nearest even): the software rounding of common.h costs ~6 VALU per value,
-// a third of this file's forward kernel
-typedef __bf16 cb_bf16x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ bf16_t cb_bf(float f) { return __builtin_bit_cast(bf16_t, (__bf16)f); }
-__device__ __forceinline__ uint32_t cb_pk(float lo, float hi) { return __builtin_bit_cast(uint32_t, (cb_bf16x2){(__bf16)lo, (__bf16)hi}); }
 
 __device__ __forceinline__ int cb_row(int r, int hi) { return (r & 3) + 8 * (r >> 2) + 4 * hi; }      // C/D layout of v_mfma_f32_32x32x16: row of register r
 
@@ -45,10 +34,10 @@ __global__ void __launch_bounds__(256) conv1x1_gram_k(const bf16_t* __restrict__
   __shared__ float red[CB_GRAM];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, hi = lane >> 5;
   bf16_t* stage = stage_all[wv];
-  cb_f32x16 acc[2][2], sum[2];
+  ge_f32x16 acc[2][2], sum[2];
 #pragma unroll
   for (int i = 0; i < 16; ++i) { acc[0][0][i] = 0.f; acc[0][1][i] = 0.f; acc[1][0][i] = 0.f; acc[1][1][i] = 0.f; sum[0][i] = 0.f; sum[1][i] = 0.f; }
-  const cb_bf16x8 ones = {(__bf16)1.f, (__bf16)1.f, (__bf16)1.f, (__bf16)1.f, (__bf16)1.f, (__bf16)1.f, (__bf16)1.f, (__bf16)1.f};
+  const ge_bf16x8 ones = {(__bf16)1.f, (__bf16)1.f, (__bf16)1.f, (__bf16)1.f, (__bf16)1.f, (__bf16)1.f, (__bf16)1.f, (__bf16)1.f};
   // transposing read: lane (n = lane & 31, kg = lane >> 5) ends up with rows 8 kg .. 8 kg + 7 of column n of a [16 rows][32 columns] block
   const int tr_row = hi * 8 + ((lane & 15) >> 2), tr_col = ((lane >> 4) & 1) * 16 + (lane & 3) * 4;
   const long nblk = (rows + 63) / 64;
@@ -69,12 +58,12 @@ __global__ void __launch_bounds__(256) conv1x1_gram_k(const bf16_t* __restrict__
     __builtin_amdgcn_wave_barrier();
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) {
-      cb_bf16x8 F[2];
+      ge_bf16x8 F[2];
 #pragma unroll
       for (int cb = 0; cb < 2; ++cb) {
         const bf16_t* p = stage + (ks * 16 + tr_row) * CB_LD + cb * 32 + tr_col;
-        const cb_bf16x4 t0 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(CB_LDS(cb_bf16x4, p));
-        const cb_bf16x4 t1 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(CB_LDS(cb_bf16x4, p + 4 * CB_LD));
+        const ge_bf16x4 t0 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(GE_LDS(ge_bf16x4, p));
+        const ge_bf16x4 t1 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(GE_LDS(ge_bf16x4, p + 4 * CB_LD));
         F[cb] = __builtin_shufflevector(t0, t1, 0, 1, 2, 3, 4, 5, 6, 7);
       }
 #pragma unroll
@@ -126,11 +115,6 @@ __global__ void __launch_bounds__(256) conv1x1_partials_reduce_k(const float* __
 }
 
 // t_i = sum_j S[i][j] w[j] for lane i (S in LDS, stride 65 doubles; w in LDS), wave-wide helpers
-__device__ __forceinline__ double cb_wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 __device__ __forceinline__ void cb_load_gram(const double* __restrict__ gram, double* Ss, double* ss) {
   for (int i = threadIdx.x; i < CB_K * CB_K; i += blockDim.x) Ss[(i >> 6) * 65 + (i & 63)] = gram[i];
   for (int i = threadIdx.x; i < CB_K; i += blockDim.x) ss[i] = gram[CB_K * CB_K + i];
@@ -154,8 +138,8 @@ __global__ void __launch_bounds__(256) conv1x1_bn_finalize_k(const double* __res
   double t = 0.0;
 #pragma unroll 8
   for (int j = 0; j < CB_K; ++j) t += Ss[lane * 65 + j] * ws[wv][j];
-  const double mean = cb_wave_sum(wi * ss[lane]) / n;
-  const double ez2 = cb_wave_sum(wi * t) / n;
+  const double mean = ge_wave_sum(wi * ss[lane]) / n;
+  const double ez2 = ge_wave_sum(wi * t) / n;
   if (c >= Cout || lane != 0) return;
   double var = ez2 - mean * mean;
   if (var < 0.0) var = 0.0;
@@ -175,9 +159,8 @@ __global__ void __launch_bounds__(256) conv1x1_bn_finalize_k(const double* __res
 #ifndef CB_EPI_GROUP
 #define CB_EPI_GROUP 4
 #endif
-typedef unsigned cb_u32x4 __attribute__((ext_vector_type(4)));
 #ifdef CB_NT_STORE
-#define CB_STORE16(P_, V_) { const uint4 v__ = (V_); __builtin_nontemporal_store((cb_u32x4){v__.x, v__.y, v__.z, v__.w}, (cb_u32x4*)(P_)); }
+#define CB_STORE16(P_, V_) { const uint4 v__ = (V_); __builtin_nontemporal_store((ge_u32x4){v__.x, v__.y, v__.z, v__.w}, (ge_u32x4*)(P_)); }
 #else
 #define CB_STORE16(P_, V_) *(uint4*)(P_) = (V_)
 #endif
@@ -192,12 +175,12 @@ __global__ void __launch_bounds__(256) conv1x1_bn_act_k(const bf16_t* __restrict
   if (cg * 128 >= Cout) return;                                       // waves are independent: no workgroup barrier below
   bf16_t* ytile = ytile_all[wv];
   const int c0 = cg * 128;
-  cb_bf16x8 Wf[4][4];                                                  // [channel block][K step]: B operand, lane (channel n, k group hi)
+  ge_bf16x8 Wf[4][4];                                                  // [channel block][K step]: B operand, lane (channel n, k group hi)
   float ca[4], cbv[4];
 #pragma unroll
   for (int jb = 0; jb < 4; ++jb) {
 #pragma unroll
-    for (int s = 0; s < 4; ++s) Wf[jb][s] = *(const cb_bf16x8*)(w + (long)(c0 + jb * 32 + n) * CB_K + s * 16 + hi * 8);
+    for (int s = 0; s < 4; ++s) Wf[jb][s] = *(const ge_bf16x8*)(w + (long)(c0 + jb * 32 + n) * CB_K + s * 16 + hi * 8);
     ca[jb] = coef[c0 + jb * 32 + n];
     cbv[jb] = coef[Cout + c0 + jb * 32 + n];
   }
@@ -205,7 +188,7 @@ __global__ void __launch_bounds__(256) conv1x1_bn_act_k(const bf16_t* __restrict
   const long npt = (HW + 31) / 32;                                    // position tiles
   const long npx = npt > xcd ? (npt - xcd + 7) / 8 : 0;               // ... of this XCD
   const long nq = npx * B;
-  cb_bf16x8 A[4];
+  ge_bf16x8 A[4];
   // the rows of tile t (clamped: rows past the end are computed and not stored); the loads of tile t + wgx are issued right after the MFMAs of tile t
 #define CB_LOAD_A(T_)                                                                           \
   {                                                                                             \
@@ -213,14 +196,14 @@ __global__ void __launch_bounds__(256) conv1x1_bn_act_k(const bf16_t* __restrict
     const int b_ = (int)((T_) - pl_ * B);                                                       \
     const long p_ = (pl_ * 8 + xcd) * 32 + n;                                                   \
     const bf16_t* xr = x + ((long)b_ * HW + (p_ < HW ? p_ : HW - 1)) * CB_K + hi * 8;           \
-    _Pragma("unroll") for (int s = 0; s < 4; ++s) A[s] = *(const cb_bf16x8*)(xr + s * 16);      \
+    _Pragma("unroll") for (int s = 0; s < 4; ++s) A[s] = *(const ge_bf16x8*)(xr + s * 16);      \
   }
   if (j0 < nq) CB_LOAD_A((long)j0)
   for (long t = j0; t < nq; t += wgx) {
     const long pl = t / B;
     const int b = (int)(t - pl * B);
     const long p0 = (pl * 8 + xcd) * 32;                              // first position of the tile
-    cb_f32x16 acc[4];
+    ge_f32x16 acc[4];
 #pragma unroll
     for (int jb = 0; jb < 4; ++jb) {
 #pragma unroll
@@ -235,7 +218,7 @@ __global__ void __launch_bounds__(256) conv1x1_bn_act_k(const bf16_t* __restrict
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const float z = __fmaf_rn(acc[jb][r], ca[jb], cbv[jb]);
-        ytile[cb_row(r, hi) * CB_YLD + jb * 32 + n] = cb_bf(z > 0.f ? z : z * slope);
+        ytile[cb_row(r, hi) * CB_YLD + jb * 32 + n] = f2bf_hw(z > 0.f ? z : z * slope);
       }
     __builtin_amdgcn_wave_barrier();
     // rows back out of LDS as 16-byte pieces (16 lanes = one token's 256 bytes); CB_EPI_GROUP pieces per lane are handled together so that
@@ -270,7 +253,7 @@ __global__ void __launch_bounds__(256) conv1x1_bn_act_k(const bf16_t* __restrict
 #pragma unroll
           for (int k = 0; k < 4; ++k) {
             const float lo = __uint_as_float(u[k] << 16) + e[2 * k], hi2 = __uint_as_float(u[k] & 0xffff0000u) + e[2 * k + 1];
-            o[k] = cb_pk(lo, hi2);
+            o[k] = ge_pack_bf16x2(lo, hi2);
           }
           if (p0 + tok < HW) CB_STORE16(q + ((long)b * HW + p0 + tok) * Cout + c0 + piece * 8, make_uint4(o[0], o[1], o[2], o[3]));
         }
@@ -365,7 +348,7 @@ __global__ void __launch_bounds__(256) conv1x1_bn_bwd_finalize_k(const float* __
   for (int j = 0; j < CB_K; ++j) t += Ss[lane * 65 + j] * ws[wv][j];
   const double mean = (double)save_mean[c], rstd = (double)save_rstd[c], a = (double)gamma[c] * rstd;
   const double m1 = (double)m1s[c], Gi = (double)GT[(long)c * CB_K + lane], si = ss[lane];
-  const double dg = rstd * cb_wave_sum(wi * (Gi - m1 * si / n));
+  const double dg = rstd * ge_wave_sum(wi * (Gi - m1 * si / n));
   const double m1n = m1 / n, m2n = dg / n;
   const double ui = rstd * (t - si * mean);
   dW[(long)c * CB_K + lane] = (float)(a * (Gi - si * m1n - ui * m2n));
@@ -420,12 +403,12 @@ __global__ void __launch_bounds__(256) conv1x1_bn_dgrad_k(const bf16_t* __restri
   const bf16_t* wa = wl + n * LD + hi * 8;                                                // + mt * 32 * LD + k * 16
   const long ntile = (rows + 31) / 32, tstep = (long)gridDim.x * 4;
   const int nch = Cout / 128;                                                             // chunks of 8 K-steps over g
-  cb_bf16x8 Fa[8], Fb[8], Fx[4];
+  ge_bf16x8 Fa[8], Fb[8], Fx[4];
 #define CB_ROWPTR(T_) (((T_) * 32 + n < rows) ? (T_) * 32 + n : rows - 1)
-#define CB_LOADG(F_, T_, C_) { const bf16_t* gr_ = g + CB_ROWPTR(T_) * Cout + (C_) * 128 + hi * 8; _Pragma("unroll") for (int s_ = 0; s_ < 8; ++s_) F_[s_] = *(const cb_bf16x8*)(gr_ + s_ * 16); }
+#define CB_LOADG(F_, T_, C_) { const bf16_t* gr_ = g + CB_ROWPTR(T_) * Cout + (C_) * 128 + hi * 8; _Pragma("unroll") for (int s_ = 0; s_ < 8; ++s_) F_[s_] = *(const ge_bf16x8*)(gr_ + s_ * 16); }
 #define CB_MMA(F_, C_)                                                                                                         \
   _Pragma("unroll") for (int s_ = 0; s_ < 8; ++s_) {                                                                           \
-    const cb_bf16x8 w0_ = *(const cb_bf16x8*)(wa + ((C_) * 8 + s_) * 16), w1_ = *(const cb_bf16x8*)(wa + 32 * LD + ((C_) * 8 + s_) * 16); \
+    const ge_bf16x8 w0_ = *(const ge_bf16x8*)(wa + ((C_) * 8 + s_) * 16), w1_ = *(const ge_bf16x8*)(wa + 32 * LD + ((C_) * 8 + s_) * 16); \
     acc0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w0_, F_[s_], acc0, 0, 0, 0);                                                 \
     acc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w1_, F_[s_], acc1, 0, 0, 0);                                                 \
   }
@@ -435,9 +418,9 @@ __global__ void __launch_bounds__(256) conv1x1_bn_dgrad_k(const bf16_t* __restri
     {
       const bf16_t* xr = x + CB_ROWPTR(tile) * CB_K + hi * 8;
 #pragma unroll
-      for (int s = 0; s < 4; ++s) Fx[s] = *(const cb_bf16x8*)(xr + s * 16);
+      for (int s = 0; s < 4; ++s) Fx[s] = *(const ge_bf16x8*)(xr + s * 16);
     }
-    cb_f32x16 acc0, acc1;
+    ge_f32x16 acc0, acc1;
 #pragma unroll
     for (int i = 0; i < 16; ++i) { acc0[i] = 0.f; acc1[i] = 0.f; }
     for (int c = 0; c < nch; c += 2) {
@@ -449,7 +432,7 @@ __global__ void __launch_bounds__(256) conv1x1_bn_dgrad_k(const bf16_t* __restri
     }
 #pragma unroll
     for (int s = 0; s < 4; ++s) {
-      const cb_bf16x8 w0 = *(const cb_bf16x8*)(wa + Cout + s * 16), w1 = *(const cb_bf16x8*)(wa + 32 * LD + Cout + s * 16);
+      const ge_bf16x8 w0 = *(const ge_bf16x8*)(wa + Cout + s * 16), w1 = *(const ge_bf16x8*)(wa + 32 * LD + Cout + s * 16);
       acc0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w0, Fx[s], acc0, 0, 0, 0);
       acc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w1, Fx[s], acc1, 0, 0, 0);
     }
@@ -459,10 +442,10 @@ __global__ void __launch_bounds__(256) conv1x1_bn_dgrad_k(const bf16_t* __restri
 #pragma unroll
       for (int r4 = 0; r4 < 4; ++r4) {
         uint2 v0, v1;
-        v0.x = cb_pk(acc0[4 * r4] + c0r[0][4 * r4], acc0[4 * r4 + 1] + c0r[0][4 * r4 + 1]);
-        v0.y = cb_pk(acc0[4 * r4 + 2] + c0r[0][4 * r4 + 2], acc0[4 * r4 + 3] + c0r[0][4 * r4 + 3]);
-        v1.x = cb_pk(acc1[4 * r4] + c0r[1][4 * r4], acc1[4 * r4 + 1] + c0r[1][4 * r4 + 1]);
-        v1.y = cb_pk(acc1[4 * r4 + 2] + c0r[1][4 * r4 + 2], acc1[4 * r4 + 3] + c0r[1][4 * r4 + 3]);
+        v0.x = ge_pack_bf16x2(acc0[4 * r4] + c0r[0][4 * r4], acc0[4 * r4 + 1] + c0r[0][4 * r4 + 1]);
+        v0.y = ge_pack_bf16x2(acc0[4 * r4 + 2] + c0r[0][4 * r4 + 2], acc0[4 * r4 + 3] + c0r[0][4 * r4 + 3]);
+        v1.x = ge_pack_bf16x2(acc1[4 * r4] + c0r[1][4 * r4], acc1[4 * r4 + 1] + c0r[1][4 * r4 + 1]);
+        v1.y = ge_pack_bf16x2(acc1[4 * r4 + 2] + c0r[1][4 * r4 + 2], acc1[4 * r4 + 3] + c0r[1][4 * r4 + 3]);
         *(uint2*)(o + 8 * r4) = v0;
         *(uint2*)(o + 32 + 8 * r4) = v1;
       }
@@ -535,11 +518,9 @@ extern "C" int ge_conv1x1_bn_bwd_mask(const void* dy1, long ld1, const void* dy2
   const int lpr = C / 8;
   if (lpr > 256) return GE_ERR_UNSUPPORTED;
   const int rpi = 256 / lpr;
-  long nb = (rows + (long)rpi * 8 - 1) / ((long)rpi * 8);
-  if (nb < 1) nb = 1;
-  if (nb > 1024) nb = 1024;
+  const unsigned nb = ge_blocks(rows, rpi * 8, 1024);
   float* part = (float*)workspace;
-#define CB_MASK(A_, B_) conv1x1_bn_mask_k<A_, B_><<<(unsigned)nb, 256, 0, s>>>((const bf16_t*)dy1, ld1, (const bf16_t*)dy2, ld2, (const bf16_t*)y, (bf16_t*)g, part, C, rows, lpr, rpi, slope)
+#define CB_MASK(A_, B_) conv1x1_bn_mask_k<A_, B_><<<nb, 256, 0, s>>>((const bf16_t*)dy1, ld1, (const bf16_t*)dy2, ld2, (const bf16_t*)y, (bf16_t*)g, part, C, rows, lpr, rpi, slope)
   if (dy1 && dy2) CB_MASK(true, true);
   else if (dy1) CB_MASK(true, false);
   else CB_MASK(false, true);

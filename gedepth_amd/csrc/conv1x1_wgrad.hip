@@ -16,11 +16,6 @@
 #include "common.h"
 #include <algorithm>
 
-typedef __bf16 c1_bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 c1_bf16x4 __attribute__((ext_vector_type(4)));
-typedef float c1_f32x16 __attribute__((ext_vector_type(16)));
-#define C1_LDS(T, p) ((__attribute__((address_space(3))) T*)(p))
-
 #define C1_ROWS 64                    // rows per stage = 4 K steps of 16
 #define C1_MAX_CB 16                  // 32-channel blocks of dY per workgroup (512 output channels)
 #define C1_MAX_IB 3                   // 32-channel blocks of X per workgroup (96 input channels)
@@ -66,7 +61,7 @@ __global__ void __launch_bounds__(512, 1) conv1x1_wgrad_k(const bf16_t* __restri
     a_off[j] = cb * C1_ROWS * 32 + tr_off;
     b_off[j] = ib * C1_ROWS * 32 + tr_off;
   }
-  c1_f32x16 acc[C1_TPW];
+  ge_f32x16 acc[C1_TPW];
 #pragma unroll
   for (int j = 0; j < C1_TPW; ++j) acc[j] = 0.f;
 
@@ -88,8 +83,8 @@ __global__ void __launch_bounds__(512, 1) conv1x1_wgrad_k(const bf16_t* __restri
 #define C1_PARK()                                                                                           \
   _Pragma("unroll") for (int i = 0; i < C1_DY_PIECES; ++i) { if (dy_row[i] >= 0) *(uint4*)(dy_t + dy_lds[i]) = pd[i]; }   \
   _Pragma("unroll") for (int i = 0; i < C1_X_PIECES; ++i) { if (x_row[i] >= 0) *(uint4*)(x_t + x_lds[i]) = px[i]; }
-#define C1_RD(P) __builtin_shufflevector(__builtin_amdgcn_ds_read_tr16_b64_v4bf16(C1_LDS(c1_bf16x4, (P))), \
-                                         __builtin_amdgcn_ds_read_tr16_b64_v4bf16(C1_LDS(c1_bf16x4, (P) + 4 * 32)), 0, 1, 2, 3, 4, 5, 6, 7)
+#define C1_RD(P) __builtin_shufflevector(__builtin_amdgcn_ds_read_tr16_b64_v4bf16(GE_LDS(ge_bf16x4, (P))), \
+                                         __builtin_amdgcn_ds_read_tr16_b64_v4bf16(GE_LDS(ge_bf16x4, (P) + 4 * 32)), 0, 1, 2, 3, 4, 5, 6, 7)
   long s = blockIdx.z;
   if (s < nstage) {
     C1_PREFETCH(s)
@@ -104,8 +99,8 @@ __global__ void __launch_bounds__(512, 1) conv1x1_wgrad_k(const bf16_t* __restri
 #pragma unroll
       for (int j = 0; j < C1_TPW; ++j) {
         if (wv + 8 * j < T) {                                        // wave-uniform
-          const c1_bf16x8 A = C1_RD(dy_t + a_off[j] + ks * 16 * 32);
-          const c1_bf16x8 B = C1_RD(x_t + b_off[j] + ks * 16 * 32);
+          const ge_bf16x8 A = C1_RD(dy_t + a_off[j] + ks * 16 * 32);
+          const ge_bf16x8 B = C1_RD(x_t + b_off[j] + ks * 16 * 32);
           acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A, B, acc[j], 0, 0, 0);
         }
       }

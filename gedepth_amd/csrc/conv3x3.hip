@@ -19,9 +19,6 @@
 #include "common.h"
 #include <stdlib.h>
 
-typedef __bf16 cv_bf16x8 __attribute__((ext_vector_type(8)));
-typedef float cv_f32x16 __attribute__((ext_vector_type(16)));
-
 #define CV_TH 8
 #define CV_TW 32
 #define CV_KC 32                     // input channels per chunk
@@ -73,7 +70,7 @@ __global__ void __launch_bounds__(256, 2) conv3x3_nhwc_k(const bf16_t* __restric
   _Pragma("unroll") for (int i = 0; i < 6; ++i) if (in_src[i] != -1) *(uint4*)(in_tile + in_dst[i]) = pin[i];             \
   _Pragma("unroll") for (int i = 0; i < 9; ++i) *(uint4*)(w_tile + w_dst[i]) = pw[i];
 
-  cv_f32x16 acc[2][2];
+  ge_f32x16 acc[2][2];
 #pragma unroll
   for (int a = 0; a < 2; ++a)
 #pragma unroll
@@ -93,15 +90,15 @@ __global__ void __launch_bounds__(256, 2) conv3x3_nhwc_k(const bf16_t* __restric
     // MFMAs of step it issue (round 4: left to the compiler, every group of MFMAs waited on fragment reads issued a moment earlier —
     // s_waitcnt lgkmcnt(1) / (0) in the middle of each tap)
     {
-      cv_bf16x8 A[2][2], B[2][2];
+      ge_bf16x8 A[2][2], B[2][2];
       auto frags = [&](int set, int it) {
         const int tap = it >> 1, ks = it & 1, r = tap / 3, s = tap - 3 * r;
         const int ao = a_base0 + (r * (CV_TW + 2) + s) * CV_PITCH + ks * 16;
-        A[set][0] = *(const cv_bf16x8*)(in_tile + ao);
-        A[set][1] = *(const cv_bf16x8*)(in_tile + ao + (CV_TW + 2) * CV_PITCH);
+        A[set][0] = *(const ge_bf16x8*)(in_tile + ao);
+        A[set][1] = *(const ge_bf16x8*)(in_tile + ao + (CV_TW + 2) * CV_PITCH);
         const int bo = b_base + tap * CV_NT * CV_PITCH + ks * 16;
-        B[set][0] = *(const cv_bf16x8*)(w_tile + bo);
-        B[set][1] = *(const cv_bf16x8*)(w_tile + bo + 32 * CV_PITCH);
+        B[set][0] = *(const ge_bf16x8*)(w_tile + bo);
+        B[set][1] = *(const ge_bf16x8*)(w_tile + bo + 32 * CV_PITCH);
       };
       frags(0, 0);
 #pragma unroll
@@ -174,7 +171,6 @@ __global__ void __launch_bounds__(256, 2) conv3x3_nhwc_k(const bf16_t* __restric
 #define CD_BUF (80 * 1024)                                // per buffer: 75 KB of operands + 5 KB that absorb the idle DMA slots (8 waves x 10 slots)
 #define CD_NCH (CD_HCH + CD_WCH)                          // 75 DMA instructions per chunk
 #define CD_SLOTS 10                                       // per wave: chunks w, w + 8, ...
-#define CD_LDS(T, p) ((__attribute__((address_space(3))) T*)(p))
 #define CD_GLB(p) ((const __attribute__((address_space(1))) void*)(p))
 
 __device__ __attribute__((aligned(16))) uint32_t cd_zero16[4] = {0, 0, 0, 0};
@@ -215,11 +211,11 @@ __global__ void __launch_bounds__(512, 1) conv3x3_nhwc_dma_k(const bf16_t* __res
     const unsigned char* base = ch < CD_HCH ? xn : wb;       // compiler waits for ALL outstanding LDS reads at every join
     const unsigned char* p = goff[i] == ~0u ? (const unsigned char*)cd_zero16 : base + (size_t)(goff[i] + (unsigned)(c0 * 2));
     // inline asm instead of __builtin_amdgcn_global_load_lds: see csrc/gemm.hip (the builtin turns every LDS wait near it into lgkmcnt(0))
-    const unsigned ldst = (unsigned)(uintptr_t)CD_LDS(unsigned char, smem + buf * CD_BUF + ch * 1024);
+    const unsigned ldst = (unsigned)(uintptr_t)GE_LDS(unsigned char, smem + buf * CD_BUF + ch * 1024);
     asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off" :: "s"(ldst), "v"(p) : "memory", "m0");
   };
 
-  cv_f32x16 acc[2][2];
+  ge_f32x16 acc[2][2];
 #pragma unroll
   for (int a = 0; a < 2; ++a)
 #pragma unroll
@@ -248,16 +244,16 @@ __global__ void __launch_bounds__(512, 1) conv3x3_nhwc_dma_k(const bf16_t* __res
     const unsigned char* base = smem + buf * CD_BUF;
     // 18 groups (tap, ks) of 4 reads + 4 MFMAs; the reads of group g + 1 are issued before the MFMAs of group g (two register sets);
     // one DMA instruction of the next chunk after every second group
-    cv_bf16x8 A[2][2], B[2][2];
-    A[0][0] = *(const cv_bf16x8*)(base + abase[0][0]); A[0][1] = *(const cv_bf16x8*)(base + abase[0][1]);
-    B[0][0] = *(const cv_bf16x8*)(base + bbase); B[0][1] = *(const cv_bf16x8*)(base + bbase + 2048);
+    ge_bf16x8 A[2][2], B[2][2];
+    A[0][0] = *(const ge_bf16x8*)(base + abase[0][0]); A[0][1] = *(const ge_bf16x8*)(base + abase[0][1]);
+    B[0][0] = *(const ge_bf16x8*)(base + bbase); B[0][1] = *(const ge_bf16x8*)(base + bbase + 2048);
 #pragma unroll
     for (int g = 0; g < 18; ++g) {
       const int cs = g & 1, ns = cs ^ 1;
       if (g < 17) {
         const int tap = (g + 1) >> 1, kx = ((g + 1) & 1) << 5;
-        A[ns][0] = *(const cv_bf16x8*)(base + (abase[tap][0] ^ kx)); A[ns][1] = *(const cv_bf16x8*)(base + (abase[tap][1] ^ kx));
-        B[ns][0] = *(const cv_bf16x8*)(base + (bbase ^ kx) + tap * 4096); B[ns][1] = *(const cv_bf16x8*)(base + (bbase ^ kx) + tap * 4096 + 2048);
+        A[ns][0] = *(const ge_bf16x8*)(base + (abase[tap][0] ^ kx)); A[ns][1] = *(const ge_bf16x8*)(base + (abase[tap][1] ^ kx));
+        B[ns][0] = *(const ge_bf16x8*)(base + (bbase ^ kx) + tap * 4096); B[ns][1] = *(const ge_bf16x8*)(base + (bbase ^ kx) + tap * 4096 + 2048);
       }
       __builtin_amdgcn_sched_barrier(0);
       if (!(g & 1)) dma(g >> 1, cn, buf ^ 1);

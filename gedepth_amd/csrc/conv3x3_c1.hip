@@ -17,25 +17,16 @@
 // with one fp32 atomic per (tap, channel) and workgroup.
 #include "common.h"
 
-typedef __bf16 c1_bf2 __attribute__((ext_vector_type(2)));
-
 #define C1_THREADS 256
 #define C1_MAX_CIN 1024
 
 __device__ __forceinline__ float c1_dot8(const uint4 a, const uint4 b, float acc) {
-  acc = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(c1_bf2, a.x), __builtin_bit_cast(c1_bf2, b.x), acc, false);
-  acc = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(c1_bf2, a.y), __builtin_bit_cast(c1_bf2, b.y), acc, false);
-  acc = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(c1_bf2, a.z), __builtin_bit_cast(c1_bf2, b.z), acc, false);
-  acc = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(c1_bf2, a.w), __builtin_bit_cast(c1_bf2, b.w), acc, false);
+  acc = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(ge_bf16x2, a.x), __builtin_bit_cast(ge_bf16x2, b.x), acc, false);
+  acc = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(ge_bf16x2, a.y), __builtin_bit_cast(ge_bf16x2, b.y), acc, false);
+  acc = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(ge_bf16x2, a.z), __builtin_bit_cast(ge_bf16x2, b.z), acc, false);
+  acc = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(ge_bf16x2, a.w), __builtin_bit_cast(ge_bf16x2, b.w), acc, false);
   return acc;
 }
-
-template <typename TO> struct C1Out;
-template <> struct C1Out<float> { static __device__ __forceinline__ void st(float* p, float v) { *p = v; } static __device__ __forceinline__ float ld(const float* p) { return *p; } };
-template <> struct C1Out<bf16_t> {
-  static __device__ __forceinline__ void st(bf16_t* p, float v) { *p = f2bf(v); }
-  static __device__ __forceinline__ float ld(const bf16_t* p) { return bf2f(*p); }
-};
 
 // Work decomposition (both directions): a unit = 4 image rows x C1_XSEG pixels; wave w of the workgroup owns row w of the unit and walks it 8
 // pixels at a time, so the vertical taps of a wave are the rows its neighbours in the same CU load (L1), and no per-pixel divisions are
@@ -82,7 +73,7 @@ __global__ void __launch_bounds__(C1_THREADS) conv3x3_c1_fwd_k(const bf16_t* __r
       acc += __shfl_xor(acc, 1, 64);
       acc += __shfl_xor(acc, 2, 64);
       acc += __shfl_xor(acc, 4, 64);
-      if (sub == 0) C1Out<TO>::st(y + p, acc + b0);
+      if (sub == 0) Io<TO>::st(y + p, acc + b0);
     }
   }
 }
@@ -119,7 +110,7 @@ __global__ void __launch_bounds__(C1_THREADS) conv3x3_c1_bwd_k(const bf16_t* __r
         const int ry = i / (C1_XSEG + 2), rx = i - ry * (C1_XSEG + 2);
         const int yy = y0 + ry - 1, xx = x0 + rx - 1;
         float d = 0.f;
-        if (yy >= 0 && yy < H && xx >= 0 && xx < W) d = C1Out<TD>::ld(dy + ((long)n * H + yy) * W + xx);
+        if (yy >= 0 && yy < H && xx >= 0 && xx < W) d = Io<TD>::ld(dy + ((long)n * H + yy) * W + xx);
         dyt[i] = d;
       }
       __syncthreads();

@@ -15,11 +15,6 @@
 // accumulator tiles of 32 x 32.  One fp32 atomic flush per workgroup at the end (128-byte runs along Cin); dW must be zero-filled.
 #include "common.h"
 
-typedef __bf16 wg_bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 wg_bf16x4 __attribute__((ext_vector_type(4)));
-typedef float wg_f32x16 __attribute__((ext_vector_type(16)));
-#define WG_LDS(T, p) ((__attribute__((address_space(3))) T*)(p))
-
 #define WG_TH 8
 #define WG_TW 32
 #define WG_HALO ((WG_TH + 2) * (WG_TW + 2))          // 340 halo pixels
@@ -32,10 +27,10 @@ typedef float wg_f32x16 __attribute__((ext_vector_type(16)));
 // register + an immediate, and the fragments of step ks + 1 are read (second register set) BEFORE the MFMAs of step ks issue — with a
 // single set the compiler serialised read -> s_waitcnt lgkmcnt(0) -> MFMA for each of the 80 MFMAs of a tile (round 3: 22 % MFMA-busy).
 template <int TAP0, int NTAP>
-__device__ __forceinline__ void wg_tile_mfma(const bf16_t* dyh, const bf16_t* xt, wg_f32x16* acc) {
-  wg_bf16x8 A[2], B[2][NTAP];
-#define WG_RD(P) __builtin_shufflevector(__builtin_amdgcn_ds_read_tr16_b64_v4bf16(WG_LDS(wg_bf16x4, (P))), \
-                                         __builtin_amdgcn_ds_read_tr16_b64_v4bf16(WG_LDS(wg_bf16x4, (P) + 4 * 32)), 0, 1, 2, 3, 4, 5, 6, 7)
+__device__ __forceinline__ void wg_tile_mfma(const bf16_t* dyh, const bf16_t* xt, ge_f32x16* acc) {
+  ge_bf16x8 A[2], B[2][NTAP];
+#define WG_RD(P) __builtin_shufflevector(__builtin_amdgcn_ds_read_tr16_b64_v4bf16(GE_LDS(ge_bf16x4, (P))), \
+                                         __builtin_amdgcn_ds_read_tr16_b64_v4bf16(GE_LDS(ge_bf16x4, (P) + 4 * 32)), 0, 1, 2, 3, 4, 5, 6, 7)
 #define WG_FRAGS(SET, KS)                                                                                   \
   {                                                                                                         \
     constexpr int row_ = (KS) >> 1, xh_ = ((KS) & 1) * 16;                                                  \
@@ -68,7 +63,7 @@ __global__ void __launch_bounds__(256, 2) conv3x3_wgrad_k(const bf16_t* __restri
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const int c0 = blockIdx.x * 32, n0 = blockIdx.y * 64;
   const int mb = wv & 1, tap0 = (wv >> 1) ? 5 : 0, ntap = (wv >> 1) ? 4 : 5;
-  wg_f32x16 acc[5];
+  ge_f32x16 acc[5];
 #pragma unroll
   for (int t = 0; t < 5; ++t) acc[t] = 0.f;
   // transposing-read lane pattern: pixel row (lane >> 5) * 8 + ((lane & 15) >> 2) (+ 4 for the second read), channel piece

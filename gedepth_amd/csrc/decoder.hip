@@ -56,18 +56,6 @@ __global__ void __launch_bounds__(256) upcat_fwd_k(const T* __restrict__ coarse,
   V8<T>::st(o, v);
 }
 
-// output indices whose taps can touch input index X: src(o) in (X - 1, X + 1); one spare candidate on each side against rounding
-// (weights are recomputed exactly, a spare candidate contributes 0) — 5 instead of the 7 of the generic kernel at factor 2
-__device__ __forceinline__ void dec_cand_range(int X, int out, float scale, bool align, int& lo, int& hi) {
-  if (scale <= 0.f) { lo = 0; hi = out - 1; return; }
-  float a, b;
-  if (align) { a = ((float)X - 1.f) / scale; b = ((float)X + 1.f) / scale; }
-  else { a = ((float)X - 0.5f) / scale - 0.5f; b = ((float)X + 1.5f) / scale - 0.5f; }
-  lo = (int)floorf(a);
-  hi = (int)ceilf(b);
-  if (lo < 0) lo = 0;
-  if (hi > out - 1) hi = out - 1;
-}
 // d_coarse[n, Y, X, :] = sum over the outputs (oy, ox) whose taps touch (Y, X) of w * d_out[n, oy, ox, 0:Cu]; d_out rows have `pitch`
 // elements (the concat row).  Deterministic gather, no atomics.  grid.y = coarse row (n * Hc + Y).
 template <typename T>
@@ -81,8 +69,8 @@ __global__ void __launch_bounds__(256) upcat_bwd_k(const T* __restrict__ gout, T
   const int row = blockIdx.y, n = row / Hc, Y = row - n * Hc;
   const float sy = ge_scale(Hc, H, align), sx = ge_scale(Wc, W, align);
   int ylo, yhi, xlo, xhi;
-  dec_cand_range(Y, H, sy, align, ylo, yhi);
-  dec_cand_range(X, W, sx, align, xlo, xhi);
+  ge_cand_range<0>(Y, H, sy, align, ylo, yhi);
+  ge_cand_range<0>(X, W, sx, align, xlo, xhi);
   const T* g = gout + (long)n * H * W * pitch + j * VN;
   float acc[VN];
 #pragma unroll

@@ -37,11 +37,8 @@
 // built and dropped: its temporaries push the K loop's long-lived values into scratch (76 - 112 spilled registers in every variant tried).
 #include "common.h"
 
-typedef __bf16 gm_bf16x8 __attribute__((ext_vector_type(8)));
-typedef float gm_f32x16 __attribute__((ext_vector_type(16)));
 typedef float gm_f32x8 __attribute__((ext_vector_type(8)));
 typedef unsigned gm_u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned gm_u32x4 __attribute__((ext_vector_type(4)));
 
 #define GM_BM 256
 #define GM_BN 256
@@ -50,7 +47,6 @@ typedef unsigned gm_u32x4 __attribute__((ext_vector_type(4)));
 #ifndef GM_DIAG
 #define GM_DIAG 0                            // measurement aid: 1 no DMA in the K loop, 2 no MFMA, 4 no epilogue
 #endif
-#define GM_LDS(T, p) ((__attribute__((address_space(3))) T*)(p))
 #define GM_GLB(p) ((const __attribute__((address_space(1))) void*)(p))
 
 __device__ __attribute__((aligned(16))) uint32_t gm_zero16[4] = {0, 0, 0, 0};
@@ -97,7 +93,7 @@ __global__ void __launch_bounds__(512, 1) gemm_nt_k(GemmArgs a) {
   const int xoff0 = (wm * 128 + l31) * 128 + ((h ^ swz) << 4);
   const int woff0 = (wn * 64 + l31) * 128 + ((h ^ swz) << 4);
 
-  gm_f32x16 acc[4][2];
+  ge_f32x16 acc[4][2];
 
   // LDS-DMA.  The A operand streams from HBM (each token tile is read once per chip, latency ~2 us under load), the B operand from L2
   // (every workgroup reads the same weight rows): A gets a ring of THREE slots (the DMA of step g + 2 is issued during step g), B two.
@@ -127,7 +123,7 @@ __global__ void __launch_bounds__(512, 1) gemm_nt_k(GemmArgs a) {
     // inline asm, not __builtin_amdgcn_global_load_lds: the compiler books a FLAT-class instruction on BOTH counters, and with one of
     // them among the ds_reads every LDS wait of the K loop becomes lgkmcnt(0) — the fragment reads issued a moment ago included.  The
     // hardware counts an LDS-DMA on vmcnt only; all vmcnt waits of this kernel are explicit.
-    const unsigned ldst = (unsigned)(uintptr_t)GM_LDS(unsigned char, slot + wv * 4096 + c * 1024);
+    const unsigned ldst = (unsigned)(uintptr_t)GE_LDS(unsigned char, slot + wv * 4096 + c * 1024);
     asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off" :: "s"(ldst), "v"(p) : "memory", "m0");
   };
   unsigned char* const aslots = smem;
@@ -164,19 +160,19 @@ __global__ void __launch_bounds__(512, 1) gemm_nt_k(GemmArgs a) {
     unsigned char* da = aslots + a_slot * GM_TILE;
     unsigned char* db = bslots + b_slot * GM_TILE;
     // fragments of K group kk + 1 are read while the MFMAs of group kk run (two register sets)
-    gm_bf16x8 wf[2][2], xf[2][4];
+    ge_bf16x8 wf[2][2], xf[2][4];
 #pragma unroll
-    for (int nb = 0; nb < 2; ++nb) wf[0][nb] = *(const gm_bf16x8*)(wb + woff0 + nb * 4096);
+    for (int nb = 0; nb < 2; ++nb) wf[0][nb] = *(const ge_bf16x8*)(wb + woff0 + nb * 4096);
 #pragma unroll
-    for (int tb = 0; tb < 4; ++tb) xf[0][tb] = *(const gm_bf16x8*)(xa + xoff0 + tb * 4096);
+    for (int tb = 0; tb < 4; ++tb) xf[0][tb] = *(const ge_bf16x8*)(xa + xoff0 + tb * 4096);
 #pragma unroll
     for (int kk = 0; kk < 4; ++kk) {
       const int cs = kk & 1, ns = cs ^ 1;
       if (kk < 3) {
 #pragma unroll
-        for (int nb = 0; nb < 2; ++nb) wf[ns][nb] = *(const gm_bf16x8*)(wb + (woff0 ^ ((kk + 1) << 5)) + nb * 4096);
+        for (int nb = 0; nb < 2; ++nb) wf[ns][nb] = *(const ge_bf16x8*)(wb + (woff0 ^ ((kk + 1) << 5)) + nb * 4096);
 #pragma unroll
-        for (int tb = 0; tb < 4; ++tb) xf[ns][tb] = *(const gm_bf16x8*)(xa + (xoff0 ^ ((kk + 1) << 5)) + tb * 4096);
+        for (int tb = 0; tb < 4; ++tb) xf[ns][tb] = *(const ge_bf16x8*)(xa + (xoff0 ^ ((kk + 1) << 5)) + tb * 4096);
       }
       __builtin_amdgcn_sched_barrier(0);                      // keep the reads of group kk + 1 AHEAD of the MFMAs of group kk
       if (!(GM_DIAG & 1)) {                                   // B first: the four youngest DMA instructions at the end of the step are A's
@@ -219,8 +215,7 @@ __global__ void __launch_bounds__(512, 1) gemm_nt_k(GemmArgs a) {
       const GmTile cur = gm_tile(j + tl * per, xcd, a.ntn);
       const long m0 = (long)cur.mt * GM_BM + wm * 128;
       const int n0 = cur.nt * GM_BN + wn * 64;
-      typedef __bf16 b2 __attribute__((ext_vector_type(2)));
-      const unsigned slot_lds = (unsigned)(uintptr_t)GM_LDS(unsigned char, slot);
+      const unsigned slot_lds = (unsigned)(uintptr_t)GE_LDS(unsigned char, slot);
       // bias of the wave's 64 features through the SCALAR cache (s_load: lgkmcnt): an ordinary vector load here makes the compiler wait
       // vmcnt(0), which would drain the A ring's in-flight DMA once per tile.  n is wave-uniform; lanes pick their half by h.
       // The bias is added into the accumulators in place (16 bias registers live at a time).
@@ -262,8 +257,8 @@ __global__ void __launch_bounds__(512, 1) gemm_nt_k(GemmArgs a) {
 #pragma unroll
               for (int i = 0; i < 4; ++i) v[i] = acc[tb][nb][4 * g4 + i];
               gm_u32x2 d;
-              d.x = __builtin_bit_cast(unsigned, (b2){(__bf16)v[0], (__bf16)v[1]});
-              d.y = __builtin_bit_cast(unsigned, (b2){(__bf16)v[2], (__bf16)v[3]});
+              d.x = ge_pack_bf16x2(v[0], v[1]);
+              d.y = ge_pack_bf16x2(v[2], v[3]);
               // feature f = nb * 32 + 8 g4 + 4 h: piece f >> 3 = nb * 4 + g4, byte (f & 7) * 2 = 8 h inside it.  Written with an asm
               // ds_write: for a store the compiler can see it waits vmcnt(0) first (it cannot tell this slot from the ones the DMA in
               // flight is writing), and that would drain the A ring once per tile
@@ -280,7 +275,7 @@ __global__ void __launch_bounds__(512, 1) gemm_nt_k(GemmArgs a) {
         const bool inside = m0 + half * 64 + 64 <= a.M && n0 + 64 <= a.N;   // wave-uniform: no per-store masks inside the matrix
 #pragma unroll
         for (int q4 = 0; q4 < 2; ++q4) {                          // 4 + 4 rows of 8 tokens: 16 staging registers
-          gm_u32x4 o[4];                                          // asm reads for the same reason as the asm writes above
+          ge_u32x4 o[4];                                          // asm reads for the same reason as the asm writes above
 #pragma unroll
           for (int it = 0; it < 4; ++it) {
             const int tok = (q4 * 4 + it) * 8 + (lane_e >> 3), piece = lane_e & 7;
@@ -290,11 +285,11 @@ __global__ void __launch_bounds__(512, 1) gemm_nt_k(GemmArgs a) {
           asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
           if (inside) {
 #pragma unroll
-            for (int it = 0; it < 4; ++it) *(gm_u32x4*)(dp + (q4 * 4 + it) * 8 * ldc) = o[it];
+            for (int it = 0; it < 4; ++it) *(ge_u32x4*)(dp + (q4 * 4 + it) * 8 * ldc) = o[it];
           } else {
 #pragma unroll
             for (int it = 0; it < 4; ++it)
-              if (row0 + (q4 * 4 + it) * 8 < a.M && n < a.N) *(gm_u32x4*)(dp + (q4 * 4 + it) * 8 * ldc) = o[it];
+              if (row0 + (q4 * 4 + it) * 8 < a.M && n < a.N) *(ge_u32x4*)(dp + (q4 * 4 + it) * 8 * ldc) = o[it];
           }
         }
       }

@@ -43,18 +43,6 @@ __global__ void __launch_bounds__(256) bilinear_fwd_k(const T* __restrict__ in, 
   }
 }
 
-// candidate output indices whose taps can touch input index X
-__device__ __forceinline__ void cand_range(int X, int in, int out, float scale, bool align, int& lo, int& hi) {
-  if (scale <= 0.f) { lo = 0; hi = out - 1; return; }
-  float a, b;
-  if (align) { a = ((float)X - 1.f) / scale; b = ((float)X + 1.f) / scale; }
-  else { a = ((float)X - 0.5f) / scale - 0.5f; b = ((float)X + 1.5f) / scale - 0.5f; }
-  lo = (int)floorf(a) - 1;
-  hi = (int)ceilf(b) + 1;
-  if (lo < 0) lo = 0;
-  if (hi > out - 1) hi = out - 1;
-}
-
 #define GE_MAXC 8   // candidate taps per dimension kept in registers (up-sampling factors <= 2.5; wider ranges take the loop)
 
 template <typename T>
@@ -69,8 +57,8 @@ __global__ void __launch_bounds__(256) bilinear_bwd_k(const T* __restrict__ gout
     int Y = (int)(t % Hi);
     long nc = t / Hi;
     int ylo, yhi, xlo, xhi;
-    cand_range(Y, Hi, Ho, sy, align, ylo, yhi);
-    cand_range(X, Wi, Wo, sx, align, xlo, xhi);
+    ge_cand_range<1>(Y, Ho, sy, align, ylo, yhi);
+    ge_cand_range<1>(X, Wo, sx, align, xlo, xhi);
     const long n_ = nc / C, c_ = nc - n_ * C;
     const T* g = gout + n_ * gout_bs + c_ * gout_ps;
     float acc = 0.f;
@@ -475,11 +463,6 @@ extern "C" int ge_pe_channels(const float* raw, float* norm, float depth_scale, 
 }
 
 // ========================================================================================= SiLog
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 __global__ void __launch_bounds__(256) silog_stats_k(const float* __restrict__ pred, const float* __restrict__ gt, float eps,
                                                      double* __restrict__ stats, long n) {
   double cnt = 0, s1 = 0, s2 = 0;
@@ -491,7 +474,7 @@ __global__ void __launch_bounds__(256) silog_stats_k(const float* __restrict__ p
     }
   }
   __shared__ double sm[3][4];
-  cnt = wave_sum_d(cnt); s1 = wave_sum_d(s1); s2 = wave_sum_d(s2);
+  cnt = ge_wave_sum(cnt); s1 = ge_wave_sum(s1); s2 = ge_wave_sum(s2);
   int wv = threadIdx.x >> 6, ln = threadIdx.x & 63;
   if (ln == 0) { sm[0][wv] = cnt; sm[1][wv] = s1; sm[2][wv] = s2; }
   __syncthreads();
@@ -540,7 +523,7 @@ __global__ void __launch_bounds__(256) sumsq_k(const float* __restrict__ x, long
   }
   if (blockIdx.x == 0 && threadIdx.x < (n & 3)) { float v = x[(n4 << 2) + threadIdx.x]; s += (double)v * v; }
   __shared__ double sm[4];
-  s = wave_sum_d(s);
+  s = ge_wave_sum(s);
   if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = s;
   __syncthreads();
   if (threadIdx.x == 0) atomicAdd(out, sm[0] + sm[1] + sm[2] + sm[3]);
@@ -669,10 +652,7 @@ static int bias_act_launch(bool fwd, void* x_or_dx, const void* dy, const void* 
                            long HW, float slope, hipStream_t s) {
   const bool vec = (HW % V8<T>::N) == 0 && (((uintptr_t)x_or_dx | (uintptr_t)dy | (uintptr_t)y) & 15) == 0;
   const long per_plane = vec ? HW / V8<T>::N : HW;
-  unsigned gx = (unsigned)((per_plane + 256 * 4 - 1) / (256 * 4));
-  if (gx < 1) gx = 1;
-  if (gx > 64) gx = 64;
-  dim3 grid(gx, (unsigned)(N * C));
+  dim3 grid(ge_blocks(per_plane, 256 * 4, 64), (unsigned)(N * C));
   if (fwd) {
     if (vec) bias_act_fwd_k<T, true><<<grid, 256, 0, s>>>((T*)x_or_dx, bias, C, HW, slope);
     else bias_act_fwd_k<T, false><<<grid, 256, 0, s>>>((T*)x_or_dx, bias, C, HW, slope);

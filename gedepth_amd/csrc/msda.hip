@@ -15,35 +15,6 @@
 #include <mutex>
 #include <vector>
 
-template <typename T> struct Vec4;
-template <> struct Vec4<float> {
-  static __device__ __forceinline__ void ld(const float* p, float v[4]) {
-    float4 t = *(const float4*)p; v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-  }
-  static __device__ __forceinline__ void st(float* p, const float v[4]) { *(float4*)p = make_float4(v[0], v[1], v[2], v[3]); }
-};
-template <> struct Vec4<bf16_t> {
-  static __device__ __forceinline__ void ld(const bf16_t* p, float v[4]) {
-    uint2 t = *(const uint2*)p;
-    v[0] = __uint_as_float(t.x << 16); v[1] = __uint_as_float(t.x & 0xffff0000u);
-    v[2] = __uint_as_float(t.y << 16); v[3] = __uint_as_float(t.y & 0xffff0000u);
-  }
-  static __device__ __forceinline__ void st(bf16_t* p, const float v[4]) {
-    uint2 t;
-    t.x = (uint32_t)f2bf(v[0]) | ((uint32_t)f2bf(v[1]) << 16);
-    t.y = (uint32_t)f2bf(v[2]) | ((uint32_t)f2bf(v[3]) << 16);
-    *(uint2*)p = t;
-  }
-};
-
-__device__ __forceinline__ float group16_sum(float v) {
-  v += __shfl_xor(v, 8, 64);
-  v += __shfl_xor(v, 4, 64);
-  v += __shfl_xor(v, 2, 64);
-  v += __shfl_xor(v, 1, 64);
-  return v;
-}
-
 // HM (head-major work order): the work index runs (image, head, query) instead of (image, query, head), so that everything
 // an XCD has in flight samples ONE head of ONE image — 4.2 MB of value rows at the KITTI shape, which its 4 MB L2 mostly
 // holds — instead of all 8 heads (33.5 MB).  For query sets without spatial coherence (the cross-attention at
@@ -93,30 +64,21 @@ __global__ void __launch_bounds__(256) msda_fwd_k(const T* __restrict__ value, M
         const float wxa = x0 >= 0 ? 1.f - ax : 0.f, wxb = x0 + 1 < Wl ? ax : 0.f;
         const float wya = y0 >= 0 ? 1.f - ay : 0.f, wyb = y0 + 1 < Hl ? ay : 0.f;
         float v00[CPL], v01[CPL], v10[CPL], v11[CPL];
-        VecL<T>::ld(vl + mul24(mul24(ya, Wl) + xa, nh64), v00);
-        VecL<T>::ld(vl + mul24(mul24(ya, Wl) + xb, nh64), v01);
-        VecL<T>::ld(vl + mul24(mul24(yb, Wl) + xa, nh64), v10);
-        VecL<T>::ld(vl + mul24(mul24(yb, Wl) + xb, nh64), v11);
+        V8<T>::ld(vl + mul24(mul24(ya, Wl) + xa, nh64), v00);
+        V8<T>::ld(vl + mul24(mul24(ya, Wl) + xb, nh64), v01);
+        V8<T>::ld(vl + mul24(mul24(yb, Wl) + xa, nh64), v10);
+        V8<T>::ld(vl + mul24(mul24(yb, Wl) + xb, nh64), v11);
         const float w00 = wya * wxa * wgt, w01 = wya * wxb * wgt, w10 = wyb * wxa * wgt, w11 = wyb * wxb * wgt;
 #pragma unroll
         for (int i = 0; i < CPL; ++i) acc[i] += w00 * v00[i] + w01 * v01[i] + w10 * v10[i] + w11 * v11[i];
       }
     }
-    VecL<T>::st(out + grp * 64 + c0, acc);
+    V8<T>::st(out + grp * 64 + c0, acc);
   }
 }
 
-template <typename T> struct Ld1;
-template <> struct Ld1<float> { static __device__ __forceinline__ float ld(const float* p) { return *p; } };
-template <> struct Ld1<bf16_t> { static __device__ __forceinline__ float ld(const bf16_t* p) { return bf2f(*p); } };
-
 __device__ __forceinline__ float readlane_f(float v, int l) {   // the builtin is typed (int, int)
   return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l));
-}
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
 }
 
 // Backward: one wave64 per (batch, query, head), lane == channel.  Sampling locations / weights are wave-uniform
@@ -139,7 +101,7 @@ __global__ void __launch_bounds__(256) msda_bwd_k(const T* __restrict__ value, M
     const float* lp = loc + grp * (long)(LP * 2);
     const float* ap = attw + grp * (long)LP;
     const long vbase = ((long)b * Nv * nH + head) * 64 + lane;
-    const float go = Ld1<T>::ld(gout + grp * 64 + lane);
+    const float go = Io<T>::ld(gout + grp * 64 + lane);
     // per point: 4 taps (wave-uniform branch structure), partial sums over this lane's channel
 #define MSDA_POINT(j_, l_, Hl_, Wl_, sv_, sx_, sy_)                                                      \
     {                                                                                                    \
@@ -158,7 +120,7 @@ __global__ void __launch_bounds__(256) msda_bwd_k(const T* __restrict__ value, M
           if (yy >= 0 && yy < (Hl_) && xx >= 0 && xx < (Wl_)) {                                          \
             const long o = lbase + ((long)yy * (Wl_) + xx) * nH * 64;                                    \
             const float wx = (t & 1) ? ax : bx, wy = (t >> 1) ? ay : by;                                 \
-            const float gv = go * Ld1<T>::ld(value + o);                                                 \
+            const float gv = go * Io<T>::ld(value + o);                                                 \
             s_val += wy * wx * gv;                                                                       \
             s_dx += ((t & 1) ? wy : -wy) * gv;                                                           \
             s_dy += ((t >> 1) ? wx : -wx) * gv;                                                          \
@@ -223,7 +185,7 @@ __global__ void __launch_bounds__(256) msda_bwd_k(const T* __restrict__ value, M
           const int Hl = lv.H[l], Wl = lv.W[l];
           float sv, sx, sy;
           MSDA_POINT(j, l, Hl, Wl, sv, sx, sy)
-          sv = wave_sum(sv); sx = wave_sum(sx); sy = wave_sum(sy);
+          sv = ge_wave_sum(sv); sx = ge_wave_sum(sx); sy = ge_wave_sum(sy);
           if (lane == j) my_dattw = sv;
           if (lane == 2 * j) my_dloc = sx;
           if (lane == 2 * j + 1) my_dloc = sy;
@@ -445,8 +407,7 @@ __global__ void __launch_bounds__(256) MSDA_LW_ATTR msda_bwd_lw_k(const T* __res
         aw[l] = sub < 8 ? ap[l * 8 + sub] : 0.f;
         t += aw[l] * (sub < 8 ? ka[l] : 0.f);
       }
-#pragma unroll
-      for (int o = G / 2; o > 0; o >>= 1) t += __shfl_xor(t, o, 64);
+      t = ge_group_sum<G>(t);
       if (live && sub < 8) {
         T* lrow = (T*)em.d_logit + (g_ / nH) * em.logit_ld + (long)head * 32 + sub;
 #pragma unroll
@@ -550,17 +511,13 @@ __global__ void __launch_bounds__(1024) msda_hist_k(MsdaLevels lv, MsdaBins bins
 
 // The same two passes fed from the RAW projection outputs (bf16) + reference points instead of the fp32 loc / attw tensors (round 4:
 // those 2.4 GB per cross-attention launch are no longer written by the forward, ge_msda_fwd_mm), L == 4, P == 8: thread = sampling
-// point, the 32 points of a (query, head) are one half wave — locations in the forward's arithmetic to the bit (mm_div: the tile and
+// point, the 32 points of a (query, head) are one half wave — locations in the forward's arithmetic to the bit (ge_div_rn: the tile and
 // the cell of every tap must be the forward's), the softmax over the half wave on the DPP network (FILL only), 8-byte records.
 struct MsdaRawIn {
   const bf16_t* off; long off_ld; const bf16_t* logit; long logit_ld;
   const float* ref; long ref_sb, ref_sq, ref_sl;
   float fW[4], fH[4], rW[4], rH[4];                     // map sizes and their correctly rounded reciprocals
 };
-__device__ __forceinline__ float msda_div(float n, float d, float r) {       // = n / d for bf16-valued n, integer d <= 8191 (msda_mm.hip)
-  const float q0 = n * r;
-  return __builtin_fmaf(__builtin_fmaf(-q0, d, n), r, q0);
-}
 __device__ __forceinline__ float msda_half_max(float v) {                    // over the 32 lanes of a half wave, result in every lane
 #define MSDA_DPP_F(V, CTRL, RM) __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(V), __float_as_int(V), CTRL, RM, 0xf, false))
   v = fmaxf(v, MSDA_DPP_F(v, 0x111, 0xf)); v = fmaxf(v, MSDA_DPP_F(v, 0x112, 0xf));
@@ -648,8 +605,8 @@ __global__ void __launch_bounds__(1024, (FILL && U > 2) ? 4 : 8) msda_hist_raw_k
           const int t = g + s;
           const int j = j0 + t * 1024 + (int)threadIdx.x;
           const bool live = j < n;
-          const float lx = rx[t] + msda_div(__uint_as_float(o[t] << 16), fW, rW);
-          const float ly = ry[t] + msda_div(__uint_as_float(o[t] & 0xffff0000u), fH, rH);
+          const float lx = rx[t] + ge_div_rn(__uint_as_float(o[t] << 16), fW, rW);
+          const float ly = ry[t] + ge_div_rn(__uint_as_float(o[t] & 0xffff0000u), fH, rH);
           const float x = lx * fW - 0.5f, y = ly * fH - 0.5f;
           float wgt = 0.f;
           if (FILL) {
@@ -938,14 +895,14 @@ __global__ void __launch_bounds__(256) msda_drain_k(MsdaLevels lv, MsdaBins bins
       __builtin_amdgcn_wave_barrier();
 
       // ---- gather (next block in flight while this one is consumed) + run-wise accumulation
-      u32x4_t R[NR];                                       // (HIP's uint4 struct kept this array in scratch)
+      ge_u32x4 R[NR];                                       // (HIP's uint4 struct kept this array in scratch)
 #define MSDA_GATHER(BLK)                                                                                   \
   _Pragma("unroll") for (int i = 0; i < NR; ++i) {                                                         \
     const int q = s_key[(BLK) * 32 + i * RPI + gi] >> 7;                                                   \
-    R[i] = *(const u32x4_t*)(gout + (rowbase + (long)q * nH) * 64 + subc);                                 \
+    R[i] = *(const ge_u32x4*)(gout + (rowbase + (long)q * nH) * 64 + subc);                                 \
   }
 #define MSDA_PARK()                                                                                        \
-  _Pragma("unroll") for (int i = 0; i < NR; ++i) *(u32x4_t*)(stage + (i * RPI + gi) * 64 + subc) = R[i];
+  _Pragma("unroll") for (int i = 0; i < NR; ++i) *(ge_u32x4*)(stage + (i * RPI + gi) * 64 + subc) = R[i];
       // a0[p] += v for a wave-uniform p, only when `ok` (a branch around it makes the compiler copy all 32 registers)
 #define MSDA_PUT(P_, OK_, V_) a0[(P_) & 31] += (OK_) ? (V_) : 0.f
       int cls = 0;
@@ -959,7 +916,7 @@ __global__ void __launch_bounds__(256) msda_drain_k(MsdaLevels lv, MsdaBins bins
         // otherwise serialise every record on an LDS round trip; then the stage is free for the next block
         float gr[32];
 #pragma unroll
-        for (int k = 0; k < 32; ++k) gr[k] = Ld1<T>::ld(stage + k * 64 + lane);
+        for (int k = 0; k < 32; ++k) gr[k] = Io<T>::ld(stage + k * 64 + lane);
         if (blk + 1 < nb) { MSDA_GATHER(blk + 1) }
         // bilinear corner coefficients of record i0 + (lane & 31), zero for the corners that lie outside this tile
         f32x2_t cT, cB;
@@ -1082,7 +1039,6 @@ static int msda_bins(const MsdaLevels& lv, int L, MsdaBins& bins) {
   bins.first_tile[L] = n;
   return n;
 }
-
 
 // Kernel selection: bit 0 = LDS-window forward, bit 1 = LDS-window d_loc / d_attw (both need the query geometry), bit 2 =
 // owner-lane tap arithmetic in the window kernels, bit 3 = head-major work order in the streaming kernels; the
@@ -1559,7 +1515,6 @@ extern "C" int ge_msda_prep_bwd(const float* d_loc, const float* d_attw, const f
   return GE_OK;
 }
 
-
 // ============================================================================ fused prepare + sampling ("raw" entry points)
 // d_ref[b, q, l, :] = sum_{h, p} d_loc[b, q, h, l, p, :] from the emitted d_off_raw = d_loc / (W_l, H_l) (the heads of a query are
 // spread over workgroups in the head-major d_loc / d_attw kernel, so the sum is a small pass of its own: one thread per (row, level)).
@@ -1584,7 +1539,6 @@ __global__ void __launch_bounds__(256) msda_dref_k(const T* __restrict__ d_off, 
     d_ref[t * 2 + 1] = sy * (float)lv.H[l];
   }
 }
-
 
 // 1 when ge_msda_fwd_raw / ge_msda_bwd_raw run their fused kernels for this geometry under the current kernel-selection mode
 extern "C" int ge_msda_raw_supported(const int* spatial_hw, const int* query_hw, int n_qseg, int B, int Nv, int Nq, int nH, int L, int P) {

@@ -20,16 +20,10 @@
 // type); products are exact, sums fp32.  The exact-fp32 parity path keeps the VALU drain.
 #include "msda.h"
 
-typedef __bf16 md_bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 md_bf16x4 __attribute__((ext_vector_type(4)));
-typedef float md_f32x16 __attribute__((ext_vector_type(16)));
-
 #define MD_BLK 64                      // records per block = 4 K steps
 #define MD_HALF (MD_BLK * 32 + 32)     // bf16 elements of one channel-half image of the stage: [64 records][32 channels] + 64 B skew
 #define MD_STAGE (2 * MD_HALF)
 #define MD_AIMG (MD_BLK * 32)          // [4 K steps][2 k-groups][32 positions][8 records]
-#define LDS_PTR(T, p) ((__attribute__((address_space(3))) T*)(p))
-__device__ __forceinline__ bf16_t md_bf(float f) { return __builtin_bit_cast(bf16_t, (__bf16)f); }   // v_cvt_pk_bf16_f32, RNE
 
 // REC8: 8-byte records (bf16 weight, 8-bit fractions: the coefficients are rounded to bf16 in the image anyway; a fraction is taken at
 // the centre of its 1/256 step, so a coefficient moves by <= 2^-9 of the point's weight) — half the record bytes of fill and drain.
@@ -114,9 +108,9 @@ __global__ void __launch_bounds__(256) msda_drain_mfma_k(MsdaLevels lv, MsdaBins
     const bf16_t* grow = gout + ((long)b * Nq * nH + head) * 64 + sub8 * 8;     // + q * nH * 64
     const int qpitch = nH * 64;
 
-    md_f32x16 acc0 = 0.f, acc1 = 0.f;
+    ge_f32x16 acc0 = 0.f, acc1 = 0.f;
     const int nb = (n + MD_BLK - 1) / MD_BLK;
-    u32x4_t R[8];
+    ge_u32x4 R[8];
     rec_t E0, E1, E2;
     // a record slot past the end of the chunk: zero weight, the query of the chunk's first record (a row that exists)
     const rec_t padrec = MdRec<REC8>::pad(MdRec<REC8>::key(ent[0]));
@@ -124,10 +118,10 @@ __global__ void __launch_bounds__(256) msda_drain_mfma_k(MsdaLevels lv, MsdaBins
 #define MD_GATHER(EE)                                                                          \
   _Pragma("unroll") for (int i = 0; i < 8; ++i) {                                              \
     const int q = __shfl(MdRec<REC8>::key(EE) >> 7, i * 8 + row8, 64);                                       \
-    R[i] = *(const u32x4_t*)(grow + (long)q * qpitch);                                         \
+    R[i] = *(const ge_u32x4*)(grow + (long)q * qpitch);                                         \
   }
 #define MD_PARK()                                                                              \
-  _Pragma("unroll") for (int i = 0; i < 8; ++i) *(u32x4_t*)(stage + park_off + (i * 8 + row8) * 32) = R[i];
+  _Pragma("unroll") for (int i = 0; i < 8; ++i) *(ge_u32x4*)(stage + park_off + (i * 8 + row8) * 32) = R[i];
     // the four coefficients of this lane's record -> the A image (ZERO = true: clear the same slots again)
 #define MD_COEF(EE, ZERO)                                                                      \
   {                                                                                            \
@@ -137,10 +131,10 @@ __global__ void __launch_bounds__(256) msda_drain_mfma_k(MsdaLevels lv, MsdaBins
     const bool xl = lx >= 0, xr = lx < MSDA_TW - 1, yt = ly >= 0, yb = ly < MSDA_TH - 1;        \
     const float wl = 1.f - ax, wt = w * (1.f - ay), wb = w * ay;                                \
     bf16_t* a00 = aimg + a_rec + (ly * MSDA_TW + lx) * 8;                                       \
-    if (yt && xl) a00[0] = (ZERO) ? (bf16_t)0 : md_bf(wt * wl);                                 \
-    if (yt && xr) a00[8] = (ZERO) ? (bf16_t)0 : md_bf(wt * ax);                                 \
-    if (yb && xl) a00[MSDA_TW * 8] = (ZERO) ? (bf16_t)0 : md_bf(wb * wl);                       \
-    if (yb && xr) a00[MSDA_TW * 8 + 8] = (ZERO) ? (bf16_t)0 : md_bf(wb * ax);                   \
+    if (yt && xl) a00[0] = (ZERO) ? (bf16_t)0 : f2bf_hw(wt * wl);                                 \
+    if (yt && xr) a00[8] = (ZERO) ? (bf16_t)0 : f2bf_hw(wt * ax);                                 \
+    if (yb && xl) a00[MSDA_TW * 8] = (ZERO) ? (bf16_t)0 : f2bf_hw(wb * wl);                       \
+    if (yb && xr) a00[MSDA_TW * 8 + 8] = (ZERO) ? (bf16_t)0 : f2bf_hw(wb * ax);                   \
   }
     MD_LOAD(E0, 0)
     MD_LOAD(E1, 1)
@@ -155,21 +149,21 @@ __global__ void __launch_bounds__(256) msda_drain_mfma_k(MsdaLevels lv, MsdaBins
       MD_LOAD(E2, blk + 2)
 #pragma unroll
       for (int ks = 0; ks < 4; ++ks) {
-        const md_bf16x8 A = *(const md_bf16x8*)(aimg + ((ks * 2 + (lane >> 5)) * 32 + (lane & 31)) * 8);
+        const ge_bf16x8 A = *(const ge_bf16x8*)(aimg + ((ks * 2 + (lane >> 5)) * 32 + (lane & 31)) * 8);
 #pragma unroll
         for (int half = 0; half < 2; ++half) {
-          md_bf16x8 Bv;
+          ge_bf16x8 Bv;
           if (TR) {
             const bf16_t* p = stage + half * MD_HALF + (ks * 16 + tr_row) * 32 + tr_col;
-            const md_bf16x4 t0 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(LDS_PTR(md_bf16x4, p));
-            const md_bf16x4 t1 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(LDS_PTR(md_bf16x4, p + 4 * 32));
+            const ge_bf16x4 t0 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(GE_LDS(ge_bf16x4, p));
+            const ge_bf16x4 t1 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(GE_LDS(ge_bf16x4, p + 4 * 32));
             Bv = __builtin_shufflevector(t0, t1, 0, 1, 2, 3, 4, 5, 6, 7);
           } else {
             const bf16_t* p = stage + half * MD_HALF + (ks * 16 + (lane >> 5) * 8) * 32 + (lane & 31);
             uint32_t wq[4];
 #pragma unroll
             for (int e = 0; e < 4; ++e) wq[e] = (uint32_t)p[(2 * e) * 32] | ((uint32_t)p[(2 * e + 1) * 32] << 16);
-            Bv = __builtin_bit_cast(md_bf16x8, make_uint4(wq[0], wq[1], wq[2], wq[3]));
+            Bv = __builtin_bit_cast(ge_bf16x8, make_uint4(wq[0], wq[1], wq[2], wq[3]));
           }
           if (half == 0) acc0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A, Bv, acc0, 0, 0, 0);
           else acc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A, Bv, acc1, 0, 0, 0);

@@ -34,12 +34,6 @@
 #include <limits.h>
 #include <algorithm>
 
-typedef __bf16 mm_bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 mm_bf16x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 mm_bf16x2 __attribute__((ext_vector_type(2)));
-typedef float mm_f32x16 __attribute__((ext_vector_type(16)));
-typedef short mm_s16x2 __attribute__((ext_vector_type(2)));
-
 #ifndef MM_CAP
 #define MM_CAP 64                        // columns of the coefficient image = value rows staged per chunk (multiple of 16)
 #endif
@@ -70,15 +64,6 @@ typedef short mm_s16x2 __attribute__((ext_vector_type(2)));
 #ifndef MM_DIAG
 #define MM_DIAG 0                        // measurement aid: 1 no gathers, 2 no scatter, 4 no MFMA, 8 no output stores
 #endif
-#define MM_LDS_PTR(T, p) ((__attribute__((address_space(3))) T*)(p))
-
-__device__ __forceinline__ bf16_t mm_bf(float f) { return __builtin_bit_cast(bf16_t, (__bf16)f); }   // v_cvt_pk_bf16_f32, RNE
-
-// n / d for a bf16-valued n and an integer-valued d <= 8191, given r = RN(1 / d): see mm_taps
-__device__ __forceinline__ float mm_div(float n, float d, float r) {
-  const float q0 = n * r;
-  return __builtin_fmaf(__builtin_fmaf(-q0, d, n), r, q0);
-}
 
 struct MmArgs {
   const bf16_t* value; MsdaLevels lv;
@@ -93,7 +78,7 @@ struct MmArgs {
 // packed (x, y) 16-bit min / max over the 32 lanes of a half wave on the DPP network (row_shr 1, 2, 4, 8 inside the 16-lane rows, then
 // row_bcast:15 into rows 1 and 3): lanes 31 and 63 end up with their halves' results.  No LDS round trips (ds_bpermute: ~100 cycles each).
 template <bool MAXOP> __device__ __forceinline__ int mm_pk(int a, int b) {
-  const mm_s16x2 x = __builtin_bit_cast(mm_s16x2, a), y = __builtin_bit_cast(mm_s16x2, b);
+  const ge_s16x2 x = __builtin_bit_cast(ge_s16x2, a), y = __builtin_bit_cast(ge_s16x2, b);
   return __builtin_bit_cast(int, MAXOP ? __builtin_elementwise_max(x, y) : __builtin_elementwise_min(x, y));
 }
 template <bool MAXOP> __device__ __forceinline__ int mm_half_reduce(int v) {
@@ -155,9 +140,9 @@ __device__ __forceinline__ void mm_taps(const MmArgs& a, const uint32_t* u, floa
     // mmcv's arithmetic to the bit (`off / W` as msda_prep_fwd_k computes it): at initialisation the self-attention samples EXACT
     // pixel positions, where floor() — i.e. which one-sided derivative the offsets get — is decided by the last bit of the location.
     // The quotient is formed as q0 = off * RN(1 / W), q = fma(fma(-q0, W, off), RN(1 / W), q0): correctly rounded (Markstein), and
-    // bit-identical to IEEE division for EVERY bf16 offset and every W <= 8191 (exhaustive check: tools/ubench/msda_mm/divcheck.c) at 3
+    // bit-identical to IEEE division for EVERY bf16 offset and every W <= 8191 (exhaustive check: tools/ubench/divcheck.c) at 3
     // instead of ~10 instructions
-    const float lx = rx + mm_div(ox, fW, rW), ly = ry + mm_div(oy, fH, rH);
+    const float lx = rx + ge_div_rn(ox, fW, rW), ly = ry + ge_div_rn(oy, fH, rH);
     if (LOC && lp) *(float2*)(lp + 2 * p) = make_float2(lx, ly);
     const float x = lx * fW - 0.5f, y = ly * fH - 0.5f;                 // grid_sample, align_corners=False
     const bool in = qok && y > -1.f && x > -1.f && y < fH && x < fW;     // NaN-safe
@@ -204,8 +189,8 @@ __device__ __forceinline__ void mm_stage_rows(const MmWin& w, int c0, int n16, i
     const int pix = inA ? mul24(w.yminA + ry, w.WA) + w.xminA + rx + w.startA : mul24(w.yminB + ry, w.WB) + w.xminB + rx + w.startB;
     const bf16_t* src = w.vb + (uint32_t)(mul24(pix, nh64) + piece);      // uniform base + 32-bit element offset (launcher: < 2^31)
     if (!(MM_DIAG & 1)) {
-      __builtin_amdgcn_global_load_lds(src, MM_LDS_PTR(void, stage + j * 16 * 32), 16, 0, 0);
-      __builtin_amdgcn_global_load_lds(src + 32, MM_LDS_PTR(void, stage + HALF + j * 16 * 32), 16, 0, 0);
+      __builtin_amdgcn_global_load_lds(src, GE_LDS(void, stage + j * 16 * 32), 16, 0, 0);
+      __builtin_amdgcn_global_load_lds(src + 32, GE_LDS(void, stage + HALF + j * 16 * 32), 16, 0, 0);
     }
   }
 }
@@ -246,7 +231,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(MM_WAVE
     float rx = rp[0], ry = rp[1];
     float aw[2][8];
     mm_softmax(a, row, head, hv, qok, aw);
-    mm_f32x16 acc0 = 0.f, acc1 = 0.f;
+    ge_f32x16 acc0 = 0.f, acc1 = 0.f;
     const bf16_t* vb = a.value + ((long)b * a.Nv * a.nH + head) * 64;
 #pragma unroll 1
     for (int s = 0; s < 2; ++s) {
@@ -336,7 +321,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(MM_WAVE
             const int i00 = (o00 ? r00 : MF_CAP) * 32, i01 = (o01 ? r00 + dx : MF_CAP + 1) * 32;
             const int i10 = (o10 ? r10 : MF_CAP + 2) * 32, i11 = (o11 ? r10 + dx : MF_CAP + 3) * 32;
             const float v00 = bf2f(crow[i00]) + w00, v01 = bf2f(crow[i01]) + w01, v10 = bf2f(crow[i10]) + w10, v11 = bf2f(crow[i11]) + w11;
-            crow[i00] = mm_bf(v00); crow[i01] = mm_bf(v01); crow[i10] = mm_bf(v10); crow[i11] = mm_bf(v11);
+            crow[i00] = f2bf_hw(v00); crow[i01] = f2bf_hw(v01); crow[i10] = f2bf_hw(v10); crow[i11] = f2bf_hw(v11);
           }
         }
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");       // this chunk's LDS-DMA has landed; earlier operand reads are done
@@ -347,15 +332,15 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(MM_WAVE
 #pragma unroll 1
           for (int ks = 0; ks < n16; ++ks) {
             const bf16_t* pa = cimg + (ks * 16 + tr_row) * 32 + tr_col;
-            const mm_bf16x4 a0 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(MM_LDS_PTR(mm_bf16x4, pa));
-            const mm_bf16x4 a1 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(MM_LDS_PTR(mm_bf16x4, pa + 4 * 32));
-            const mm_bf16x8 A = __builtin_shufflevector(a0, a1, 0, 1, 2, 3, 4, 5, 6, 7);
+            const ge_bf16x4 a0 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(GE_LDS(ge_bf16x4, pa));
+            const ge_bf16x4 a1 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(GE_LDS(ge_bf16x4, pa + 4 * 32));
+            const ge_bf16x8 A = __builtin_shufflevector(a0, a1, 0, 1, 2, 3, 4, 5, 6, 7);
 #pragma unroll
             for (int half = 0; half < 2; ++half) {
               const bf16_t* p = stage + half * MF_HALF + (ks * 16 + tr_row) * 32 + tr_col;
-              const mm_bf16x4 t0 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(MM_LDS_PTR(mm_bf16x4, p));
-              const mm_bf16x4 t1 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(MM_LDS_PTR(mm_bf16x4, p + 4 * 32));
-              const mm_bf16x8 Bv = __builtin_shufflevector(t0, t1, 0, 1, 2, 3, 4, 5, 6, 7);
+              const ge_bf16x4 t0 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(GE_LDS(ge_bf16x4, p));
+              const ge_bf16x4 t1 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(GE_LDS(ge_bf16x4, p + 4 * 32));
+              const ge_bf16x8 Bv = __builtin_shufflevector(t0, t1, 0, 1, 2, 3, 4, 5, 6, 7);
               if (half == 0) acc0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A, Bv, acc0, 0, 0, 0);
               else acc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A, Bv, acc1, 0, 0, 0);
             }
@@ -371,8 +356,8 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(MM_WAVE
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const int m = (r & 3) + 8 * (r >> 2) + 4 * hv;
-        stage2[m * 72 + (lane & 31)] = mm_bf(acc0[r]);
-        stage2[m * 72 + 32 + (lane & 31)] = mm_bf(acc1[r]);
+        stage2[m * 72 + (lane & 31)] = f2bf_hw(acc0[r]);
+        stage2[m * 72 + 32 + (lane & 31)] = f2bf_hw(acc1[r]);
       }
       __builtin_amdgcn_wave_barrier();
 #pragma unroll
@@ -430,11 +415,11 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(MM_WAVE
     uint4 o0 = *(const uint4*)op, o1 = *(const uint4*)(op + 8);
     float rx = rp[0], ry = rp[1];
     // gradient row of (query, head) as the four B fragments: channels ks * 16 + hv * 8 .. + 7
-    mm_bf16x8 G[4];
+    ge_bf16x8 G[4];
     {
       const bf16_t* gp = ba.gout + row * nh64 + head * 64 + hv * 8;
 #pragma unroll
-      for (int ks = 0; ks < 4; ++ks) G[ks] = qok ? *(const mm_bf16x8*)(gp + ks * 16) : mm_bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
+      for (int ks = 0; ks < 4; ++ks) G[ks] = qok ? *(const ge_bf16x8*)(gp + ks * 16) : ge_bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
     }
     float aw[2][8];
     mm_softmax(a, row, head, hv, qok, aw);
@@ -462,7 +447,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(MM_WAVE
         for (int p = 0; p < 8; ++p) {
           awl[p] = s ? aw[1][p] : aw[0][p];
           const float ox = __uint_as_float(u[p] << 16), oy = __uint_as_float(u[p] & 0xffff0000u);
-          const float lx = rx + mm_div(ox, fW, rW), ly = ry + mm_div(oy, fH, rH);     // the forward's arithmetic to the bit
+          const float lx = rx + ge_div_rn(ox, fW, rW), ly = ry + ge_div_rn(oy, fH, rH);     // the forward's arithmetic to the bit
           const float x = lx * fW - 0.5f, y = ly * fH - 0.5f;
           const bool in = qok && y > -1.f && x > -1.f && y < fH && x < fW;
           const float xc = fminf(fmaxf(x, -1.f), fW), yc = fminf(fmaxf(y, -1.f), fH);
@@ -537,10 +522,10 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(MM_WAVE
           __builtin_amdgcn_wave_barrier();
 #pragma unroll 1
           for (int mb = 0; mb < (n16 + 1) >> 1; ++mb) {
-            mm_f32x16 acc = 0.f;
+            ge_f32x16 acc = 0.f;
 #pragma unroll
             for (int ks = 0; ks < 4; ++ks) {
-              const mm_bf16x8 A = *(const mm_bf16x8*)(stage + (ks >> 1) * MM_HALF + (mb * 32 + q) * 32 + (ks & 1) * 16 + hv * 8);
+              const ge_bf16x8 A = *(const ge_bf16x8*)(stage + (ks >> 1) * MM_HALF + (mb * 32 + q) * 32 + (ks & 1) * 16 + hv * 8);
               acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A, G[ks], acc, 0, 0, 0);
             }
 #pragma unroll
@@ -572,7 +557,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(MM_WAVE
         uint32_t pr[8];
 #pragma unroll
         for (int p = 0; p < 8; ++p) {
-          pr[p] = (uint32_t)mm_bf(sx[p] * awl[p]) | ((uint32_t)mm_bf(sy[p] * awl[p]) << 16);
+          pr[p] = (uint32_t)f2bf_hw(sx[p] * awl[p]) | ((uint32_t)f2bf_hw(sy[p] * awl[p]) << 16);
           dsum += awl[p] * sv[p];
           if (s == 0) dav[0][p] = sv[p]; else dav[1][p] = sv[p];
         }
@@ -591,7 +576,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(MM_WAVE
         uint32_t pr[4];
 #pragma unroll
         for (int i = 0; i < 4; ++i)
-          pr[i] = (uint32_t)mm_bf(aw[s][2 * i] * (dav[s][2 * i] - dsum)) | ((uint32_t)mm_bf(aw[s][2 * i + 1] * (dav[s][2 * i + 1] - dsum)) << 16);
+          pr[i] = (uint32_t)f2bf_hw(aw[s][2 * i] * (dav[s][2 * i] - dsum)) | ((uint32_t)f2bf_hw(aw[s][2 * i + 1] * (dav[s][2 * i + 1] - dsum)) << 16);
         *(uint4*)(ba.d_logit + row * ba.d_logit_ld + head * 32 + (s + 2 * hv) * 8) = make_uint4(pr[0], pr[1], pr[2], pr[3]);
       }
     }
@@ -913,7 +898,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(MM_WAVE
     for (int c0 = 0; c0 < Ks; c0 += MV_CAP) {
       const int rows = min(MV_CAP, Ks - c0);
       const int nb = (rows + 31) >> 5;
-      mm_f32x16 acc[MV_NB][2];
+      ge_f32x16 acc[MV_NB][2];
 #pragma unroll
       for (int i = 0; i < MV_NB; ++i) { acc[i][0] = 0.f; acc[i][1] = 0.f; }
       // software pipeline over the tiles of the run: order entry two tiles ahead, raw projections one tile ahead
@@ -939,8 +924,8 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(MM_WAVE
           const int qr = __shfl(qq, j * 16 + (lane >> 2), 64);
           const bf16_t* src = va.gout + ((long)b * a.Nq + qr) * nh64 + head * 64 + (lane & 3) * 8;
           if (!(MV_DIAG & 1)) {
-            __builtin_amdgcn_global_load_lds(src, MM_LDS_PTR(void, stage + j * 16 * 32), 16, 0, 0);
-            __builtin_amdgcn_global_load_lds(src + 32, MM_LDS_PTR(void, stage + MV_HALF + j * 16 * 32), 16, 0, 0);
+            __builtin_amdgcn_global_load_lds(src, GE_LDS(void, stage + j * 16 * 32), 16, 0, 0);
+            __builtin_amdgcn_global_load_lds(src + 32, GE_LDS(void, stage + MV_HALF + j * 16 * 32), 16, 0, 0);
           }
         }
         // in flight under this tile's arithmetic: the next tile's raw projections, the order entry of the tile after it
@@ -973,7 +958,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(MM_WAVE
 #pragma unroll
           for (int p = 0; p < 4; ++p) {
             const float ox = __uint_as_float(u[p] << 16), oy = __uint_as_float(u[p] & 0xffff0000u);
-            const float lx = rw.rx + mm_div(ox, fW, rW), ly = rw.ry + mm_div(oy, fH, rH);
+            const float lx = rw.rx + ge_div_rn(ox, fW, rW), ly = rw.ry + ge_div_rn(oy, fH, rH);
             const float x = lx * fW - 0.5f, y = ly * fH - 0.5f;
             const bool in = qok && y > -1.f && x > -1.f && y < fH && x < fW;
             const float xc = fminf(fmaxf(x, -1.f), fW), yc = fminf(fmaxf(y, -1.f), fH);
@@ -1013,20 +998,20 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(MM_WAVE
           const int i00 = (o00 ? r00 : MV_CAP) * MV_CROW, i01 = (o01 ? r00 + dx : MV_CAP + 1) * MV_CROW;
           const int i10 = (o10 ? r10 : MV_CAP + 2) * MV_CROW, i11 = (o11 ? r10 + dx : MV_CAP + 3) * MV_CROW;
           const float v00 = bf2f(ccol[i00]) + w00, v01 = bf2f(ccol[i01]) + w01, v10 = bf2f(ccol[i10]) + w10, v11 = bf2f(ccol[i11]) + w11;
-          ccol[i00] = mm_bf(v00); ccol[i01] = mm_bf(v01); ccol[i10] = mm_bf(v10); ccol[i11] = mm_bf(v11);
+          ccol[i00] = f2bf_hw(v00); ccol[i01] = f2bf_hw(v01); ccol[i10] = f2bf_hw(v10); ccol[i11] = f2bf_hw(v11);
         }
         // the two lanes of a query write different ROWS (their groups' boxes), but a masked corner of group 0 and one of group 1 share
         // the dump rows: harmless (never read)
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");         // gradient rows have landed (and the prefetches), image complete
         __builtin_amdgcn_wave_barrier();
-        mm_bf16x8 Bf[2][2];                                                 // queries ks * 16 .. + 15 of both channel halves
+        ge_bf16x8 Bf[2][2];                                                 // queries ks * 16 .. + 15 of both channel halves
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
           for (int half = 0; half < 2; ++half) {
             const bf16_t* p = stage + half * MV_HALF + (ks * 16 + tr_row) * 32 + tr_col;
-            const mm_bf16x4 u0 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(MM_LDS_PTR(mm_bf16x4, p));
-            const mm_bf16x4 u1 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(MM_LDS_PTR(mm_bf16x4, p + 4 * 32));
+            const ge_bf16x4 u0 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(GE_LDS(ge_bf16x4, p));
+            const ge_bf16x4 u1 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(GE_LDS(ge_bf16x4, p + 4 * 32));
             Bf[ks][half] = __builtin_shufflevector(u0, u1, 0, 1, 2, 3, 4, 5, 6, 7);
           }
 #pragma unroll
@@ -1034,7 +1019,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(MM_WAVE
           if (rb < nb && !(MV_DIAG & 4)) {
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks) {
-              const mm_bf16x8 A = *(const mm_bf16x8*)(cimg + (rb * 32 + q) * MV_CROW + ks * 16 + (lane >> 5) * 8);
+              const ge_bf16x8 A = *(const ge_bf16x8*)(cimg + (rb * 32 + q) * MV_CROW + ks * 16 + (lane >> 5) * 8);
               acc[rb][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A, Bf[ks][0], acc[rb][0], 0, 0, 0);
               acc[rb][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A, Bf[ks][1], acc[rb][1], 0, 0, 0);
             }
@@ -1258,8 +1243,6 @@ __global__ void __launch_bounds__(256) msda_vs_index_k(MvWs mv, VsWs vs, MsdaLev
 struct VsArgs { MmArgs f; const bf16_t* gout; float* d_value; VsWs ws; };
 struct VsRaw { uint32_t o; uint32_t l01, l23; uint32_t own; float rx, ry; };      // offsets (x, y) of the lane's point, four of the 32 logits, the lane's own logit, reference point
 
-typedef short vs_s16x2 __attribute__((ext_vector_type(2)));
-
 // OR over the 8 lanes that share a query / over the wave, on the DPP network
 __device__ __forceinline__ float vs_max8(float v) {
   v = fmaxf(v, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xf, 0xf, true)));     // quad_perm [1,0,3,2]
@@ -1327,7 +1310,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))
     const int q = tid >> 3, p = tid & 7, lane = tid & 63;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int tr_row = (lane >> 5) * 8 + ((lane & 15) >> 2), tr_col = ((lane >> 4) & 1) * 16 + (lane & 3) * 4;
-    mm_f32x16 acc[3][2];
+    ge_f32x16 acc[3][2];
 #pragma unroll
     for (int i = 0; i < 3; ++i) { acc[i][0] = 0.f; acc[i][1] = 0.f; }
     auto tile_at = [&](int i) { return list[min(i, n - 1)]; };
@@ -1393,7 +1376,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))
       float w[4];
       {
         const float ox = __uint_as_float(raw0.o << 16), oy = __uint_as_float(raw0.o & 0xffff0000u);
-        const float lx = raw0.rx + mm_div(ox, fW, rW), ly = raw0.ry + mm_div(oy, fH, rH);
+        const float lx = raw0.rx + ge_div_rn(ox, fW, rW), ly = raw0.ry + ge_div_rn(oy, fH, rH);
         const float x = lx * fW - 0.5f, y = ly * fH - 0.5f;
         const bool in = qok && y > -1.f && x > -1.f && y < fH && x < fW;
         const float xc = fminf(fmaxf(x, -1.f), fW), yc = fminf(fmaxf(y, -1.f), fH);
@@ -1428,10 +1411,10 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))
           mask |= 1 << (e[k] >> 5);
           const int el = buf * VS_IMG + e[k] * VS_CROW + q;
           c1[k] = el;
-          const short hv = (short)mm_bf(w[k]);
-          vs_s16x2 pv;
+          const short hv = (short)f2bf_hw(w[k]);
+          ge_s16x2 pv;
           pv[0] = (q & 1) ? (short)0 : hv; pv[1] = (q & 1) ? hv : (short)0;
-          __builtin_amdgcn_ds_atomic_fadd_v2bf16(MM_LDS_PTR(vs_s16x2, cimg + (el & ~1)), pv);
+          __builtin_amdgcn_ds_atomic_fadd_v2bf16(GE_LDS(ge_s16x2, cimg + (el & ~1)), pv);
         }
       }
       mask = vs_wave_or(mask);
@@ -1445,14 +1428,14 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))
       const int mine = (lm >> (3 * wv)) & 7;
       if (mine && !(VS_DIAG & 4)) {
         const bf16_t* st = stage + buf * 2 * MV_HALF;
-        mm_bf16x8 Bf[2][2];
+        ge_bf16x8 Bf[2][2];
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
           for (int half = 0; half < 2; ++half) {
             const bf16_t* pp = st + half * MV_HALF + (ks * 16 + tr_row) * 32 + tr_col;
-            const mm_bf16x4 u0 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(MM_LDS_PTR(mm_bf16x4, pp));
-            const mm_bf16x4 u1 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(MM_LDS_PTR(mm_bf16x4, pp + 4 * 32));
+            const ge_bf16x4 u0 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(GE_LDS(ge_bf16x4, pp));
+            const ge_bf16x4 u1 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(GE_LDS(ge_bf16x4, pp + 4 * 32));
             Bf[ks][half] = __builtin_shufflevector(u0, u1, 0, 1, 2, 3, 4, 5, 6, 7);
           }
 #pragma unroll
@@ -1460,7 +1443,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))
           if ((mine >> rb) & 1) {
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks) {
-              const mm_bf16x8 A = *(const mm_bf16x8*)(img + ((wv * 3 + rb) * 32 + (lane & 31)) * VS_CROW + ks * 16 + (lane >> 5) * 8);
+              const ge_bf16x8 A = *(const ge_bf16x8*)(img + ((wv * 3 + rb) * 32 + (lane & 31)) * VS_CROW + ks * 16 + (lane >> 5) * 8);
               acc[rb][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A, Bf[ks][0], acc[rb][0], 0, 0, 0);
               acc[rb][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A, Bf[ks][1], acc[rb][1], 0, 0, 0);
             }

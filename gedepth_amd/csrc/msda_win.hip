@@ -52,16 +52,6 @@ __device__ __forceinline__ MwTap mw_tap(float x, float y, int Wl, int Hl) {
   t.kxa = x0 >= 0; t.kxb = x0 + 1 < Wl; t.kya = y0 >= 0; t.kyb = y0 + 1 < Hl;
   return t;
 }
-__device__ __forceinline__ int mw_wave_min(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o, 64));
-  return v;
-}
-__device__ __forceinline__ int mw_wave_max(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o, 64));
-  return v;
-}
 
 // RAW = true: the kernel consumes the raw outputs of the `sampling_offsets` / `attention_weights` linears (+ the reference
 // points) instead of ready-made locations / weights, i.e. mmcv's view -> softmax over L*P -> `ref + off / (W_l, H_l)` happens in
@@ -176,7 +166,7 @@ __device__ __forceinline__ bool mw_stage(const T* __restrict__ vl, int Wl, int H
       xmin = min(xmin, t.xa); xmax = max(xmax, t.xb); ymin = min(ymin, t.ya); ymax = max(ymax, t.yb);
     }
   }
-  xmin = mw_wave_min(xmin); ymin = mw_wave_min(ymin); xmax = mw_wave_max(xmax); ymax = mw_wave_max(ymax);
+  xmin = ge_wave_min(xmin); ymin = ge_wave_min(ymin); xmax = ge_wave_max(xmax); ymax = ge_wave_max(ymax);
   __syncthreads();                                            // s_box initialised; previous level's window reads done
   if ((threadIdx.x & 63) == 0 && xmax >= 0) {
     atomicMin(&s_box[0], xmin); atomicMin(&s_box[1], ymin); atomicMax(&s_box[2], xmax); atomicMax(&s_box[3], ymax);
@@ -223,16 +213,16 @@ template <> struct MwAcc<bf16_t> {
 __device__ __forceinline__ void mw_fma4_packed(float* acc, const uint4& a, const uint4& b, const uint4& c, const uint4& d, uint32_t wab,
                                                uint32_t wcd) {
   const uint32_t ra[4] = {a.x, a.y, a.z, a.w}, rb[4] = {b.x, b.y, b.z, b.w}, rc[4] = {c.x, c.y, c.z, c.w}, rd[4] = {d.x, d.y, d.z, d.w};
-  const bf16x2_t vab = __builtin_bit_cast(bf16x2_t, wab), vcd = __builtin_bit_cast(bf16x2_t, wcd);
+  const ge_bf16x2 vab = __builtin_bit_cast(ge_bf16x2, wab), vcd = __builtin_bit_cast(ge_bf16x2, wcd);
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     const uint32_t ab_lo = __builtin_amdgcn_perm(rb[i], ra[i], 0x05040100u), ab_hi = __builtin_amdgcn_perm(rb[i], ra[i], 0x07060302u);
     const uint32_t cd_lo = __builtin_amdgcn_perm(rd[i], rc[i], 0x05040100u), cd_hi = __builtin_amdgcn_perm(rd[i], rc[i], 0x07060302u);
     float lo = acc[2 * i], hi = acc[2 * i + 1];
-    lo = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2_t, ab_lo), vab, lo, false);
-    hi = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2_t, ab_hi), vab, hi, false);
-    lo = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2_t, cd_lo), vcd, lo, false);
-    hi = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2_t, cd_hi), vcd, hi, false);
+    lo = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(ge_bf16x2, ab_lo), vab, lo, false);
+    hi = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(ge_bf16x2, ab_hi), vab, hi, false);
+    lo = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(ge_bf16x2, cd_lo), vcd, lo, false);
+    hi = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(ge_bf16x2, cd_hi), vcd, hi, false);
     acc[2 * i] = lo; acc[2 * i + 1] = hi;
   }
 }
@@ -375,7 +365,7 @@ __global__ void __launch_bounds__(256) msda_fwd_win_k(const T* __restrict__ valu
   }
 #pragma unroll
   for (int i = 0; i < MW_QPG; ++i)
-    if (qok[i]) VecL<T>::st(out + (long)qrow[i] * 64 + sub * CPL, acc[i]);
+    if (qok[i]) V8<T>::st(out + (long)qrow[i] * 64 + sub * CPL, acc[i]);
 }
 
 // d_loc / d_attw: per point the four <gradient row, value row> dot products (raw bf16 pairs through v_dot2c), the three

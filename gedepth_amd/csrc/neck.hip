@@ -207,16 +207,6 @@ extern "C" int ge_map_from_tokens(const void* tok, long tok_bs, const void* res,
 // = `identity + DropPath(branch)` of the Swin blocks (depthformer_swin.py:461-472 via mmcv DropPath / FFN): ATen runs a
 // divide, a multiply and an add over the token tensor; this is one pass, mixed precision (fp32 residual stream + bf16
 // branch in stage 0).  Backward of the branch: d_branch = d_out * scale[b] (ge_scale_rows); the identity gradient is d_out.
-template <typename T> struct E8;       // 8 consecutive elements <-> 8 floats
-template <> struct E8<float> {
-  static __device__ __forceinline__ void ld(const float* p, float v[8]) { V8<float>::ld(p, v); V8<float>::ld(p + 4, v + 4); }
-  static __device__ __forceinline__ void st(float* p, const float v[8]) { V8<float>::st(p, v); V8<float>::st(p + 4, v + 4); }
-};
-template <> struct E8<bf16_t> {
-  static __device__ __forceinline__ void ld(const bf16_t* p, float v[8]) { V8<bf16_t>::ld(p, v); }
-  static __device__ __forceinline__ void st(bf16_t* p, const float v[8]) { V8<bf16_t>::st(p, v); }
-};
-
 // HAS_ID = false: out = branch * scale (the backward pass)
 template <typename TI, typename TB, typename TO, bool HAS_ID, bool VEC>
 __global__ void __launch_bounds__(256) scale_add_k(const TI* __restrict__ identity, const TB* __restrict__ branch,
@@ -228,16 +218,16 @@ __global__ void __launch_bounds__(256) scale_add_k(const TI* __restrict__ identi
     const long nv = per_sample / 8;
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < nv; i += (long)gridDim.x * blockDim.x) {
       float x[8], y[8];
-      E8<TB>::ld(branch + base + i * 8, y);
+      Vec<TB, 8>::ld(branch + base + i * 8, y);
       if (HAS_ID) {
-        E8<TI>::ld(identity + base + i * 8, x);
+        Vec<TI, 8>::ld(identity + base + i * 8, x);
 #pragma unroll
         for (int k = 0; k < 8; ++k) y[k] = x[k] + y[k] * sc;
       } else {
 #pragma unroll
         for (int k = 0; k < 8; ++k) y[k] = y[k] * sc;
       }
-      E8<TO>::st(out + base + i * 8, y);
+      Vec<TO, 8>::st(out + base + i * 8, y);
     }
   } else {
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < per_sample; i += (long)gridDim.x * blockDim.x) {
@@ -251,10 +241,7 @@ template <typename TI, typename TB, typename TO, bool HAS_ID>
 static int scale_add_launch(const void* identity, const void* branch, const float* scale, void* out, int B, long per_sample,
                             hipStream_t s) {
   const bool vec = per_sample % 8 == 0 && al16(branch) && al16(out) && (!HAS_ID || al16(identity));
-  long gx = ((vec ? per_sample / 8 : per_sample) + 256 * 4 - 1) / (256 * 4);
-  if (gx < 1) gx = 1;
-  if (gx > 4096) gx = 4096;
-  dim3 grid((unsigned)gx, (unsigned)B);
+  dim3 grid(ge_blocks(vec ? per_sample / 8 : per_sample, 256 * 4, 4096), (unsigned)B);
   if (vec) scale_add_k<TI, TB, TO, HAS_ID, true><<<grid, 256, 0, s>>>((const TI*)identity, (const TB*)branch, scale, (TO*)out, per_sample);
   else scale_add_k<TI, TB, TO, HAS_ID, false><<<grid, 256, 0, s>>>((const TI*)identity, (const TB*)branch, scale, (TO*)out, per_sample);
   GE_LAUNCH_CHECK();

@@ -71,12 +71,7 @@ __global__ void __launch_bounds__(256) nh_partials_reduce_k(const float* __restr
     ws[kc] = accumulate ? (O)((double)ws[kc] + a) : (O)a;
   }
 }
-static inline unsigned nh_grid_rows(long R, int rpi) {
-  long b = (R + (long)rpi * 8 - 1) / ((long)rpi * 8);
-  if (b < 1) b = 1;
-  if (b > NH_MAXBLOCKS) b = NH_MAXBLOCKS;
-  return (unsigned)b;
-}
+static inline unsigned nh_grid_rows(long R, int rpi) { return ge_blocks(R, rpi * 8, NH_MAXBLOCKS); }      // ~8 rows per thread
 // workspace of the column-sum users: K*C doubles (sums) | 3*C floats (BatchNorm coefficients) | NH_MAXBLOCKS*K*C floats (partials)
 extern "C" size_t ge_nhwc_workspace(int C, int K) {
   return (size_t)C * ((size_t)K * sizeof(double) + 3 * sizeof(float) + (size_t)NH_MAXBLOCKS * K * sizeof(float));
@@ -240,12 +235,8 @@ static inline bool nh_aligned(const void* a, const void* b = nullptr, const void
   return ((((uintptr_t)a) | ((uintptr_t)b) | ((uintptr_t)c) | ((uintptr_t)d)) & 15) == 0;
 }
 static inline unsigned nh_grid_vec(long nvec) { return ge_blocks(nvec, 256 * 4, 65536); }
-static inline unsigned nh_grid_apply(long R, int rpi) {           // ~4 rows per thread, enough workgroups to fill 256 CUs several times
-  long b = (R + (long)rpi * 4 - 1) / ((long)rpi * 4);
-  if (b < 1) b = 1;
-  if (b > 16384) b = 16384;
-  return (unsigned)b;
-}
+// ~4 rows per thread, enough workgroups to fill 256 CUs several times
+static inline unsigned nh_grid_apply(long R, int rpi) { return ge_blocks(R, rpi * 4, 16384); }
 
 // workspace: ge_nhwc_workspace(C, 2) bytes: double[2C] sums | float[3C] coefficients | partials
 template <typename T>
@@ -414,17 +405,6 @@ __global__ void __launch_bounds__(256) bilinear_nhwc_fwd_k(const T* __restrict__
     V8<T>::st(out + ((n * Ho + y) * (long)Wo + x) * C + c0, o);
   }
 }
-// candidate output indices whose taps can touch input index X (same rule as the NCHW kernel, ground.hip)
-__device__ __forceinline__ void nh_cand_range(int X, int in, int out, float scale, bool align, int& lo, int& hi) {
-  if (scale <= 0.f) { lo = 0; hi = out - 1; return; }
-  float a, b;
-  if (align) { a = ((float)X - 1.f) / scale; b = ((float)X + 1.f) / scale; }
-  else { a = ((float)X - 0.5f) / scale - 0.5f; b = ((float)X + 1.5f) / scale - 0.5f; }
-  lo = (int)floorf(a) - 1;
-  hi = (int)ceilf(b) + 1;
-  if (lo < 0) lo = 0;
-  if (hi > out - 1) hi = out - 1;
-}
 // deterministic gather: each input element sums the contributions of the outputs whose taps touch it (no atomics)
 template <typename T>
 __global__ void __launch_bounds__(256) bilinear_nhwc_bwd_k(const T* __restrict__ gout, T* __restrict__ gin, int N, int Hi, int Wi, int Ho, int Wo,
@@ -439,8 +419,8 @@ __global__ void __launch_bounds__(256) bilinear_nhwc_bwd_k(const T* __restrict__
     const int Y = (int)(t % Hi);
     const long n = t / Hi;
     int ylo, yhi, xlo, xhi;
-    nh_cand_range(Y, Hi, Ho, sy, align, ylo, yhi);
-    nh_cand_range(X, Wi, Wo, sx, align, xlo, xhi);
+    ge_cand_range<1>(Y, Ho, sy, align, ylo, yhi);
+    ge_cand_range<1>(X, Wo, sx, align, xlo, xhi);
     const T* g = gout + n * (long)Ho * Wo * C + c0;
     float acc[VN];
 #pragma unroll
@@ -483,7 +463,7 @@ __global__ void __launch_bounds__(256) bilinear_nhwc_bwd_h_k(const T* __restrict
     const int X = (int)(t % Wi);
     const long row = t / Wi;                                  // n * Ho + oy
     int xlo, xhi;
-    nh_cand_range(X, Wi, Wo, sx, align, xlo, xhi);
+    ge_cand_range<1>(X, Wo, sx, align, xlo, xhi);
     const T* g = gout + row * (long)Wo * C + c0;
     float acc[VN];
 #pragma unroll
@@ -515,7 +495,7 @@ __global__ void __launch_bounds__(256) bilinear_nhwc_bwd_v_k(const float* __rest
     const int Y = (int)(t % Hi);
     const long n = t / Hi;
     int ylo, yhi;
-    nh_cand_range(Y, Hi, Ho, sy, align, ylo, yhi);
+    ge_cand_range<1>(Y, Ho, sy, align, ylo, yhi);
     float acc[VN];
 #pragma unroll
     for (int k = 0; k < VN; ++k) acc[k] = 0.f;
@@ -834,10 +814,7 @@ static int bias_gelu_fwd_launch(const void* x, const float* bias, void* out, lon
   int lpr = lanes < NH_MAXLANES ? lanes : NH_MAXLANES;
   while (lanes % lpr) --lpr;
   const int rpi = NH_MAXLANES / lpr, chunks = lanes / lpr;
-  long gx = (R + (long)rpi * 4 - 1) / ((long)rpi * 4);           // ~4 rows per thread
-  if (gx < 1) gx = 1;
-  if (gx > 16384) gx = 16384;
-  bias_gelu_fwd_k<T><<<dim3((unsigned)gx, chunks), 256, 0, s>>>((const T*)x, bias, (T*)out, C, R, lpr, rpi);
+  bias_gelu_fwd_k<T><<<dim3(nh_grid_apply(R, rpi), chunks), 256, 0, s>>>((const T*)x, bias, (T*)out, C, R, lpr, rpi);
   GE_LAUNCH_CHECK();
   return GE_OK;
 }

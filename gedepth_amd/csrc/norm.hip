@@ -13,32 +13,6 @@
 
 #define LN_MAX_CH 12            // 4-element chunks per lane: C <= 4 * GS * 12 (3072 at GS = 64)
 
-template <typename T> struct Q4;      // 4 consecutive elements <-> 4 floats
-template <> struct Q4<float> {
-  static __device__ __forceinline__ void ld(const float* p, float v[4]) { const float4 t = *(const float4*)p; v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w; }
-  static __device__ __forceinline__ void st(float* p, const float v[4]) { *(float4*)p = make_float4(v[0], v[1], v[2], v[3]); }
-};
-template <> struct Q4<bf16_t> {
-  static __device__ __forceinline__ void ld(const bf16_t* p, float v[4]) {
-    const uint2 t = *(const uint2*)p;
-    v[0] = __uint_as_float(t.x << 16); v[1] = __uint_as_float(t.x & 0xffff0000u);
-    v[2] = __uint_as_float(t.y << 16); v[3] = __uint_as_float(t.y & 0xffff0000u);
-  }
-  static __device__ __forceinline__ void st(bf16_t* p, const float v[4]) {
-    uint2 t;
-    t.x = (uint32_t)f2bf(v[0]) | ((uint32_t)f2bf(v[1]) << 16);
-    t.y = (uint32_t)f2bf(v[2]) | ((uint32_t)f2bf(v[3]) << 16);
-    *(uint2*)p = t;
-  }
-};
-
-template <int GS>
-__device__ __forceinline__ float group_sum(float v) {
-#pragma unroll
-  for (int o = GS / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 // grid-stride over rows; C % 4 == 0; NCH = ceil(C / (4 * GS)) <= LN_MAX_CH
 template <typename TX, typename TY, int GS, int NCH>
 __global__ void __launch_bounds__(256) layernorm_fwd_k(const TX* __restrict__ x, const float* __restrict__ gamma,
@@ -54,10 +28,10 @@ __global__ void __launch_bounds__(256) layernorm_fwd_k(const TX* __restrict__ x,
 #pragma unroll
     for (int j = 0; j < NCH; ++j) {
       const int c = (j * GS + sub) * 4;
-      if (c < C) { Q4<TX>::ld(xp + c, v[j]); s += (v[j][0] + v[j][1]) + (v[j][2] + v[j][3]); }
+      if (c < C) { Vec<TX, 4>::ld(xp + c, v[j]); s += (v[j][0] + v[j][1]) + (v[j][2] + v[j][3]); }
       else { v[j][0] = v[j][1] = v[j][2] = v[j][3] = 0.f; }
     }
-    const float mu = group_sum<GS>(s) * inv_c;
+    const float mu = ge_group_sum<GS>(s) * inv_c;
     float q = 0.f;
 #pragma unroll
     for (int j = 0; j < NCH; ++j) {
@@ -67,7 +41,7 @@ __global__ void __launch_bounds__(256) layernorm_fwd_k(const TX* __restrict__ x,
         for (int k = 0; k < 4; ++k) { const float d = v[j][k] - mu; q += d * d; }
       }
     }
-    const float rs = rsqrtf(group_sum<GS>(q) * inv_c + eps);
+    const float rs = rsqrtf(ge_group_sum<GS>(q) * inv_c + eps);
     TY* yp = y + row * C;
 #pragma unroll
     for (int j = 0; j < NCH; ++j) {
@@ -76,7 +50,7 @@ __global__ void __launch_bounds__(256) layernorm_fwd_k(const TX* __restrict__ x,
         const float4 g = *(const float4*)(gamma + c), b = *(const float4*)(beta + c);
         float o[4] = {(v[j][0] - mu) * rs * g.x + b.x, (v[j][1] - mu) * rs * g.y + b.y,
                       (v[j][2] - mu) * rs * g.z + b.z, (v[j][3] - mu) * rs * g.w + b.w};
-        Q4<TY>::st(yp + c, o);
+        Vec<TY, 4>::st(yp + c, o);
       }
     }
     if (sub == 0) { mean[row] = mu; rstd[row] = rs; }
@@ -115,8 +89,8 @@ __global__ void __launch_bounds__(256) layernorm_bwd_k(const TY* __restrict__ dy
       const int c = (j * GS + sub) * 4;
       if (c < C) {
         float xv[4], gv[4];
-        Q4<TX>::ld(xp + c, xv);
-        Q4<TY>::ld(gp + c, gv);
+        Vec<TX, 4>::ld(xp + c, xv);
+        Vec<TY, 4>::ld(gp + c, gv);
         const float4 gm = *(const float4*)(gamma + c);
         const float gmv[4] = {gm.x, gm.y, gm.z, gm.w};
 #pragma unroll
@@ -133,7 +107,7 @@ __global__ void __launch_bounds__(256) layernorm_bwd_k(const TY* __restrict__ dy
         for (int k = 0; k < 4; ++k) { xh[j][k] = 0.f; g[j][k] = 0.f; }
       }
     }
-    const float m1 = group_sum<GS>(s1) * inv_c, m2 = group_sum<GS>(s2) * inv_c;
+    const float m1 = ge_group_sum<GS>(s1) * inv_c, m2 = ge_group_sum<GS>(s2) * inv_c;
     TX* dp = dx + row * C;
 #pragma unroll
     for (int j = 0; j < NCH; ++j) {
@@ -144,11 +118,11 @@ __global__ void __launch_bounds__(256) layernorm_bwd_k(const TY* __restrict__ dy
         for (int k = 0; k < 4; ++k) o[k] = rs * (g[j][k] - m1 - xh[j][k] * m2);
         if (dres) {                                      // the gradient that reached x through the residual branch: summed here, not by autograd
           float q[4];
-          Q4<TX>::ld(dres + row * C + c, q);
+          Vec<TX, 4>::ld(dres + row * C + c, q);
 #pragma unroll
           for (int k = 0; k < 4; ++k) o[k] += q[k];
         }
-        Q4<TX>::st(dp + c, o);
+        Vec<TX, 4>::st(dp + c, o);
       }
     }
   }
@@ -505,10 +479,7 @@ __global__ void __launch_bounds__(256) bn_bwd_apply_k(const T* __restrict__ dy, 
 
 static inline dim3 bn_grid(int N, int C, long HW, int vn, bool vec) {
   const long per_plane = vec ? HW / vn : HW;
-  long gx = (per_plane + 256 * 4 - 1) / (256 * 4);
-  if (gx < 1) gx = 1;
-  if (gx > 64) gx = 64;
-  return dim3((unsigned)gx, (unsigned)(N * C));
+  return dim3(ge_blocks(per_plane, 256 * 4, 64), (unsigned)(N * C));
 }
 static inline bool bn_vec(long HW, int vn, const void* a, const void* b, const void* c, const void* d) {
   return HW % vn == 0 && ((((uintptr_t)a) | ((uintptr_t)b) | ((uintptr_t)c) | ((uintptr_t)d)) & 15) == 0;

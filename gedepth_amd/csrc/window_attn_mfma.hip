@@ -22,20 +22,17 @@
 #include "common.h"
 #include "window_attn.h"
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
 #define RLD 40   // row-major bf16 tiles: 64 rows x (32 + 8 pad) -> 80-byte rows: ds_read_b128 conflict-free
 #define VLD 68   // transposed V tile: 32 dims x (64 + 4 pad) keys -> 136-byte rows (8-byte aligned)
 
-__device__ __forceinline__ f32x16 mfma_bf16(bf16x8 a, bf16x8 b, f32x16 c) {
+__device__ __forceinline__ ge_f32x16 mfma_bf16(ge_bf16x8 a, ge_bf16x8 b, ge_f32x16 c) {
   return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
 }
 // ---- fp8 (OCP e4m3 on gfx950) variant of the two forward contractions: v_mfma_f32_32x32x16_fp8_fp8 has the same
-// (lane, k-slot) operand map as the bf16 instruction (8 values per lane and K = 16 step), so a bf16x8 fragment converts in
+// (lane, k-slot) operand map as the bf16 instruction (8 values per lane and K = 16 step), so a ge_bf16x8 fragment converts in
 // registers: value * scale -> v_cvt_pk_fp8_f32.  Scales are per (window, head) and per operand: 448 / amax of the staged
 // tile (the e4m3 maximum), folded back into the score scale / output multiplier.  BASELINE.json configs[4].
-__device__ __forceinline__ f32x16 mfma_fp8(long a, long b, f32x16 c) {
+__device__ __forceinline__ ge_f32x16 mfma_fp8(long a, long b, ge_f32x16 c) {
   return __builtin_amdgcn_mfma_f32_32x32x16_fp8_fp8(a, b, c, 0, 0, 0);
 }
 __device__ __forceinline__ long fp8x8_from_f32(const float v[8]) {
@@ -46,7 +43,7 @@ __device__ __forceinline__ long fp8x8_from_f32(const float v[8]) {
   hi = __builtin_amdgcn_cvt_pk_fp8_f32(v[6], v[7], hi, true);
   return (long)(((unsigned long)(unsigned)hi << 32) | (unsigned long)(unsigned)lo);
 }
-__device__ __forceinline__ long fp8x8_from_bf16(bf16x8 x, float scale) {
+__device__ __forceinline__ long fp8x8_from_bf16(ge_bf16x8 x, float scale) {
   const uint4 u = __builtin_bit_cast(uint4, x);
   const uint32_t w[4] = {u.x, u.y, u.z, u.w};
   float v[8];
@@ -62,28 +59,21 @@ __device__ __forceinline__ float tile_fp8_scale(const bf16_t* tile, int ld, int 
     const int r = i / cols, cc = i - r * cols;
     m = fmaxf(m, fabsf(bf2f(tile[r * ld + cc])));
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+  m = ge_wave_max(m);
   return m > 0.f ? FP8_MAX / m : 1.f;
 }
 
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ uint32_t pack2(float lo, float hi) {   // -> v_cvt_pk_bf16_f32 (round-to-nearest-even)
-  bf16x2 v = {(__bf16)lo, (__bf16)hi};
-  return __builtin_bit_cast(uint32_t, v);
-}
-__device__ __forceinline__ bf16_t f2bf_hw(float f) { return __builtin_bit_cast(bf16_t, (__bf16)f); }
-__device__ __forceinline__ bf16x8 pack8(const f32x16& v, int base) {   // v[base .. base+7] -> 8 bf16
+__device__ __forceinline__ ge_bf16x8 pack8(const ge_f32x16& v, int base) {   // v[base .. base+7] -> 8 bf16
   uint4 u;
-  u.x = pack2(v[base + 0], v[base + 1]); u.y = pack2(v[base + 2], v[base + 3]);
-  u.z = pack2(v[base + 4], v[base + 5]); u.w = pack2(v[base + 6], v[base + 7]);
-  return __builtin_bit_cast(bf16x8, u);
+  u.x = ge_pack_bf16x2(v[base + 0], v[base + 1]); u.y = ge_pack_bf16x2(v[base + 2], v[base + 3]);
+  u.z = ge_pack_bf16x2(v[base + 4], v[base + 5]); u.w = ge_pack_bf16x2(v[base + 6], v[base + 7]);
+  return __builtin_bit_cast(ge_bf16x8, u);
 }
 // register r of the C/D layout -> row inside the 32-row tile
 __device__ __forceinline__ int crow(int r, int hi) { return (r & 3) + 8 * (r >> 2) + 4 * hi; }
 
 // 8 bf16 of one column `col` of a row-major [.][RLD] tile, rows kappa(base, e), e = 0..7  (A operand of X^T products)
-__device__ __forceinline__ bf16x8 col8(const bf16_t* tile, int base_row, int col) {
+__device__ __forceinline__ ge_bf16x8 col8(const bf16_t* tile, int base_row, int col) {
   uint32_t w[4];
 #pragma unroll
   for (int p = 0; p < 4; ++p) {
@@ -92,19 +82,19 @@ __device__ __forceinline__ bf16x8 col8(const bf16_t* tile, int base_row, int col
     w[p] = (uint32_t)tile[r0 * RLD + col] | ((uint32_t)tile[r1 * RLD + col] << 16);
   }
   uint4 u = make_uint4(w[0], w[1], w[2], w[3]);
-  return __builtin_bit_cast(bf16x8, u);
+  return __builtin_bit_cast(ge_bf16x8, u);
 }
 // same but rows are CONSECUTIVE (base_row + e): used for the query-contracted products
-__device__ __forceinline__ bf16x8 col8_lin(const bf16_t* tile, int base_row, int col) {
+__device__ __forceinline__ ge_bf16x8 col8_lin(const bf16_t* tile, int base_row, int col) {
   uint32_t w[4];
 #pragma unroll
   for (int p = 0; p < 4; ++p)
     w[p] = (uint32_t)tile[(base_row + 2 * p) * RLD + col] | ((uint32_t)tile[(base_row + 2 * p + 1) * RLD + col] << 16);
   uint4 u = make_uint4(w[0], w[1], w[2], w[3]);
-  return __builtin_bit_cast(bf16x8, u);
+  return __builtin_bit_cast(ge_bf16x8, u);
 }
-__device__ __forceinline__ bf16x8 row8(const bf16_t* tile, int row, int col0) {   // 16-byte aligned row fragment
-  return __builtin_bit_cast(bf16x8, *(const uint4*)(tile + row * RLD + col0));
+__device__ __forceinline__ ge_bf16x8 row8(const bf16_t* tile, int row, int col0) {   // 16-byte aligned row fragment
+  return __builtin_bit_cast(ge_bf16x8, *(const uint4*)(tile + row * RLD + col0));
 }
 
 // Stage a 49 x 32 bf16 operand row-major into LDS (rows >= 49 zero).  pad rows take `padval` (fp32 -> bf16).
@@ -122,7 +112,7 @@ __device__ __forceinline__ void stage_rm(const bf16_t* __restrict__ base, long r
         v[it] = *(const uint4*)(base + (long)src * row_stride + col0 + part);
       } else if (padval) {
         const float* pv = padval + col0 + part;
-        v[it] = make_uint4(pack2(pv[0], pv[1]), pack2(pv[2], pv[3]), pack2(pv[4], pv[5]), pack2(pv[6], pv[7]));
+        v[it] = make_uint4(ge_pack_bf16x2(pv[0], pv[1]), ge_pack_bf16x2(pv[2], pv[3]), ge_pack_bf16x2(pv[4], pv[5]), ge_pack_bf16x2(pv[6], pv[7]));
       }
     }
   }
@@ -147,7 +137,7 @@ __device__ __forceinline__ void load_rm(const bf16_t* __restrict__ base, long ro
         v[it] = *(const uint4*)(base + (long)src * row_stride + col0 + part);
       } else if (padval) {
         const float* pv = padval + col0 + part;
-        v[it] = make_uint4(pack2(pv[0], pv[1]), pack2(pv[2], pv[3]), pack2(pv[4], pv[5]), pack2(pv[6], pv[7]));
+        v[it] = make_uint4(ge_pack_bf16x2(pv[0], pv[1]), ge_pack_bf16x2(pv[2], pv[3]), ge_pack_bf16x2(pv[4], pv[5]), ge_pack_bf16x2(pv[6], pv[7]));
       }
     }
   }
@@ -175,7 +165,7 @@ __device__ __forceinline__ void stage_vt(const bf16_t* __restrict__ base, long r
         v[it] = *(const uint4*)(base + (long)src * row_stride + col0 + part);
       } else {
         const float* pv = padval + col0 + part;
-        v[it] = make_uint4(pack2(pv[0], pv[1]), pack2(pv[2], pv[3]), pack2(pv[4], pv[5]), pack2(pv[6], pv[7]));
+        v[it] = make_uint4(ge_pack_bf16x2(pv[0], pv[1]), ge_pack_bf16x2(pv[2], pv[3]), ge_pack_bf16x2(pv[4], pv[5]), ge_pack_bf16x2(pv[6], pv[7]));
       }
     }
   }
@@ -205,7 +195,7 @@ __device__ __forceinline__ void fill_meta(const WinGeom& g, int wy, int wx, int 
 }
 
 // S^T tiles: acc[kt][qt] (row = key, col = query) from row-major K and Q tiles
-__device__ __forceinline__ void st_tiles(const bf16_t* A_rows, const bf16_t* B_rows, int c, int hi, f32x16 acc[2][2]) {
+__device__ __forceinline__ void st_tiles(const bf16_t* A_rows, const bf16_t* B_rows, int c, int hi, ge_f32x16 acc[2][2]) {
 #pragma unroll
   for (int kt = 0; kt < 2; ++kt)
 #pragma unroll
@@ -214,8 +204,8 @@ __device__ __forceinline__ void st_tiles(const bf16_t* A_rows, const bf16_t* B_r
       for (int i = 0; i < 16; ++i) acc[kt][qt][i] = 0.f;
 #pragma unroll
   for (int ks = 0; ks < 2; ++ks) {
-    const bf16x8 a0 = row8(A_rows, c, ks * 16 + hi * 8), a1 = row8(A_rows, 32 + c, ks * 16 + hi * 8);
-    const bf16x8 b0 = row8(B_rows, c, ks * 16 + hi * 8), b1 = row8(B_rows, 32 + c, ks * 16 + hi * 8);
+    const ge_bf16x8 a0 = row8(A_rows, c, ks * 16 + hi * 8), a1 = row8(A_rows, 32 + c, ks * 16 + hi * 8);
+    const ge_bf16x8 b0 = row8(B_rows, c, ks * 16 + hi * 8), b1 = row8(B_rows, 32 + c, ks * 16 + hi * 8);
     acc[0][0] = mfma_bf16(a0, b0, acc[0][0]);
     acc[0][1] = mfma_bf16(a0, b1, acc[0][1]);
     acc[1][0] = mfma_bf16(a1, b0, acc[1][0]);
@@ -226,7 +216,7 @@ __device__ __forceinline__ void st_tiles(const bf16_t* A_rows, const bf16_t* B_r
 // fp8 version of st_tiles: operands converted fragment by fragment with the tile scales sa (A rows) / sb (B rows); the
 // accumulators hold (sa * sb) * S^T
 __device__ __forceinline__ void st_tiles_fp8(const bf16_t* A_rows, const bf16_t* B_rows, int c, int hi, float sa, float sb,
-                                             f32x16 acc[2][2]) {
+                                             ge_f32x16 acc[2][2]) {
 #pragma unroll
   for (int kt = 0; kt < 2; ++kt)
 #pragma unroll
@@ -245,7 +235,7 @@ __device__ __forceinline__ void st_tiles_fp8(const bf16_t* A_rows, const bf16_t*
 }
 
 // scores -> normalised probabilities, in place.  Lane owns query columns c (qt=0) and 32+c (qt=1).
-__device__ __forceinline__ void softmax_cols(f32x16 acc[2][2], const float* bias, const uint32_t* meta, int c, int hi,
+__device__ __forceinline__ void softmax_cols(ge_f32x16 acc[2][2], const float* bias, const uint32_t* meta, int c, int hi,
                                              float scale, bool use_mask) {
 #pragma unroll
   for (int qt = 0; qt < 2; ++qt) {
@@ -288,12 +278,12 @@ __device__ __forceinline__ void softmax_cols(f32x16 acc[2][2], const float* bias
 }
 
 // store a (32 dims x 32 cols) C/D tile as rows of `dst`: column `col_tok` (token index) gets dims d = crow(r,hi)
-__device__ __forceinline__ void store_cols(const f32x16& o, float mul, bf16_t* __restrict__ row_ptr, int hi) {
+__device__ __forceinline__ void store_cols(const ge_f32x16& o, float mul, bf16_t* __restrict__ row_ptr, int hi) {
 #pragma unroll
   for (int gq = 0; gq < 4; ++gq) {
     uint2 u;
-    u.x = pack2(o[4 * gq + 0] * mul, o[4 * gq + 1] * mul);
-    u.y = pack2(o[4 * gq + 2] * mul, o[4 * gq + 3] * mul);
+    u.x = ge_pack_bf16x2(o[4 * gq + 0] * mul, o[4 * gq + 1] * mul);
+    u.y = ge_pack_bf16x2(o[4 * gq + 2] * mul, o[4 * gq + 3] * mul);
     *(uint2*)(row_ptr + 8 * gq + 4 * hi) = u;
   }
 }
@@ -329,7 +319,7 @@ __global__ void __launch_bounds__(64) window_attn_fwd_mfma_k(const bf16_t* __res
   stage_vt(base, 3 * g.C, 2 * g.C + head * HD, sm.m.tok, qkv_bias, sm.vt, lane);
   __syncthreads();
 
-  f32x16 acc[2][2];
+  ge_f32x16 acc[2][2];
   float out_mul = 1.f;
   float v_scale = 1.f;
   if constexpr (FP8) {
@@ -345,7 +335,7 @@ __global__ void __launch_bounds__(64) window_attn_fwd_mfma_k(const bf16_t* __res
   softmax_cols(acc, sm.bias, sm.m.meta, c, hi, scale, use_mask);
 
   // O^T[d][query] = sum_key V^T[d][key] P^T[key][query]; k-slot (hi,e) <-> key kappa = kt*32 + 16 s + 4 hi + (e&3) + 8 (e>>2)
-  f32x16 o[2];
+  ge_f32x16 o[2];
 #pragma unroll
   for (int qt = 0; qt < 2; ++qt)
 #pragma unroll
@@ -356,7 +346,7 @@ __global__ void __launch_bounds__(64) window_attn_fwd_mfma_k(const bf16_t* __res
     for (int s = 0; s < 2; ++s) {
       const int kb = kt * 32 + 16 * s + 4 * hi;
       const uint2 lo = *(const uint2*)(sm.vt + c * VLD + kb), hi8 = *(const uint2*)(sm.vt + c * VLD + kb + 8);
-      const bf16x8 a = __builtin_bit_cast(bf16x8, make_uint4(lo.x, lo.y, hi8.x, hi8.y));
+      const ge_bf16x8 a = __builtin_bit_cast(ge_bf16x8, make_uint4(lo.x, lo.y, hi8.x, hi8.y));
       if constexpr (FP8) {
         const long a8 = fp8x8_from_bf16(a, v_scale);
         float p0[8], p1[8];
@@ -411,7 +401,7 @@ __global__ void __launch_bounds__(64) window_attn_bwd_mfma_k(const bf16_t* __res
   // that owns accumulator element (kt, qt, r) sums its dS over all windows in REGISTERS and scatters once at the end
   // (64 LDS float atomics per workgroup instead of per window: ds_add_f32 costs ~170 cycles per wave-instruction, which made
   // this kernel 5x slower than the forward one).
-  f32x16 dB[2][2];
+  ge_f32x16 dB[2][2];
 #pragma unroll
   for (int kt = 0; kt < 2; ++kt)
 #pragma unroll
@@ -431,7 +421,7 @@ __global__ void __launch_bounds__(64) window_attn_bwd_mfma_k(const bf16_t* __res
     stage_rm(gout + (long)b * L * g.C, g.C, head * HD, sm.m.tok, nullptr, sm.go, lane);
     __syncthreads();
 
-    f32x16 P[2][2], dS[2][2];
+    ge_f32x16 P[2][2], dS[2][2];
     st_tiles(sm.k, sm.q, c, hi, P);
     const bool use_mask = g.shift > 0 && (wy == g.nWh - 1 || wx == g.nWw - 1);
     softmax_cols(P, sm.bias, sm.m.meta, c, hi, scale, use_mask);
@@ -459,7 +449,7 @@ __global__ void __launch_bounds__(64) window_attn_bwd_mfma_k(const bf16_t* __res
 
     // dQ^T[d][query] = scale * sum_key K^T[d][key] dS^T[key][query]
     {
-      f32x16 dq[2];
+      ge_f32x16 dq[2];
 #pragma unroll
       for (int qt = 0; qt < 2; ++qt)
 #pragma unroll
@@ -468,7 +458,7 @@ __global__ void __launch_bounds__(64) window_attn_bwd_mfma_k(const bf16_t* __res
       for (int kt = 0; kt < 2; ++kt)
 #pragma unroll
         for (int s = 0; s < 2; ++s) {
-          const bf16x8 a = col8(sm.k, kt * 32 + 16 * s + 4 * hi, c);
+          const ge_bf16x8 a = col8(sm.k, kt * 32 + 16 * s + 4 * hi, c);
           dq[0] = mfma_bf16(a, pack8(dS[kt][0], 8 * s), dq[0]);
           dq[1] = mfma_bf16(a, pack8(dS[kt][1], 8 * s), dq[1]);
         }
@@ -483,7 +473,7 @@ __global__ void __launch_bounds__(64) window_attn_bwd_mfma_k(const bf16_t* __res
     }
 
     // dV^T[d][key] = sum_q dO^T[d][q] P[q][key];  dK^T[d][key] = scale * sum_q Q^T[d][q] dS[q][key]
-    f32x16 dv[2], dk[2];
+    ge_f32x16 dv[2], dk[2];
 #pragma unroll
     for (int kt = 0; kt < 2; ++kt)
 #pragma unroll
@@ -502,8 +492,8 @@ __global__ void __launch_bounds__(64) window_attn_bwd_mfma_k(const bf16_t* __res
         const bf16_t* lhs = pass == 0 ? sm.go : sm.q;
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
-          const bf16x8 a = col8_lin(lhs, qt * 32 + ks * 16 + hi * 8, c);    // X^T[d = c][8 consecutive queries]
-          const bf16x8 b0 = row8(tb, c, ks * 16 + hi * 8), b1 = row8(tb, 32 + c, ks * 16 + hi * 8);
+          const ge_bf16x8 a = col8_lin(lhs, qt * 32 + ks * 16 + hi * 8, c);    // X^T[d = c][8 consecutive queries]
+          const ge_bf16x8 b0 = row8(tb, c, ks * 16 + hi * 8), b1 = row8(tb, 32 + c, ks * 16 + hi * 8);
           if (pass == 0) { dv[0] = mfma_bf16(a, b0, dv[0]); dv[1] = mfma_bf16(a, b1, dv[1]); }
           else { dk[0] = mfma_bf16(a, b0, dk[0]); dk[1] = mfma_bf16(a, b1, dk[1]); }
         }
@@ -555,21 +545,21 @@ __global__ void __launch_bounds__(64) window_attn_bwd_mfma_k(const bf16_t* __res
 // wave-local (half the registers: two waves per SIMD), the four operand tiles are staged by both waves, and only the key-side sums
 // dK / dV = sum over ALL queries meet: each wave sends its partial for the other wave's key tile through LDS (8 KB each way, in the space
 // of the dead operand tiles) and finishes its own key tile.
-__device__ __forceinline__ void st_tiles_q(const bf16_t* A_rows, const bf16_t* B_rows, int qt, int c, int hi, f32x16 acc[2]) {
+__device__ __forceinline__ void st_tiles_q(const bf16_t* A_rows, const bf16_t* B_rows, int qt, int c, int hi, ge_f32x16 acc[2]) {
 #pragma unroll
   for (int kt = 0; kt < 2; ++kt)
 #pragma unroll
     for (int i = 0; i < 16; ++i) acc[kt][i] = 0.f;
 #pragma unroll
   for (int ks = 0; ks < 2; ++ks) {
-    const bf16x8 a0 = row8(A_rows, c, ks * 16 + hi * 8), a1 = row8(A_rows, 32 + c, ks * 16 + hi * 8);
-    const bf16x8 b = row8(B_rows, qt * 32 + c, ks * 16 + hi * 8);
+    const ge_bf16x8 a0 = row8(A_rows, c, ks * 16 + hi * 8), a1 = row8(A_rows, 32 + c, ks * 16 + hi * 8);
+    const ge_bf16x8 b = row8(B_rows, qt * 32 + c, ks * 16 + hi * 8);
     acc[0] = mfma_bf16(a0, b, acc[0]);
     acc[1] = mfma_bf16(a1, b, acc[1]);
   }
 }
 // softmax_cols for one query tile: the lane owns query column qt * 32 + c
-__device__ __forceinline__ void softmax_q(f32x16 acc[2], const float* bias, const uint32_t* meta, int qt, int c, int hi, float scale,
+__device__ __forceinline__ void softmax_q(ge_f32x16 acc[2], const float* bias, const uint32_t* meta, int qt, int c, int hi, float scale,
                                           bool use_mask) {
   const int q = qt * 32 + c;
   const uint32_t mq = meta[q < WT ? q : 0];
@@ -642,7 +632,7 @@ __global__ void __launch_bounds__(128, WA_BWD_WAVES) window_attn_bwd_mfma2_k(con
   for (int i = tid; i < NBIAS; i += 128) { sm.bias[i] = bias_table[i * g.nH + head]; sm.dbias[i] = 0.f; }
   if (tid < 2 * HD) { sm.dpad[0][tid] = 0.f; sm.dpad[1][tid] = 0.f; }
   __syncthreads();
-  f32x16 dB[2];                                              // bias-table gradient of this wave's query tile, summed over the windows
+  ge_f32x16 dB[2];                                              // bias-table gradient of this wave's query tile, summed over the windows
 #pragma unroll
   for (int kt = 0; kt < 2; ++kt)
 #pragma unroll
@@ -687,7 +677,7 @@ __global__ void __launch_bounds__(128, WA_BWD_WAVES) window_attn_bwd_mfma2_k(con
     __syncthreads();
     if (WA_BWD_PREFETCH && bw_next < n_bw) fetch(bw_next, sm.m[cur ^ 1]);
 
-    f32x16 P[2], dS[2];
+    ge_f32x16 P[2], dS[2];
     st_tiles_q(sm.k, sm.q, qt, c, hi, P);
     const bool use_mask = g.shift > 0 && (wy == g.nWh - 1 || wx == g.nWw - 1);
     softmax_q(P, sm.bias, M.meta, qt, c, hi, scale, use_mask);
@@ -710,7 +700,7 @@ __global__ void __launch_bounds__(128, WA_BWD_WAVES) window_attn_bwd_mfma2_k(con
     }
     // dQ^T[d][query] = scale * sum_key K^T[d][key] dS^T[key][query]
     {
-      f32x16 dq;
+      ge_f32x16 dq;
 #pragma unroll
       for (int i = 0; i < 16; ++i) dq[i] = 0.f;
 #pragma unroll
@@ -729,7 +719,7 @@ __global__ void __launch_bounds__(128, WA_BWD_WAVES) window_attn_bwd_mfma2_k(con
     // `qt` (round 6): each wave parks the transposed P (then dS) of ITS query tile in its own dead operand tile (wave 0: v, wave 1: k) and, after
     // the barrier, contracts BOTH waves' tiles against its own key rows — the full sums, no exchange of fp32 partials through LDS (it cost 32
     // writes + 32 reads per lane, a barrier and 32 registers)
-    f32x16 dv, dk;
+    ge_f32x16 dv, dk;
 #pragma unroll
     for (int i = 0; i < 16; ++i) { dv[i] = 0.f; dk[i] = 0.f; }
     bf16_t* tb = qt == 0 ? sm.v : sm.k;                      // [64 keys][RLD], columns 0..31 = the queries of this wave's tile
@@ -746,8 +736,8 @@ __global__ void __launch_bounds__(128, WA_BWD_WAVES) window_attn_bwd_mfma2_k(con
         const bf16_t* tbx = x == 0 ? sm.v : sm.k;
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
-          const bf16x8 a = col8_lin(lhs, x * 32 + ks * 16 + hi * 8, c);    // X^T[d = c][8 consecutive queries of tile x]
-          const bf16x8 bb = row8(tbx, qt * 32 + c, ks * 16 + hi * 8);      // keys of this wave's key tile
+          const ge_bf16x8 a = col8_lin(lhs, x * 32 + ks * 16 + hi * 8, c);    // X^T[d = c][8 consecutive queries of tile x]
+          const ge_bf16x8 bb = row8(tbx, qt * 32 + c, ks * 16 + hi * 8);      // keys of this wave's key tile
           if (pass == 0) dv = mfma_bf16(a, bb, dv);
           else dk = mfma_bf16(a, bb, dk);
         }
