@@ -67,8 +67,7 @@ __global__ void __launch_bounds__(256) aug_resize_k(const float* __restrict__ sr
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
     const int y = (int)(i / Wd), x = (int)(i - (long)y * Wd);
     if (mode == 0) {
-      int ys = (int)floor((double)y * dy), xs = (int)floor((double)x * dx);
-      ys = min(ys, Hs - 1); xs = min(xs, Ws - 1);
+      const int ys = ge_nearest_src(y, dy, Hs), xs = ge_nearest_src(x, dx, Ws);
       for (int c = 0; c < C; ++c) dst[(long)c * n + i] = src[((long)c * Hs + ys) * Ws + xs];
     } else {
       const Lerp ly = ge_lerp(y, Hs, sy, false), lx = ge_lerp(x, Ws, sx, false);
@@ -213,39 +212,16 @@ extern "C" int ge_aug_color_normalize(const float* src, float* dst, int H, int W
 //
 // Area filter: destination cell j covers the source interval [j s, (j + 1) s), s = in / out; source pixel i weighs by its overlap,
 // weights normalised per cell, float64 (imageops._area_weights); rows first, then columns; the uint8 result is rint + clip.
-__device__ __forceinline__ void area_span(int j, int n_in, int n_out, int& i0, int& i1, double& lo, double& hi, double& inv) {
-  const double s = (double)n_in / (double)n_out;
-  lo = (double)j * s; hi = (double)(j + 1) * s;
-  i0 = (int)floor(lo);
-  i1 = (int)ceil(hi);
-  if (i1 > n_in) i1 = n_in;
-  double tot = 0.0;
-  for (int i = i0; i < i1; ++i) tot += fmin(hi, (double)(i + 1)) - fmax(lo, (double)i);
-  inv = 1.0 / tot;
-}
+// (ge_area_span / ge_area_u8_pixel of common.h: the single-frame DDAD front end of infer.hip forms the same averages)
 // src: (H, W, 3) uint8 HWC -> dst: (3, Ho, Wo) planar f32 holding the uint8-rounded averages
 __global__ void __launch_bounds__(256) aug_area_u8_k(const uint8_t* __restrict__ src, float* __restrict__ dst, int H, int W, int Ho, int Wo) {
   const long n = (long)Ho * Wo;
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
     const int y = (int)(i / Wo), x = (int)(i - (long)y * Wo);
-    int y0, y1, x0, x1;
-    double ylo, yhi, yinv, xlo, xhi, xinv;
-    area_span(y, H, Ho, y0, y1, ylo, yhi, yinv);
-    area_span(x, W, Wo, x0, x1, xlo, xhi, xinv);
-    // host order: out[oh, w] = sum_h Wy[oh, h] src[h, w] (float64), then out[oh, ow] = sum_w Wx[ow, w] out[oh, w]
-    double acc[3] = {0.0, 0.0, 0.0};
-    for (int xx = x0; xx < x1; ++xx) {
-      const double wx = (fmin(xhi, (double)(xx + 1)) - fmax(xlo, (double)xx)) * xinv;
-      double col[3] = {0.0, 0.0, 0.0};
-      for (int yy = y0; yy < y1; ++yy) {
-        const double wy = (fmin(yhi, (double)(yy + 1)) - fmax(ylo, (double)yy)) * yinv;
-        const uint8_t* p = src + ((long)yy * W + xx) * 3;
-        col[0] += wy * (double)p[0]; col[1] += wy * (double)p[1]; col[2] += wy * (double)p[2];
-      }
-      acc[0] += wx * col[0]; acc[1] += wx * col[1]; acc[2] += wx * col[2];
-    }
+    float v[3];
+    ge_area_u8_pixel(src, H, W, Ho, Wo, y, x, v);
 #pragma unroll
-    for (int c = 0; c < 3; ++c) dst[c * n + i] = (float)fmin(fmax(rint(acc[c]), 0.0), 255.0);
+    for (int c = 0; c < 3; ++c) dst[c * n + i] = v[c];
   }
 }
 extern "C" int ge_aug_area_u8(const uint8_t* src_hwc, float* dst, int H, int W, int Ho, int Wo, void* stream) {

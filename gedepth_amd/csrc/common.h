@@ -133,6 +133,48 @@ __device__ __forceinline__ Lerp ge_lerp(int dst, int in, float scale, bool align
   return r;
 }
 
+// cv2.INTER_NEAREST as the host evaluates it (imageops.imresize): src = min(floor(dst * in / out), in - 1) in float64; ratio = in / out
+__device__ __forceinline__ int ge_nearest_src(int dst, double ratio, int n_in) {
+  const int s = (int)floor((double)dst * ratio);
+  return s < n_in - 1 ? s : n_in - 1;
+}
+
+// cv2.INTER_AREA when shrinking (imageops._area_weights): destination cell j covers the source interval [j s, (j + 1) s), s = in / out; source
+// pixel i weighs by its overlap, weights normalised per cell, float64.  [i0, i1) = the source pixels the cell touches, inv = 1 / total overlap.
+__device__ __forceinline__ void ge_area_span(int j, int n_in, int n_out, int& i0, int& i1, double& lo, double& hi, double& inv) {
+#pragma clang fp contract(off)
+  const double s = (double)n_in / (double)n_out;
+  lo = (double)j * s; hi = (double)(j + 1) * s;
+  i0 = (int)floor(lo);
+  i1 = (int)ceil(hi);
+  if (i1 > n_in) i1 = n_in;
+  double tot = 0.0;
+  for (int i = i0; i < i1; ++i) tot += fmin(hi, (double)(i + 1)) - fmax(lo, (double)i);
+  inv = 1.0 / tot;
+}
+// One destination pixel (y, x) of the area filter over an (H, W, 3) uint8 HWC image -> the three uint8-rounded averages (rint, clamp) as f32.
+// Host order: out[oh, w] = sum_h Wy[oh, h] src[h, w] (float64), then out[oh, ow] = sum_w Wx[ow, w] out[oh, w].
+__device__ __forceinline__ void ge_area_u8_pixel(const uint8_t* __restrict__ src, int H, int W, int Ho, int Wo, int y, int x, float out[3]) {
+#pragma clang fp contract(off)
+  int y0, y1, x0, x1;
+  double ylo, yhi, yinv, xlo, xhi, xinv;
+  ge_area_span(y, H, Ho, y0, y1, ylo, yhi, yinv);
+  ge_area_span(x, W, Wo, x0, x1, xlo, xhi, xinv);
+  double acc[3] = {0.0, 0.0, 0.0};
+  for (int xx = x0; xx < x1; ++xx) {
+    const double wx = (fmin(xhi, (double)(xx + 1)) - fmax(xlo, (double)xx)) * xinv;
+    double col[3] = {0.0, 0.0, 0.0};
+    for (int yy = y0; yy < y1; ++yy) {
+      const double wy = (fmin(yhi, (double)(yy + 1)) - fmax(ylo, (double)yy)) * yinv;
+      const uint8_t* p = src + ((long)yy * W + xx) * 3;
+      col[0] += wy * (double)p[0]; col[1] += wy * (double)p[1]; col[2] += wy * (double)p[2];
+    }
+    acc[0] += wx * col[0]; acc[1] += wx * col[1]; acc[2] += wx * col[2];
+  }
+#pragma unroll
+  for (int c = 0; c < 3; ++c) out[c] = (float)fmin(fmax(rint(acc[c]), 0.0), 255.0);
+}
+
 // Bilinear backward as a gather: [lo, hi] = the output indices whose taps can touch input index X, i.e. src(o) in (X - 1, X + 1), clipped to
 // [0, out - 1].  floor / ceil of the interval's ends already leave one spare candidate per side against the rounding of the division, and the
 // kernels recompute each candidate's weights exactly, so a spare one contributes 0.  MARGIN widens the range by that many further candidates

@@ -1,5 +1,6 @@
 // Metric sums of the KITTI evaluation protocol on the device (include/gedepth_eval.h; depth/core/evaluation.py `calculate` behind
-// depth/datasets/kitti.py `pre_eval`): one image leaves the GPU as ten f64 numbers.
+// depth/datasets/kitti.py `pre_eval`): one image leaves the GPU as ten f64 numbers.  ge_depth_metrics_resized (include/gedepth_ddad.h) is the
+// same reduction for the DDAD protocol, with the bilinear resize of the prediction to the ground truth folded into the pass.
 //
 // The discontinuous part is numpy's float32 arithmetic, bit for bit: gt = (float)raw / depth_scale, the mask gt > min && gt < max, and
 // ratio = maximum(gt / pred, pred / gt) < 1.25^p with true IEEE divisions (no reciprocal, no contraction) and a NaN-propagating maximum.
@@ -12,6 +13,7 @@
 #pragma clang fp contract(off)
 #include "common.h"
 #include "../../include/gedepth_eval.h"
+#include "../../include/gedepth_ddad.h"
 
 #define GE_EVAL_THREADS 256
 #define GE_EVAL_GROUPS 2           // groups of four pixels per lane before the grid-stride loop goes round again
@@ -20,9 +22,9 @@
 
 struct EvalArgs { int W, top, left, Hc, Wc, r0, r1, c0, c1; float scale, lo, hi; };
 
-__device__ __forceinline__ void metric_pixel(float p, uint16_t raw, bool inside, const EvalArgs& a, double acc[GE_EVAL_SUMS]) {
-  const float gt = (float)raw / a.scale;
-  if (!(inside && gt > a.lo && gt < a.hi)) return;
+// One pixel: `gt` in metres (f32), `inside` = it lies in the protocol's rectangle; it counts when also lo < gt < hi.
+__device__ __forceinline__ void metric_pixel(float p, float gt, bool inside, float lo, float hi, double acc[GE_EVAL_SUMS]) {
+  if (!(inside && gt > lo && gt < hi)) return;
   const float q0 = gt / p, q1 = p / gt;
   const float ratio = (q0 > q1 || q0 != q0) ? q0 : q1;               // numpy.maximum: NaN wins
   acc[0] += 1.0;
@@ -38,6 +40,24 @@ __device__ __forceinline__ void metric_pixel(float p, uint16_t raw, bool inside,
   acc[7] += l;
   acc[8] += l * l;
   acc[9] += fabs(log10(g) - log10(q));
+}
+
+// lane sums -> wave (shuffles) -> workgroup (LDS across the four waves) -> partials[block]
+__device__ __forceinline__ void metrics_block_fold(double acc[GE_EVAL_SUMS], double (*red)[GE_EVAL_SUMS], double* __restrict__ partials) {
+#pragma unroll
+  for (int k = 0; k < GE_EVAL_SUMS; ++k)
+    for (int s = GE_WAVE / 2; s > 0; s >>= 1) acc[k] += __shfl_down(acc[k], s, GE_WAVE);
+  const int wave = threadIdx.x / GE_WAVE, lane = threadIdx.x % GE_WAVE;
+  if (lane == 0) {
+#pragma unroll
+    for (int k = 0; k < GE_EVAL_SUMS; ++k) red[wave][k] = acc[k];
+  }
+  __syncthreads();
+  if (threadIdx.x < GE_EVAL_SUMS) {
+    double s = red[0][threadIdx.x];
+    for (int w = 1; w < GE_EVAL_THREADS / GE_WAVE; ++w) s += red[w][threadIdx.x];
+    partials[(long)blockIdx.x * GE_EVAL_SUMS + threadIdx.x] = s;
+  }
 }
 
 // PV: pred is 16-byte aligned and Wc % 4 == 0 (one float4 per group).  GV (only with PV): every group's four ground-truth values are
@@ -73,22 +93,60 @@ __global__ void __launch_bounds__(GE_EVAL_THREADS) metrics_partial_k(const float
       for (int k = 0; k < 4; ++k) raw[k] = c + k < a.Wc ? gs[k] : (uint16_t)0;
     }
 #pragma unroll
-    for (int k = 0; k < 4; ++k) metric_pixel(p[k], raw[k], c + k >= a.c0 && c + k < a.c1, a, acc);    // c1 <= Wc covers the row's tail
+    for (int k = 0; k < 4; ++k)                                                   // gt = (float)raw / depth_scale; c1 <= Wc covers the row's tail
+      metric_pixel(p[k], (float)raw[k] / a.scale, c + k >= a.c0 && c + k < a.c1, a.lo, a.hi, acc);
   }
+  metrics_block_fold(acc, red, partials);
+}
+
+// DDAD protocol (depth/datasets/ddad.py pre_eval): the (h, w) prediction is resized bilinearly, align_corners = True, to the (H, W) ground
+// truth, and every pixel with lo < gt < hi counts.  The kernel walks the ground truth in groups of four pixels; a group without a counted
+// pixel loads nothing of the prediction (DDAD: ~1 % of 1216 x 1936 is valid), a counted pixel gathers its four taps and never stores the
+// resized value.  Source index and weights are ge_scale(.., true) / ge_lerp(.., true) of common.h, whose align-corners branch computes exactly
+// scale = (float)(h - 1) / (float)(H - 1) (0 when H == 1), src = scale * (float)Y, i0 = (int)src, i1 = min(i0 + 1, h - 1), w1 = src - (float)i0,
+// w0 = 1.f - w1 (its clamp of i0 to h - 1 never acts: src < h); the blend is the expression of aug_resize_k, ATen's
+// wy0 * (wx0 * v00 + wx1 * v01) + wy1 * (wx0 * v10 + wx1 * v11), in f32 without contraction.
+// GV: gt is 16-byte aligned and W % 4 == 0 (one float4 per group); otherwise element loads, each one bounds-checked against W.
+struct ResizedArgs { int h, w, H, W; float lo, hi; };
+template <bool GV>
+__global__ void __launch_bounds__(GE_EVAL_THREADS) metrics_resized_partial_k(const float* __restrict__ pred, const float* __restrict__ gt,
+                                                                             ResizedArgs a, double* __restrict__ partials) {
+  __shared__ double red[GE_EVAL_THREADS / GE_WAVE][GE_EVAL_SUMS];
+  double acc[GE_EVAL_SUMS];
 #pragma unroll
-  for (int k = 0; k < GE_EVAL_SUMS; ++k)
-    for (int s = GE_WAVE / 2; s > 0; s >>= 1) acc[k] += __shfl_down(acc[k], s, GE_WAVE);
-  const int wave = threadIdx.x / GE_WAVE, lane = threadIdx.x % GE_WAVE;
-  if (lane == 0) {
+  for (int k = 0; k < GE_EVAL_SUMS; ++k) acc[k] = 0.0;
+  const float sy = ge_scale(a.h, a.H, true), sx = ge_scale(a.w, a.W, true);
+  const int G = (a.W + 3) >> 2;                                       // groups per ground-truth row
+  const long items = (long)a.H * G;
+  for (long it = (long)blockIdx.x * GE_EVAL_THREADS + threadIdx.x; it < items; it += (long)gridDim.x * GE_EVAL_THREADS) {
+    const int r = (int)(it / G), c = 4 * (int)(it - (long)r * G);
+    const float* gs = gt + (long)r * a.W + c;
+    float g[4];
+    if (GV) {
+      const float4 t = *(const float4*)gs;
+      g[0] = t.x; g[1] = t.y; g[2] = t.z; g[3] = t.w;
+    } else {
 #pragma unroll
-    for (int k = 0; k < GE_EVAL_SUMS; ++k) red[wave][k] = acc[k];
+      for (int k = 0; k < 4; ++k) g[k] = c + k < a.W ? gs[k] : 0.f;
+    }
+    bool any = false;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) any = any || (c + k < a.W && g[k] > a.lo && g[k] < a.hi);
+    if (!any) continue;                                               // no counted pixel in this group: no prediction loads
+    const Lerp ly = ge_lerp(r, a.h, sy, true);
+    const float* p0 = pred + (long)ly.i0 * a.w;
+    const float* p1 = pred + (long)ly.i1 * a.w;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const bool inside = c + k < a.W;
+      if (!(inside && g[k] > a.lo && g[k] < a.hi)) continue;
+      const Lerp lx = ge_lerp(c + k, a.w, sx, true);
+      const float v00 = p0[lx.i0], v01 = p0[lx.i1], v10 = p1[lx.i0], v11 = p1[lx.i1];
+      const float p = ly.w0 * (lx.w0 * v00 + lx.w1 * v01) + ly.w1 * (lx.w0 * v10 + lx.w1 * v11);
+      metric_pixel(p, g[k], inside, a.lo, a.hi, acc);
+    }
   }
-  __syncthreads();
-  if (threadIdx.x < GE_EVAL_SUMS) {
-    double s = red[0][threadIdx.x];
-    for (int w = 1; w < GE_EVAL_THREADS / GE_WAVE; ++w) s += red[w][threadIdx.x];
-    partials[(long)blockIdx.x * GE_EVAL_SUMS + threadIdx.x] = s;
-  }
+  metrics_block_fold(acc, red, partials);
 }
 
 __global__ void __launch_bounds__(GE_WAVE) metrics_fold_k(const double* __restrict__ partials, int blocks, double* __restrict__ sums) {
@@ -127,6 +185,26 @@ extern "C" int ge_depth_metrics(const float* pred, const uint16_t* gt_raw, int H
     metrics_partial_k<true, false><<<blocks, GE_EVAL_THREADS, 0, s>>>(pred, gt_raw, a, partials);
   else
     metrics_partial_k<false, false><<<blocks, GE_EVAL_THREADS, 0, s>>>(pred, gt_raw, a, partials);
+  GE_LAUNCH_CHECK();
+  metrics_fold_k<<<1, GE_WAVE, 0, s>>>(partials, (int)blocks, sums);
+  GE_LAUNCH_CHECK();
+  return GE_OK;
+}
+
+extern "C" size_t ge_depth_metrics_resized_workspace(int H, int W) { return ge_depth_metrics_workspace(H, W); }
+
+extern "C" int ge_depth_metrics_resized(const float* pred, int h, int w, const float* gt, int H, int W, float min_depth, float max_depth,
+                                        double* partials, double* sums, void* stream) {
+  if (!pred || !gt || !partials || !sums || h <= 0 || w <= 0 || H <= 0 || W <= 0) return GE_ERR_BAD_ARG;
+  if (((uintptr_t)pred & 3) || ((uintptr_t)gt & 3) || ((uintptr_t)partials & 7) || ((uintptr_t)sums & 7)) return GE_ERR_UNSUPPORTED;
+  hipStream_t s = ge_stream(stream);
+  ResizedArgs a;
+  a.h = h; a.w = w; a.H = H; a.W = W; a.lo = min_depth; a.hi = max_depth;
+  const unsigned blocks = metrics_blocks(H, W);
+  if (((uintptr_t)gt & 15) == 0 && (W & 3) == 0)
+    metrics_resized_partial_k<true><<<blocks, GE_EVAL_THREADS, 0, s>>>(pred, gt, a, partials);
+  else
+    metrics_resized_partial_k<false><<<blocks, GE_EVAL_THREADS, 0, s>>>(pred, gt, a, partials);
   GE_LAUNCH_CHECK();
   metrics_fold_k<<<1, GE_WAVE, 0, s>>>(partials, (int)blocks, sums);
   GE_LAUNCH_CHECK();

@@ -12,6 +12,12 @@ MultiScaleFlipAug(RandomFlip, Normalize) -> ``aug_test`` — on the device, thro
 
 After two eager calls, steps 3-4 are captured in a hipGraph and replayed for every later frame.  KB crop makes the forward's shape
 constant, so frames of every KITTI size share one graph; only the front end's arguments change, and it stays outside the graph.
+
+A DDAD config (``front_spec(cfg)['protocol'] == 'ddad'``) takes LoadDDADImageFromFile(USEPE, USE_DYNAMIC_PE) -> DDADResize(shape, depth=False)
+-> MultiScaleFlipAug(flip=False, Normalize) -> ``simple_test`` instead: ``ge_infer_front_ddad`` writes the one view into a static
+(1, 5, Hd, Wd) buffer, the camera's height goes into a static (1,) tensor (the adaptive ground embedding reads it through a device pointer,
+so a replayed graph follows it) and the forward's (1, Hd, Wd) map is the output.  The frame's camera names the ground depth
+(``<pe_root>/<camera>/ddad_pe.npz``) and the height: the ``camera=`` argument, else the image path's parent directory.
 """
 import os.path as osp
 
@@ -24,11 +30,14 @@ from ...mmrt.checkpoint import load_checkpoint
 from ...mmrt.config import Config
 from ..models import build_depther
 
-__all__ = ['init_depther', 'inference_depther', 'DepthInferencer', 'kitti_front_spec']
+__all__ = ['init_depther', 'inference_depther', 'DepthInferencer', 'kitti_front_spec', 'ddad_front_spec', 'front_spec']
 
 # test-time transforms of MultiScaleFlipAug the device front end restates (ImageToTensor / Collect are layout only)
 _FRONT_TRANSFORMS = ('RandomFlip', 'Normalize', 'ImageToTensor', 'Collect')
 _PROTOCOL = 'LoadImageFromFile(USEPE) -> KBCrop -> MultiScaleFlipAug(RandomFlip, Normalize)'
+_DDAD_TRANSFORMS = ('Normalize', 'ImageToTensor', 'Collect')
+_DDAD_PROTOCOL = ('LoadDDADImageFromFile(USEPE, USE_DYNAMIC_PE) -> DDADResize(shape, depth=False) -> '
+                  'MultiScaleFlipAug(flip=False, Normalize)')
 
 
 def init_depther(config, checkpoint=None, device='cuda:0'):
@@ -87,6 +96,72 @@ def kitti_front_spec(cfg):
                 pe_max=float(load.get('pe_max', 200)), pe_root=load.get('pe_root'))
 
 
+def ddad_front_spec(cfg):
+    """The parameters of the configured DDAD test pipeline the device front end needs; ``NotImplementedError``, naming the step, for
+    anything but ``_DDAD_PROTOCOL``."""
+    pipeline = cfg.data.test.pipeline
+    types = [t['type'] for t in pipeline]
+    other = [t for t in types if t not in ('LoadDDADImageFromFile', 'DDADResize', 'MultiScaleFlipAug')]
+    if other:
+        raise NotImplementedError(f'test pipeline step(s) {", ".join(other)}: no DDAD device front end for them (it implements '
+                                  f'{_DDAD_PROTOCOL})')
+    if types != ['LoadDDADImageFromFile', 'DDADResize', 'MultiScaleFlipAug']:
+        raise NotImplementedError(f'test pipeline {types}: the DDAD device front end implements {_DDAD_PROTOCOL} only')
+    load, resize, aug = pipeline
+    # without USE_DYNAMIC_PE the host builds a 4-channel image whose ground depth DDADResize area-averages, and no camera height
+    if not load.get('USEPE', False) or not load.get('USE_DYNAMIC_PE', False):
+        raise NotImplementedError('LoadDDADImageFromFile without USEPE=True, USE_DYNAMIC_PE=True: no device front end for it')
+    if load.get('to_float32', False):
+        raise NotImplementedError('LoadDDADImageFromFile(to_float32=True): no device front end for it')
+    if resize.get('depth', True):
+        raise NotImplementedError('DDADResize(depth=True): the test protocol resizes no depth; no device front end for it')
+    inner = [t['type'] for t in aug['transforms']]
+    for t in inner:
+        if t not in _DDAD_TRANSFORMS:
+            raise NotImplementedError(f'MultiScaleFlipAug transform {t}: no DDAD device front end for it ({_DDAD_PROTOCOL})')
+    norm = next((t for t in aug['transforms'] if t['type'] == 'Normalize'), None)
+    if norm is None:
+        raise NotImplementedError(f'MultiScaleFlipAug without Normalize: not the DDAD protocol {_DDAD_PROTOCOL}')
+    if aug.get('flip', False):
+        raise NotImplementedError('MultiScaleFlipAug(flip=True): no flip test-time augmentation on the DDAD device front end')
+    if aug.get('img_ratios') is not None:
+        raise NotImplementedError('MultiScaleFlipAug(img_ratios=...): no multi-scale test-time augmentation on the DDAD device front end')
+    shape = tuple(int(v) for v in resize['shape'])
+    return dict(protocol='ddad', height=shape[0], width=shape[1], views=1,
+                mean=[float(np.float32(v)) for v in norm['mean']], std=[float(np.float32(v)) for v in norm['std']],
+                to_rgb=bool(norm.get('to_rgb', True)), depth_scale=float(norm.get('depth_scale', 200)),
+                pe_max=250.0,                                          # LoadDDADImageFromFile's constant
+                pe_root=load.get('pe_root') if load.get('pe_root') is not None else osp.join('data', 'DDAD', 'pe_public_debug'))
+
+
+def front_spec(cfg):
+    """``ddad_front_spec`` for a pipeline with a DDAD step, else ``kitti_front_spec``, with ``protocol`` = 'ddad' / 'kitti'."""
+    types = [t['type'] for t in cfg.data.test.pipeline]
+    if 'LoadDDADImageFromFile' in types or 'DDADResize' in types:
+        return ddad_front_spec(cfg)
+    return dict(kitti_front_spec(cfg), protocol='kitti')
+
+
+def _ddad_cameras():
+    from ..datasets.pipelines.loading import _DDAD_CAMERA_HEIGHT
+    return _DDAD_CAMERA_HEIGHT
+
+
+def _ddad_camera(camera, path):
+    """The frame's camera: ``camera``, else the image path's parent directory (as LoadDDADCamIntrinsic takes it); None when neither names
+    one.  A ``camera`` argument that is not a DDAD camera with a known height is a ``ValueError``."""
+    known = _ddad_cameras()
+    if camera is not None:
+        if camera not in known:
+            raise ValueError(f'camera {camera!r}: the cameras with a known height are {", ".join(sorted(known))}')
+        return camera
+    if isinstance(path, str):
+        parent = osp.basename(osp.dirname(path))
+        if parent in known:
+            return parent
+    return None
+
+
 def _img_prefix(cfg):
     test = cfg.data.test
     img_dir, root = test.get('img_dir'), test.get('data_root')
@@ -136,12 +211,15 @@ class DepthInferencer:
         cfg = getattr(model, 'cfg', None)
         if cfg is None:
             raise ValueError('model.cfg is missing: build the model with init_depther (or set model.cfg to its Config)')
-        self.spec = kitti_front_spec(cfg)
+        self.spec = front_spec(cfg)
+        self.ddad = self.spec['protocol'] == 'ddad'
         self.prefix = _img_prefix(cfg)
         self.device = next(model.parameters()).device
         s = self.spec
         self.static_in = torch.empty(s['views'], 5, s['height'], s['width'], device=self.device, dtype=torch.float32)
         self.static_out = torch.empty(1, s['height'], s['width'], device=self.device, dtype=torch.float32)
+        # DDAD: the camera height, filled per frame outside the graph; ground_embed_adaptive reads it through its device pointer
+        self.static_height = torch.zeros(1, device=self.device, dtype=torch.float32) if self.ddad else None
         self.stream = torch.cuda.Stream(self.device)
         self._pinned = None
         self._uploaded = None                    # event after the last copy out of ``_pinned``
@@ -151,6 +229,7 @@ class DepthInferencer:
     def reset(self):
         """Drop every captured graph (and its memory pool) and the warm-up counts."""
         self.graphs, self.calls, self.captures = {}, {}, 0
+        self.frame_size = None                   # DDAD: the (H, W) of the frames this engine has taken
 
     # ---- ground depth
     def _cache(self, key, make):
@@ -183,20 +262,36 @@ class DepthInferencer:
             return torch.from_numpy(a).to(self.device).contiguous()
         return self._cache(('npy', npy, H, W), load)
 
+    def ground_depth_ddad(self, camera, H, W, pe=None):
+        """Raw (H, W) f32 ground depth of ``camera`` on the device: ``pe``, else ``<pe_root>/<camera>/ddad_pe.npz['pe']`` (once per camera)."""
+        if pe is not None:
+            return self.ground_depth(H, W, pe=pe)
+        npz = osp.join(self.spec['pe_root'], camera, 'ddad_pe.npz')
+
+        def load():
+            a = np.load(npz)['pe'].astype(np.float32)
+            if a.shape != (H, W):
+                raise ValueError(f'{npz} has shape {a.shape}, the frame is {(H, W)}')
+            return torch.from_numpy(a).to(self.device).contiguous()
+        return self._cache(('ddad', npz, H, W), load)
+
     # ---- one frame
     def _key(self):
         return (self.bf16,) + tuple(m.kernel_variant for m in self.model.modules() if hasattr(m, 'kernel_variant'))
 
     def _metas(self, filename, shape):
         s = self.spec
-        kb = (s['height'], s['width'], 5)
+        kb = tuple(shape) + (5,) if self.ddad else (s['height'], s['width'], 5)     # LoadDDADImageFromFile: ori_shape = the frame's
         norm = dict(mean=np.float32(s['mean']), std=np.float32(s['std']), to_rgb=s['to_rgb'])
         return [dict(filename=filename, ori_filename=filename, ori_shape=kb, img_shape=tuple(shape) + (5,), pad_shape=tuple(shape) + (5,),
                      scale_factor=1.0, flip=bool(v), flip_direction='horizontal', img_norm_cfg=norm) for v in range(s['views'])]
 
     def _body(self, metas):
         with torch.no_grad(), torch.autocast('cuda', dtype=torch.bfloat16, enabled=self.bf16):
-            pred = self.model.encode_decode(self.static_in, metas, rescale=True)
+            if self.ddad:                        # no ``test`` key: _height takes the tensor as it is
+                pred = self.model.encode_decode(self.static_in, metas, rescale=True, height=self.static_height)
+            else:
+                pred = self.model.encode_decode(self.static_in, metas, rescale=True)
         pred = pred.float().contiguous()
         if self.spec['views'] == 2:
             K.tta_merge(pred, self.static_out)
@@ -217,23 +312,41 @@ class DepthInferencer:
         self._uploaded.record()
         return dev
 
-    def __call__(self, img, pe=None, calib=None, cam_height=1.65, graph=True, to_host=True):
-        """One frame -> its (1, 352, 1216) float32 map: a fresh host array, or with ``to_host=False`` the static device buffer
-        ``static_out`` itself, without synchronising: valid until the next call, and ordered on ``self.stream`` (the caller's current
-        stream waits for it, as always)."""
+    def __call__(self, img, pe=None, calib=None, cam_height=1.65, graph=True, to_host=True, camera=None):
+        """One frame -> its (1, 352, 1216) float32 map (DDAD: (1, Hd, Wd) of DDADResize's shape): a fresh host array, or with
+        ``to_host=False`` the static device buffer ``static_out`` itself, without synchronising: valid until the next call, and ordered on
+        ``self.stream`` (the caller's current stream waits for it, as always).  ``camera`` (DDAD): the frame's camera, else the image
+        path's parent directory; ``calib`` / ``cam_height`` belong to the KITTI protocol."""
         bgr = _decode(img)
         H, W = bgr.shape[:2]
         s = self.spec
-        if H < s['height'] or W < s['width']:
+        cam = None
+        if self.ddad:
+            cam = _ddad_camera(camera, img if isinstance(img, str) else None)
+            if cam is None:
+                raise ValueError(f'no camera for this frame: pass camera= (one of {", ".join(sorted(_ddad_cameras()))}) or an image path '
+                                 'whose parent directory is the camera name')
+            if H < s['height'] or W < s['width']:
+                raise ValueError(f'frame {(H, W)} is smaller than DDADResize\'s shape {(s["height"], s["width"])}')
+            if self.frame_size is not None and self.frame_size != (H, W):
+                raise ValueError(f'frame {(H, W)}: this engine takes frames of {self.frame_size} (reset() to change)')
+            self.frame_size = (H, W)
+        elif H < s['height'] or W < s['width']:
             raise ValueError(f'frame {(H, W)} is smaller than the KB crop {(s["height"], s["width"])}')
-        top, left = int(H - s['height']), int((W - s['width']) / 2)               # KBCrop
         metas = self._metas(img if isinstance(img, str) else None, (H, W))
         cur = torch.cuda.current_stream(self.device)
         self.stream.wait_stream(cur)
         with torch.cuda.stream(self.stream):
-            raw = self.ground_depth(H, W, img if isinstance(img, str) else None, pe, calib, cam_height)
-            dev = self.upload(bgr)
-            K.infer_front(dev, raw, self.static_in, top, left, s['mean'], s['std'], s['to_rgb'], s['pe_max'], s['depth_scale'])
+            if self.ddad:
+                raw = self.ground_depth_ddad(cam, H, W, pe)
+                dev = self.upload(bgr)
+                K.infer_front_ddad(dev, raw, self.static_in, s['mean'], s['std'], s['to_rgb'], s['pe_max'], s['depth_scale'])
+                self.static_height.fill_(float(_ddad_cameras()[cam]))
+            else:
+                top, left = int(H - s['height']), int((W - s['width']) / 2)       # KBCrop
+                raw = self.ground_depth(H, W, img if isinstance(img, str) else None, pe, calib, cam_height)
+                dev = self.upload(bgr)
+                K.infer_front(dev, raw, self.static_in, top, left, s['mean'], s['std'], s['to_rgb'], s['pe_max'], s['depth_scale'])
             key = self._key()
             g = self.graphs.get(key) if graph else None
             if graph and g is None and self.calls.get(key, 0) >= self.WARMUP:
@@ -254,13 +367,17 @@ class DepthInferencer:
         return out
 
 
-def inference_depther(model, img, pe=None, calib=None, cam_height=1.65, bf16=False, graph=True):
+def inference_depther(model, img, pe=None, calib=None, cam_height=1.65, bf16=False, graph=True, camera=None):
     """Depth for each frame of ``img`` (a path, an (H, W, 3) uint8 BGR array, or a list of these): a list with one (1, 352, 1216)
     float32 array per frame — what ``model(return_loss=False, rescale=True, **data)`` returns for that frame through the config's test
     pipeline.  The raw (H, W) ground depth at frame size comes from ``pe`` (array or device tensor; a list: one per frame), else from
     ``calib=(calib_cam_to_cam.txt, calib_velo_to_cam.txt)`` with ``cam_height`` (computed on the device, cached per calibration and
     size), else from ``<date>/pe/pe_165.npy`` of an image path inside ``cfg.data.test.data_root/img_dir``.  ``bf16``: the forward under
-    bf16 autocast.  ``graph``: replay a captured hipGraph of forward + merge after two eager calls (``DepthInferencer``)."""
+    bf16 autocast.  ``graph``: replay a captured hipGraph of forward + merge after two eager calls (``DepthInferencer``).
+
+    With a DDAD config every frame needs its camera: ``camera`` (a name, or a list with one per frame), else the image path's parent
+    directory.  The result is one (1, Hd, Wd) map per frame at DDADResize's shape — what ``simple_test`` returns; the ground depth comes
+    from ``pe``, else from ``<pe_root>/<camera>/ddad_pe.npz``.  Without a camera: ``NotImplementedError``."""
     imgs = img if isinstance(img, list) else [img]
     pes = pe if isinstance(pe, list) else [pe] * len(imgs)
     if len(pes) != len(imgs):
@@ -268,12 +385,21 @@ def inference_depther(model, img, pe=None, calib=None, cam_height=1.65, bf16=Fal
     cfg = getattr(model, 'cfg', None)
     if cfg is None:
         raise ValueError('model.cfg is missing: build the model with init_depther (or set model.cfg to its Config)')
-    spec, prefix = kitti_front_spec(cfg), _img_prefix(cfg)                    # argument errors before any device work
-    if calib is None and any(p is None and _pe_file(spec, prefix, i) is None for i, p in zip(imgs, pes)):
+    spec, prefix = front_spec(cfg), _img_prefix(cfg)                          # argument errors before any device work
+    cams = camera if isinstance(camera, list) else [camera] * len(imgs)
+    if len(cams) != len(imgs):
+        raise ValueError(f'{len(cams)} cameras for {len(imgs)} frames')
+    if spec['protocol'] == 'ddad':
+        cams = [_ddad_camera(c, i) for c, i in zip(cams, imgs)]
+        if any(c is None for c in cams):
+            raise NotImplementedError('test pipeline step(s) LoadDDADImageFromFile, DDADResize: the device front end for them needs each '
+                                      f'frame\'s camera (its ground depth and its height): pass camera= (one of '
+                                      f'{", ".join(sorted(_ddad_cameras()))}) or an image path whose parent directory is the camera name')
+    elif calib is None and any(p is None and _pe_file(spec, prefix, i) is None for i, p in zip(imgs, pes)):
         raise ValueError(_NO_PE)
     engines = model.__dict__.setdefault('_ge_inferencers', {})
     bf16 = bool(bf16)
     if bf16 not in engines or engines[bf16].spec != spec or engines[bf16].prefix != prefix:     # model.cfg replaced: a new engine
         engines[bf16] = DepthInferencer(model, bf16)
     eng = engines[bf16]
-    return [eng(i, p, calib, cam_height, graph) for i, p in zip(imgs, pes)]
+    return [eng(i, p, calib, cam_height, graph, camera=c) for i, p, c in zip(imgs, pes, cams)]

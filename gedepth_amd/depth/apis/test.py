@@ -2,9 +2,12 @@
 keep the predictions or reduce them to per-image metric tuples on the fly (``pre_eval``).  With ``show`` / ``out_dir`` each image's map
 also goes through the model's ``show_result`` (a colorized image, or the raw ``.npy`` under ``format_only``).
 
-``device_eval=True`` (opt-in, KITTI protocol only) evaluates where the prediction is: every frame goes through the graphed flip-TTA engine
-(apis/inference.py) and ``dataset.pre_eval_device`` reduces its map to ten float64 sums on the engine's stream (csrc/eval.hip); the whole
-split comes back in one copy at the end."""
+``device_eval=True`` (opt-in; the KITTI and the DDAD protocol) evaluates where the prediction is: every frame goes through the graphed
+engine (apis/inference.py: flip-TTA for KITTI, the single view of DDADResize's shape for DDAD) and ``dataset.pre_eval_device`` reduces its
+map to ten float64 sums on the engine's stream (csrc/eval.hip); the whole split comes back in one copy at the end.  For DDAD the kernel
+resamples the prediction at the ground-truth pixels in float32 (include/gedepth_ddad.h), which is not bit-equal to the host's
+``F.interpolate``: the largest relative difference measured is 3.4e-7, so a threshold count can move by the pixels whose ratio lies that
+close to 1.25^p.  ``show`` / ``out_dir`` and ``mask_pe`` are not covered.  Speed: not measured."""
 import os.path as osp
 
 import torch
@@ -48,22 +51,29 @@ def _show_batch(model, data, result_depth, show, out_dir, format_only):
 def _device_eval(model, data_loader, pre_eval, format_only, show, out_dir):
     """The ``device_eval`` loop of ``single_gpu_test``: the list of metric tuples ``pre_eval`` yields, in the sampler's order."""
     from ..core.evaluation import metrics_from_sums
-    from .inference import DepthInferencer, _img_prefix, kitti_front_spec
+    from ..datasets.ddad import DDADDataset
+    from ..datasets.kitti import KITTIDataset
+    from .inference import DepthInferencer, _img_prefix, front_spec
     dataset = data_loader.dataset
     if not pre_eval or format_only:
         raise NotImplementedError('device_eval reduces every map to metric sums on the device: it needs pre_eval=True and no format_only')
     if show or out_dir:
         raise NotImplementedError('device_eval with show / out_dir: the depth maps never reach the host')
-    if not hasattr(dataset, 'pre_eval_device'):
-        raise NotImplementedError(f'device_eval: {type(dataset).__name__} has no pre_eval_device (only the KITTI protocol is evaluated '
-                                  'on the device)')
+    name = type(dataset).__name__
+    wants = 'ddad' if isinstance(dataset, DDADDataset) else 'kitti' if isinstance(dataset, KITTIDataset) else None
+    if wants is None:
+        raise NotImplementedError(f'device_eval: {name} has no pre_eval_device (the KITTI and the DDAD protocol are evaluated on the device)')
     depther = getattr(model, 'module', model)
     cfg = getattr(depther, 'cfg', None)
     if cfg is None:
         raise NotImplementedError('device_eval: model.cfg is missing (the engine reads the test protocol from it): build the model with '
                                   'init_depther or set model.cfg to its Config')
-    spec, prefix = kitti_front_spec(cfg), _img_prefix(cfg)               # NotImplementedError names what the device front end lacks
-    if (spec['height'], spec['width']) != (352, 1216):
+    spec, prefix = front_spec(cfg), _img_prefix(cfg)                     # NotImplementedError names what the device front end lacks
+    if spec['protocol'] != wants:                                        # before any attribute of the dataset is touched
+        raise NotImplementedError(f'device_eval: {name} is evaluated by the {wants} protocol, the model\'s test pipeline is the '
+                                  f'{spec["protocol"]} protocol')
+    ddad = wants == 'ddad'
+    if not ddad and (spec['height'], spec['width']) != (352, 1216):
         raise NotImplementedError(f'device_eval: KBCrop {(spec["height"], spec["width"])}, the evaluation protocol crops (352, 1216)')
     bf16 = bool(torch.is_autocast_enabled('cuda') and torch.get_autocast_dtype('cuda') == torch.bfloat16)      # what the caller asks for
     engines = depther.__dict__.setdefault('_ge_inferencers', {})
@@ -71,9 +81,19 @@ def _device_eval(model, data_loader, pre_eval, format_only, show, out_dir):
         engines[bf16] = DepthInferencer(depther, bf16)
     eng = engines[bf16]
     indices = [i for batch in data_loader.batch_sampler for i in batch]
+    if ddad:                                         # every frame's camera needs a known height: found before the first frame runs
+        from .inference import _ddad_cameras
+        cams = {dataset.img_infos[i]['ann']['depth_map'].split('/')[-2] for i in indices}
+        if cams - set(_ddad_cameras()):
+            raise ValueError(f'device_eval: the split holds frames of {", ".join(sorted(cams - set(_ddad_cameras())))}; the cameras with '
+                             f'a known height are {", ".join(sorted(_ddad_cameras()))} (set the dataset\'s cameras to these)')
     sums = torch.empty(max(len(indices), 1), 10, device=eng.device, dtype=torch.float64)
     for row, i in enumerate(indices):
-        pred = eng(osp.join(dataset.img_dir, dataset.img_infos[i]['filename']), to_host=False)
+        info = dataset.img_infos[i]
+        if ddad:                                     # the split holds full paths; the camera as LoadDDADImageFromFile takes it
+            pred = eng(info['filename'], to_host=False, camera=info['ann']['depth_map'].split('/')[-2])
+        else:
+            pred = eng(osp.join(dataset.img_dir, info['filename']), to_host=False)
         with torch.cuda.stream(eng.stream):
             dataset.pre_eval_device(pred, i, sums[row])
     with torch.cuda.stream(eng.stream):
@@ -86,7 +106,7 @@ def single_gpu_test(model, data_loader, pre_eval=False, format_only=False, forma
                     out_dir=None, device_eval=False):
     """Returns a list with one entry per image: the metric tuple (``pre_eval``) or the ``(1, H, W)`` depth map.  ``show`` / ``out_dir``:
     ``show_result`` of every image's map, written to ``out_dir/replace_str(ori_filename)`` (``format_only``: the raw map as
-    ``out_dir/<ori_filename without extension>.npy``).  ``device_eval`` (with ``pre_eval``, KITTI protocol): the module docstring."""
+    ``out_dir/<ori_filename without extension>.npy``).  ``device_eval`` (with ``pre_eval``; KITTI or DDAD protocol): the module docstring."""
     model.eval()
     if device_eval:
         return _device_eval(model, data_loader, pre_eval, format_only, show, out_dir)

@@ -88,6 +88,34 @@ class DDADDataset(Dataset):
             out_preds.append(pred)
         return out_metrics, out_preds
 
+    def pre_eval_device(self, pred, index, sums_row):
+        """``pre_eval`` of one image where the prediction already is: ``pred`` a CUDA ``(1, Hd, Wd)`` float32 map, ``sums_row`` one row of
+        a device ``(N, 10)`` float64 buffer that receives the image's metric sums (``core.metrics_from_sums`` makes the tuple of
+        ``pre_eval`` from it).  The ground truth goes up as float32 through a reused pinned buffer on the current stream; the kernel
+        resamples the prediction at the ground-truth pixels that count (bilinear, align_corners=True, in float32: not bit-equal to
+        ``F.interpolate`` on the CPU, see include/gedepth_ddad.h) and reduces in the same pass, so the resized map is never written.
+        Does not synchronise: the row is valid once the current stream has reached this point."""
+        from ... import kernels as K
+        if not (torch.is_tensor(pred) and pred.is_cuda and pred.dim() == 3 and pred.shape[0] == 1 and pred.dtype == torch.float32):
+            raise TypeError('pre_eval_device takes a CUDA (1, Hd, Wd) float32 prediction, got '
+                            f'{(tuple(pred.shape), pred.dtype, pred.device.type) if torch.is_tensor(pred) else type(pred)}')
+        path = self.img_infos[index]['ann']['depth_map']
+        gt = np.load(path)['depth']
+        if gt.ndim != 2:
+            raise TypeError(f'{path}: the ground truth must be a 2-D depth array, got shape {gt.shape}')
+        h, w = gt.shape
+        state = self.__dict__.setdefault('_gt_upload', dict(pinned=None, done=None))
+        if state['done'] is not None:
+            state['done'].synchronize()                 # the copy that last read the pinned buffer (usually long finished)
+        if state['pinned'] is None or state['pinned'].numel() < gt.size:
+            state['pinned'] = torch.empty(gt.size, dtype=torch.float32, pin_memory=True)
+        host = state['pinned'][:gt.size].view(h, w)
+        host.numpy()[...] = gt                          # astype(np.float32), as pre_eval
+        dev = host.to(pred.device, non_blocking=True)
+        state['done'] = torch.cuda.Event()
+        state['done'].record()
+        K.depth_metric_sums_resized(pred, dev, self.min_depth, self.max_depth, sums_row)
+
     def evaluate(self, results, metric='eigen', logger=None, **kwargs):
         if len(results) and isinstance(results[0], np.ndarray):
             results = self.pre_eval(list(results), list(range(len(results))))[0]

@@ -1,9 +1,11 @@
-"""ctypes binding of libgedepth_hip.so (C ABI: include/gedepth_hip.h, and include/gedepth_eval.h for the evaluation entry points).
+"""ctypes binding of libgedepth_hip.so (C ABI: include/gedepth_hip.h, include/gedepth_eval.h for the KITTI evaluation entry points and
+include/gedepth_ddad.h for the DDAD test protocol).
 
 The header is the only statement of the ABI: ``SIGNATURES`` (name -> (restype, argtypes)) is parsed from it at import, so a new entry
 point is declared there and nowhere else.  ``call(name, *args)`` launches an entry point that returns an error code and raises on a
 non-zero one; size queries and predicates that return a value are called on ``lib()`` directly.  ``EVAL_SIGNATURES`` is the same table
-for include/gedepth_eval.h, whose entry points stay outside the versioned ABI of gedepth_hip.h; ``lib()`` binds both.
+for include/gedepth_eval.h and ``DDAD_SIGNATURES`` for include/gedepth_ddad.h, whose entry points stay outside the versioned ABI of
+gedepth_hip.h; ``lib()`` binds all three.
 
 There is deliberately NO fallback: if the shared library is missing, or a tensor is not a
 contiguous CUDA(HIP) tensor of the expected dtype, the call raises.  Build the library with
@@ -19,6 +21,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('GE_LIB') or os.path.join(_HERE, 'csrc', 'libgedepth_hip.so')     # GE_LIB: a differently built library (A/B timing)
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), 'include', 'gedepth_hip.h')
 EVAL_HEADER_PATH = os.path.join(os.path.dirname(_HERE), 'include', 'gedepth_eval.h')
+DDAD_HEADER_PATH = os.path.join(os.path.dirname(_HERE), 'include', 'gedepth_ddad.h')
 GE_F32, GE_BF16 = 0, 1
 GE_COLORIZE_VMIN_DATA, GE_COLORIZE_VMAX_DATA, GE_COLORIZE_EQUAL = 1, 2, 4      # ge_depth_colorize flags
 
@@ -54,6 +57,8 @@ with open(HEADER_PATH) as _fh:
     SIGNATURES = parse_header(_fh.read())          # name -> (restype, argtypes)
 with open(EVAL_HEADER_PATH) as _fh:
     EVAL_SIGNATURES = parse_header(_fh.read())
+with open(DDAD_HEADER_PATH) as _fh:
+    DDAD_SIGNATURES = parse_header(_fh.read())
 
 _lib = None
 
@@ -71,7 +76,7 @@ def lib():
                 f'{LIB_PATH} is missing: the gfx950 HIP kernels are not built. '
                 f'Run gedepth_amd/csrc/build.sh (hipcc --offload-arch=gfx950). There is no CPU/eager fallback.')
         handle = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in list(SIGNATURES.items()) + list(EVAL_SIGNATURES.items()):
+        for name, (res, args) in list(SIGNATURES.items()) + list(EVAL_SIGNATURES.items()) + list(DDAD_SIGNATURES.items()):
             fn = getattr(handle, name)       # AttributeError here == ABI mismatch: fail loudly
             fn.restype, fn.argtypes = res, args
         _lib = handle

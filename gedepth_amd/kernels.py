@@ -2098,4 +2098,5 @@ def depth_colorize(value, vmin, vmax, lut):
 
 
 # --------------------------------------------------------------------- evaluation metric sums (csrc/eval.hip, include/gedepth_eval.h)
-from .eval_kernels import depth_metric_sums  # noqa: E402,F401
+# and the DDAD test protocol (include/gedepth_ddad.h)
+from .eval_kernels import depth_metric_sums, depth_metric_sums_resized, infer_front_ddad  # noqa: E402,F401

@@ -12,8 +12,9 @@ Any of ``--out`` / ``--format-only`` / ``--show`` / ``--show-dir``, or ``--launc
 raw maps as ``.npy``, ``--out FILE.pkl`` pickles the results list (metric tuples with ``--eval``, else the maps) on rank 0, and
 ``--launcher pytorch`` (tools/dist_test.sh) evaluates one shard per rank with ``multi_gpu_test``.
 
-``--device-eval`` (with ``--eval`` and ``--synthetic 0``, KITTI protocol) evaluates on the device: frames go through the graphed flip-TTA
-engine and each map is reduced to its metric sums by a HIP kernel, so no map is copied to the host (``single_gpu_test(device_eval=True)``).
+``--device-eval`` (with ``--eval`` and ``--synthetic 0``; KITTI or DDAD protocol) evaluates on the device: frames go through the graphed
+engine (flip-TTA for KITTI, the single view for DDAD) and each map is reduced to its metric sums by a HIP kernel, so no map is copied to the
+host (``single_gpu_test(device_eval=True)``).
 """
 import argparse
 import os
