@@ -14,8 +14,9 @@
 //     G = g^T X (ge_conv1x1_nhwc_wgrad, fp32) everything else is small-matrix algebra on G, the column sums and S (conv1x1_bn_bwd_finalize_k):
 //         d_beta = sum g,   d_gamma_c = rstd_c w_c . (G_c - sum g_c m)
 //         dW_c   = a_c (G_c - s m1_c - u_c m2_c)           u_c = rstd_c (S' w_c - s mean_c), S' = sum x x^T, s = sum x, m1 = d_beta / n, m2 = d_gamma / n
-//         dX     = g A1 + X A2 + c0       A1 = diag(a) W,  A2 = - W^T diag(rstd a m2) W,  c0 = ((mean rstd m2 - m1) a)^T W   (conv1x1_bn_dgrad_k:
-//                                                 one pass over g and X with [A1; A2] resident in LDS)
+//         dX     = g A1 + X A2 + c0       A1 = diag(a) W,  A2 = - W^T diag(rstd a m2) W,  c0 = ((mean rstd m2 - m1) a)^T W + m (A2 - bf16(A2))
+//                                                 (conv1x1_bn_dgrad_k: one pass over g and X with [A1; A2] resident in LDS in bf16; the last term of
+//                                                 c0, fp32, is what rounding A2 would otherwise leave of the input's channel means m)
 //     (the BatchNorm backward's mean-subtraction terms are rank-64 corrections of the two GEMMs the convolution backward runs anyway).
 // Statistics are those of the exact fp32 products (the two-pass path takes them from the bf16-rounded convolution output): bf16 mode only; the
 // fp32 parity mode keeps the two-pass kernels (csrc/nhwc.hip).
@@ -360,24 +361,32 @@ __global__ void __launch_bounds__(256) conv1x1_bn_bwd_finalize_k(const float* __
     k0[c] = (float)((mean * rstd * m2n - m1n) * a);
   }
 }
-// Wd[j][Cout + i] = A2[i][j] = - sum_c k2[c] w[c][i] w[c][j] (symmetric);  c0[j] = sum_c k0[c] w[c][j]  (fp32)
+// Wd[j][Cout + i] = A2[i][j] = - sum_c k2[c] w[c][i] w[c][j] (bf16);  c0[i] = sum_c k0[c] w[c][i] + sum_j m_j (A2[j][i] - bf16(A2[j][i]))  (fp32).
+// The second term: dX = ... + X A2 multiplies the bf16-rounded A2 by the RAW input x = m + (x - m), so the rounding residue times the channel
+// means m = sum x / n is a constant vector (it grows with |m| / std of the input; tests/test_conv1x1_bn_algebra_cpu.py) and belongs to c0.
+// w[c][i] w[c][j] is exact in fp32 (two 8-bit significands) and the sum runs in one fixed order, so A2 is symmetric to the bit: workgroup i,
+// which forms row i of A2 for the store, holds column i as well — the column that lands in dX[:, i] — and writes c0[i] itself.
 __global__ void __launch_bounds__(256) conv1x1_bn_bwd_a2_k(const bf16_t* __restrict__ w, const float* __restrict__ k2, const float* __restrict__ k0,
-                                                           bf16_t* __restrict__ Wd, float* __restrict__ c0v, int Cout) {
+                                                           const double* __restrict__ gram, bf16_t* __restrict__ Wd, float* __restrict__ c0v, int Cout,
+                                                           double n) {
   __shared__ float sm[4][CB_K];
+  __shared__ float sc[4];
   const int i = blockIdx.x, j = threadIdx.x & 63, sl = threadIdx.x >> 6;                 // four slices of the output channels per (i, j)
-  float a = 0.f;
-  if (i < CB_K) {
-    for (int c = sl; c < Cout; c += 4) a -= k2[c] * bf2f(w[(long)c * CB_K + i]) * bf2f(w[(long)c * CB_K + j]);
-  } else {
-    for (int c = sl; c < Cout; c += 4) a += k0[c] * bf2f(w[(long)c * CB_K + j]);
-  }
+  float a = 0.f, b = 0.f;
+  for (int c = sl; c < Cout; c += 4) a -= k2[c] * (bf2f(w[(long)c * CB_K + i]) * bf2f(w[(long)c * CB_K + j]));
+  for (int c = threadIdx.x; c < Cout; c += 256) b += k0[c] * bf2f(w[(long)c * CB_K + i]);
   sm[sl][j] = a;
   __syncthreads();
   if (sl == 0) {
     a = (sm[0][j] + sm[1][j]) + (sm[2][j] + sm[3][j]);
-    if (i < CB_K) Wd[(long)j * (Cout + CB_K) + Cout + i] = f2bf(a);
-    else c0v[j] = a;
+    const bf16_t r = f2bf(a);
+    Wd[(long)j * (Cout + CB_K) + Cout + i] = r;
+    b += (float)(gram[CB_K * CB_K + j] / n) * (a - bf2f(r));
   }
+  b = ge_wave_sum(b);
+  if (j == 0) sc[sl] = b;
+  __syncthreads();
+  if (threadIdx.x == 0) c0v[i] = (sc[0] + sc[1]) + (sc[2] + sc[3]);
 }
 
 // ------------------------------------------------------------------------------------------------ backward: data gradient
@@ -542,7 +551,7 @@ extern "C" int ge_conv1x1_bn_bwd_finalize(const float* GT, const float* colsum, 
   conv1x1_bn_bwd_finalize_k<<<(Cout + 3) / 4, 256, 0, s>>>(GT, colsum, gram, (const bf16_t*)w, gamma, save_mean, save_rstd, dgamma, dbeta, dW, (bf16_t*)Wd,
                                                            scratch, scratch + Cout, Cout, (double)rows);
   GE_LAUNCH_CHECK();
-  conv1x1_bn_bwd_a2_k<<<CB_K + 1, 256, 0, s>>>((const bf16_t*)w, scratch, scratch + Cout, (bf16_t*)Wd, c0, Cout);
+  conv1x1_bn_bwd_a2_k<<<CB_K, 256, 0, s>>>((const bf16_t*)w, scratch, scratch + Cout, gram, (bf16_t*)Wd, c0, Cout, (double)rows);
   GE_LAUNCH_CHECK();
   return GE_OK;
 }

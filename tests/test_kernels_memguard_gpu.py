@@ -23,6 +23,7 @@ import pytest
 import torch
 
 import memguard
+import test_conv1x1_bn_gpu as CB
 import test_inference_gpu as TI
 import test_kernels_gpu as TK
 import test_msda_hist_batched_gpu as HB
@@ -103,6 +104,12 @@ CASES = [
                                 'ge_conv1x1_bn_dgrad'},
          _each(lambda c, k: TK.test_conv1x1_bn_act_pos_vs_fp32_composition(c.dev, *k),
                (((1, 64, 33, 17), 512, 'tokens'), ((3, 64, 7, 9), 256, 'both'), ((2, 64, 24, 40), 512, 'slice')))),
+    # rows < 32, HW < 32, no position map, one row; Cout = 1024 (the widest Wd, one dgrad workgroup per CU) and 384 (odd chunk count, idle act_k waves)
+    Case('conv1x1_bn_act_pos edges', {'ge_conv1x1_bn_stats', 'ge_conv1x1_bn_act_fwd', 'ge_conv1x1_bn_bwd_mask', 'ge_conv1x1_nhwc_wgrad',
+                                      'ge_conv1x1_bn_bwd_finalize', 'ge_conv1x1_bn_dgrad'},
+         lambda c: ([CB.test_tile_and_channel_edges(c.dev, c.monkeypatch, *k) for k in
+                     (((1, 64, 3, 5), 128, True), ((3, 64, 1, 31), 128, True), ((3, 64, 3, 11), 128, False), ((2, 64, 7, 9), 384, True),
+                      ((2, 64, 7, 9), 1024, True))], CB.test_one_row(c.dev))),
     Case('conv1x1 as token GEMM', set(), lambda c: TK.test_conv1x1_as_token_gemm_vs_fp32_conv(c.dev, (2, 96, 24, 40), 512)),
     Case('conv1x1_wgrad', {'ge_conv1x1_nhwc_wgrad'}, lambda c: TK.test_conv1x1_wgrad_vs_float64(c.dev, (1, 64, 544, 30, 33), c.monkeypatch)),
     # ---- token GEMM and its epilogues
@@ -201,7 +208,7 @@ def test_guarded(dev, monkeypatch, golden, case, poison):
     # cached per-stream workspaces / accumulators made by earlier (unguarded) tests would bypass the frames
     for cache in ('_LN_ACC', '_COLSUM_WS', '_POS_ROWS', '_TILE_ORDER_CACHE', '_MM_VALUE_CHOICE'):
         monkeypatch.setattr(kernels, cache, {})
-    guard.install(monkeypatch, [kernels, optim, TK, TI, HB], binding=hip, frame_copies_on=dev)
+    guard.install(monkeypatch, [kernels, optim, TK, TI, HB, CB], binding=hip, frame_copies_on=dev)
     failure = None
     try:
         case.run(Ctx(dev, monkeypatch, golden))           # 2. the value test's own comparisons, NaN-strict
