@@ -1,0 +1,136 @@
+// Point clouds from a depth map (tools/misc/visualize_point-cloud_kitti.py of the reference; gedepth_amd/depth/utils/point_cloud.py here):
+// back-project the pixels whose depth is in range through the intrinsics, colour them from the frame, and leave them as 16-byte records
+// (x y z f32, R G B alpha u8) in row-major order with no holes: the device buffer is the payload of a binary PLY file byte for byte.
+//
+// Ordered stream compaction in two launches, no atomics, no block waiting on another block.  A block owns a contiguous span of
+// 256 * ipt candidates, taken 256 at a time (thread t of round j: candidate span start + 256 j + t, so a wave reads 64 neighbours).
+//   pass 1  predicate -> 64-bit ballot -> popcount per wave, the four wave counts through LDS, one int per block to the workspace;
+//   pass 2  every block folds the workspace entries before its own (as colorize_k folds the min / max partials), forms the predicate again
+//           and places a kept lane at  kept before the block + kept in earlier rounds + kept in earlier waves of the round + kept in lower
+//           lanes of the wave (mbcnt of the ballot), one 16-byte store per kept point; the last block stores the count.
+// The grid is capped by growing ipt, never by grid-striding, so a point's place is a pure function of its candidate index.
+// The arithmetic is numpy's float32 arithmetic: true IEEE division, no contraction.  Pure streaming work (1.7 MB read, up to 6.8 MB written
+// at 352 x 1216): launch-latency-sized.
+#pragma clang fp contract(off)
+#include "common.h"
+#include "../../include/gedepth_cloud.h"
+
+#define GE_CLOUD_MIN_IPT 4          // candidates per thread: at least 4 (a span of 1024), more once the grid would pass GE_CLOUD_MAX_BLOCKS
+#define GE_CLOUD_MAX_BLOCKS 1024
+
+struct CloudArgs {
+  int W, nc, n, row0, step, ipt;    // nc candidates per row, n in all
+  int Ws, top, left;
+  float fx, fy, cx, cy, dmin, dmax;
+  uint32_t alpha;
+};
+
+// candidate i -> its pixel, its depth and whether it is kept (false beyond the last candidate)
+__device__ __forceinline__ bool cloud_keep(const float* __restrict__ depth, const CloudArgs& a, long i, int& r, int& c, float& z) {
+  if (i >= a.n) return false;
+  const int ri = (int)i / a.nc;
+  r = a.row0 + ri * a.step;
+  c = ((int)i - ri * a.nc) * a.step;
+  z = depth[(long)r * a.W + c];
+  return a.dmin <= z && z <= a.dmax;
+}
+
+// pass 1: ws[b] = the number of kept candidates of block b's span
+__global__ void __launch_bounds__(256) cloud_count_k(const float* __restrict__ depth, CloudArgs a, int* __restrict__ ws) {
+  __shared__ int wc[4];
+  const long base = (long)blockIdx.x * a.ipt * 256 + threadIdx.x;
+  int cnt = 0;                                        // the same in every lane of a wave
+  for (int j = 0; j < a.ipt; ++j) {
+    int r, c;
+    float z;
+    cnt += __popcll(__ballot(cloud_keep(depth, a, base + 256 * j, r, c, z)));
+  }
+  if ((threadIdx.x & 63) == 0) wc[threadIdx.x >> 6] = cnt;
+  __syncthreads();
+  if (threadIdx.x == 0) ws[blockIdx.x] = wc[0] + wc[1] + wc[2] + wc[3];
+}
+
+// pass 2: the records, and the count from the block that owns the last candidate
+__global__ void __launch_bounds__(256) cloud_write_k(const float* __restrict__ depth, const uint8_t* __restrict__ bgr, CloudArgs a,
+                                                     const int* __restrict__ ws, ge_u32x4* __restrict__ records, int* __restrict__ count) {
+  __shared__ int red[256];
+  __shared__ int wc[2][4];                            // the wave counts of a round; two sets, so one barrier per round is enough
+  const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+  int s = 0;
+  for (int p = t; p < (int)blockIdx.x; p += 256) s += ws[p];
+  red[t] = s;
+  __syncthreads();
+  for (int h = 128; h > 0; h >>= 1) {
+    if (t < h) red[t] += red[t + h];
+    __syncthreads();
+  }
+  int run = red[0];                                   // kept candidates before this round
+  const long base = (long)blockIdx.x * a.ipt * 256 + t;
+  for (int j = 0; j < a.ipt; ++j) {
+    int r = 0, c = 0;
+    float z = 0.f;
+    const bool keep = cloud_keep(depth, a, base + 256 * j, r, c, z);
+    const unsigned long long m = __ballot(keep);
+    if (lane == 0) wc[j & 1][w] = __popcll(m);
+    __syncthreads();
+    const int c0 = wc[j & 1][0], c1 = wc[j & 1][1], c2 = wc[j & 1][2], c3 = wc[j & 1][3];
+    if (keep) {
+      const int lower = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+      const long k = (long)run + (w > 0 ? c0 : 0) + (w > 1 ? c1 : 0) + (w > 2 ? c2 : 0) + lower;
+      const float x = ((float)c - a.cx) / a.fx * z;
+      const float y = ((float)r - a.cy) / a.fy * z;
+      uint32_t rgba = 0x00ffffffu;
+      if (bgr) {
+        const uint8_t* p = bgr + ((long)(a.top + r) * a.Ws + (a.left + c)) * 3;
+        rgba = (uint32_t)p[2] | ((uint32_t)p[1] << 8) | ((uint32_t)p[0] << 16);
+      }
+      const ge_u32x4 rec = {__float_as_uint(x), __float_as_uint(y), __float_as_uint(z), rgba | (a.alpha << 24)};
+      records[k] = rec;
+    }
+    run += c0 + c1 + c2 + c3;
+  }
+  if (blockIdx.x == gridDim.x - 1 && t == 0) *count = run;
+}
+
+// nc, n, ipt and the grid of a geometry; false for one ge_depth_points refuses
+static bool cloud_geometry(int H, int W, int row0, int step, int& nc, int& n, int& ipt, unsigned& blocks) {
+  if (H <= 0 || W <= 0 || row0 < 0 || row0 >= H || step < 1 || (long)H * W > 0x7fffffffL) return false;
+  const long nr = ((long)(H - row0) + step - 1) / step;
+  nc = (int)(((long)W + step - 1) / step);
+  n = (int)(nr * nc);                                 // <= H * W
+  const long per = 256L * GE_CLOUD_MAX_BLOCKS;
+  ipt = (int)((n + per - 1) / per);
+  if (ipt < GE_CLOUD_MIN_IPT) ipt = GE_CLOUD_MIN_IPT;
+  blocks = (unsigned)((n + 256L * ipt - 1) / (256L * ipt));
+  return true;
+}
+
+extern "C" size_t ge_depth_points_workspace(int H, int W, int row0, int step) {
+  int nc, n, ipt;
+  unsigned blocks;
+  if (!cloud_geometry(H, W, row0, step, nc, n, ipt, blocks)) return 0;
+  return (size_t)blocks * sizeof(int);
+}
+
+extern "C" int ge_depth_points(const float* depth, int H, int W, const uint8_t* bgr, int Hs, int Ws, int top, int left, float fx, float fy,
+                               float cx, float cy, float dmin, float dmax, int row0, int step, int alpha, void* records, int* count,
+                               void* workspace, void* stream) {
+  if (!depth || !records || !count || !workspace || H <= 0 || W <= 0 || row0 < 0 || row0 >= H || step < 1 || alpha < 0 || alpha > 255 ||
+      fx == 0.f || fy == 0.f || dmin > dmax)
+    return GE_ERR_BAD_ARG;
+  if (bgr && (Hs <= 0 || Ws <= 0 || top < 0 || left < 0 || top > Hs - H || left > Ws - W)) return GE_ERR_BAD_ARG;   // no overflow: Hs - H
+  CloudArgs a;
+  unsigned blocks;
+  if (((uintptr_t)records & 15) || ((uintptr_t)depth & 3) || !cloud_geometry(H, W, row0, step, a.nc, a.n, a.ipt, blocks))
+    return GE_ERR_UNSUPPORTED;
+  a.W = W; a.row0 = row0; a.step = step;
+  a.Ws = Ws; a.top = top; a.left = left;
+  a.fx = fx; a.fy = fy; a.cx = cx; a.cy = cy; a.dmin = dmin; a.dmax = dmax;
+  a.alpha = (uint32_t)alpha;
+  hipStream_t s = ge_stream(stream);
+  cloud_count_k<<<blocks, 256, 0, s>>>(depth, a, (int*)workspace);
+  GE_LAUNCH_CHECK();
+  cloud_write_k<<<blocks, 256, 0, s>>>(depth, bgr, a, (const int*)workspace, (ge_u32x4*)records, count);
+  GE_LAUNCH_CHECK();
+  return GE_OK;
+}

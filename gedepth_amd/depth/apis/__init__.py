@@ -1,3 +1,3 @@
-from .inference import inference_depther, init_depther
+from .inference import inference_depther, inference_point_cloud, init_depther
 
-__all__ = ['init_depther', 'inference_depther']
+__all__ = ['init_depther', 'inference_depther', 'inference_point_cloud']

@@ -30,7 +30,8 @@ from ...mmrt.checkpoint import load_checkpoint
 from ...mmrt.config import Config
 from ..models import build_depther
 
-__all__ = ['init_depther', 'inference_depther', 'DepthInferencer', 'kitti_front_spec', 'ddad_front_spec', 'front_spec']
+__all__ = ['init_depther', 'inference_depther', 'inference_point_cloud', 'DepthInferencer', 'kitti_front_spec', 'ddad_front_spec',
+           'front_spec']
 
 # test-time transforms of MultiScaleFlipAug the device front end restates (ImageToTensor / Collect are layout only)
 _FRONT_TRANSFORMS = ('RandomFlip', 'Normalize', 'ImageToTensor', 'Collect')
@@ -224,6 +225,7 @@ class DepthInferencer:
         self._pinned = None
         self._uploaded = None                    # event after the last copy out of ``_pinned``
         self._pe = {}
+        self.last_frame = None                   # KITTI: (device uint8 BGR frame, top, left) of the last call, for ``points``
         self.reset()
 
     def reset(self):
@@ -347,6 +349,7 @@ class DepthInferencer:
                 raw = self.ground_depth(H, W, img if isinstance(img, str) else None, pe, calib, cam_height)
                 dev = self.upload(bgr)
                 K.infer_front(dev, raw, self.static_in, top, left, s['mean'], s['std'], s['to_rgb'], s['pe_max'], s['depth_scale'])
+                self.last_frame = (dev, top, left)
             key = self._key()
             g = self.graphs.get(key) if graph else None
             if graph and g is None and self.calls.get(key, 0) >= self.WARMUP:
@@ -365,6 +368,34 @@ class DepthInferencer:
             out = self.static_out.cpu().numpy() if to_host else self.static_out
         cur.wait_stream(self.stream)
         return out
+
+    def points(self, img, pe=None, calib=None, cam_height=1.65, graph=True, K=None, **cloud_kw):
+        """One frame -> the coloured points of its map, ``(records, count)`` device tensors as ``depth.utils.depth_to_points`` returns
+        them for a CUDA map, without synchronising.  The frame runs as in ``__call__`` with ``to_host=False``; ``ge_depth_points`` then
+        reads ``static_out``, the frame uploaded for this call and its KB-crop offsets on ``self.stream``, outside the captured graph (the
+        capture and its key are those of ``__call__``).  Intrinsics: ``kitti_intrinsics(img, calib, K, the test tree)``, in frame
+        coordinates, shifted by the crop (``cx - left``, ``cy - top``).  ``cloud_kw``: ``min_depth`` / ``max_depth`` (default: the decode
+        head's), ``row0``, ``step``, ``alpha``."""
+        if self.ddad:
+            raise NotImplementedError(_DDAD_NO_POINTS)
+        from ...kernels import depth_points                  # the module's ``K`` is this method's intrinsics argument
+        from ..utils.point_cloud import kitti_intrinsics
+        fx, fy, cx, cy = kitti_intrinsics(img if isinstance(img, str) else None, calib, K, self.prefix)     # errors before any device work
+        head = self.model.decode_head
+        cloud_kw.setdefault('min_depth', head.min_depth)
+        cloud_kw.setdefault('max_depth', head.max_depth)
+        depth = self(img, pe, calib, cam_height, graph, to_host=False)
+        dev, top, left = self.last_frame
+        cur = torch.cuda.current_stream(self.device)
+        with torch.cuda.stream(self.stream):
+            out = depth_points(depth, fx, fy, cx - left, cy - top, dev, top, left, **cloud_kw)
+        cur.wait_stream(self.stream)
+        return out
+
+
+_DDAD_NO_POINTS = ('point clouds on a DDAD engine: DDADResize feeds the network an area-resized frame that exists only normalised, so there '
+                   'is no uint8 colour at the map\'s size to read; depth.utils.depth_to_points with the map, intrinsics scaled to it and '
+                   'a frame the caller has resized serves DDAD maps')
 
 
 def inference_depther(model, img, pe=None, calib=None, cam_height=1.65, bf16=False, graph=True, camera=None):
@@ -403,3 +434,43 @@ def inference_depther(model, img, pe=None, calib=None, cam_height=1.65, bf16=Fal
         engines[bf16] = DepthInferencer(model, bf16)
     eng = engines[bf16]
     return [eng(i, p, calib, cam_height, graph, camera=c) for i, p, c in zip(imgs, pes, cams)]
+
+
+def inference_point_cloud(model, img, pe=None, calib=None, cam_height=1.65, bf16=False, graph=True, K=None, out_file=None, **cloud_kw):
+    """The coloured point cloud of each frame of ``img`` (a path, an (H, W, 3) uint8 BGR array, or a list of these): a list with one
+    ``depth.utils.POINT_DTYPE`` array per frame, from ``DepthInferencer.points`` (frames, ground depth, ``bf16`` and ``graph`` as in
+    ``inference_depther``).  Intrinsics: ``K`` (3x3 or 3x4, frame coordinates), else ``P_rect_02`` of ``calib``, else the recording day's
+    table for an image path inside the test tree.  ``out_file`` (a path, or a list with one per frame): the ``.ply`` files are written too
+    (``depth.utils.write_ply``).  ``cloud_kw``: ``min_depth``, ``max_depth``, ``row0``, ``step``, ``alpha``.
+
+    A DDAD config raises ``NotImplementedError`` (DDADResize: no uint8 frame at the map's size); ``depth_to_points`` serves DDAD maps."""
+    from ..utils.point_cloud import kitti_intrinsics, records_to_points, write_ply
+    imgs = img if isinstance(img, list) else [img]
+    pes = pe if isinstance(pe, list) else [pe] * len(imgs)
+    if len(pes) != len(imgs):
+        raise ValueError(f'{len(pes)} ground-depth maps for {len(imgs)} frames')
+    outs = out_file if isinstance(out_file, list) else [out_file] * len(imgs)
+    if len(outs) != len(imgs) or (out_file is not None and not isinstance(out_file, list) and len(imgs) != 1):
+        raise ValueError(f'out_file must be a list with one path per frame ({len(imgs)} frames)')
+    cfg = getattr(model, 'cfg', None)
+    if cfg is None:
+        raise ValueError('model.cfg is missing: build the model with init_depther (or set model.cfg to its Config)')
+    spec, prefix = front_spec(cfg), _img_prefix(cfg)                          # argument errors before any device work
+    if spec['protocol'] == 'ddad':
+        raise NotImplementedError(_DDAD_NO_POINTS)
+    if calib is None and any(p is None and _pe_file(spec, prefix, i) is None for i, p in zip(imgs, pes)):
+        raise ValueError(_NO_PE)
+    for i in imgs:
+        kitti_intrinsics(i if isinstance(i, str) else None, calib, K, prefix)
+    engines = model.__dict__.setdefault('_ge_inferencers', {})
+    bf16 = bool(bf16)
+    if bf16 not in engines or engines[bf16].spec != spec or engines[bf16].prefix != prefix:
+        engines[bf16] = DepthInferencer(model, bf16)
+    eng = engines[bf16]
+    clouds = []
+    for i, p, o in zip(imgs, pes, outs):
+        pts = records_to_points(*eng.points(i, p, calib, cam_height, graph, K, **cloud_kw))
+        if o is not None:
+            write_ply(o, pts)
+        clouds.append(pts)
+    return clouds

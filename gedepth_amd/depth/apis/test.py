@@ -1,6 +1,7 @@
 """Evaluation loops (depth/apis/test.py:32-232): run the model with ``return_loss=False`` over a data loader and either
 keep the predictions or reduce them to per-image metric tuples on the fly (``pre_eval``).  With ``show`` / ``out_dir`` each image's map
-also goes through the model's ``show_result`` (a colorized image, or the raw ``.npy`` under ``format_only``).
+also goes through the model's ``show_result`` (a colorized image, or the raw ``.npy`` under ``format_only``); with ``ply_dir`` it goes
+through ``save_point_cloud`` (a coloured point cloud per image, a binary ``.ply``).
 
 ``device_eval=True`` (opt-in; the KITTI and the DDAD protocol) evaluates where the prediction is: every frame goes through the graphed
 engine (apis/inference.py: flip-TTA for KITTI, the single view of DDADResize's shape for DDAD) and ``dataset.pre_eval_device`` reduces its
@@ -35,10 +36,29 @@ def replace_str(s):
     return s.replace('/', '_')
 
 
-def _show_batch(model, data, result_depth, show, out_dir, format_only):
+def _ply_file(depther, meta, depth, ply_dir):
+    """``ply_dir/<ori_filename with .ply>``: the map's points through the image's ``cam_intrinsic`` meta, coloured from the frame's KB-crop
+    window (the map is the bottom-aligned, horizontally centred window of the frame, as KBCrop cuts it)."""
+    from .inference import _decode
+    if 'cam_intrinsic' not in meta:
+        raise KeyError('ply_dir: the test pipeline\'s Collect carries no cam_intrinsic meta (add LoadKITTICamIntrinsic and the meta key)')
+    frame = _decode(meta['filename'])
+    h, w = depth.shape[-2:]
+    H, W = frame.shape[:2]
+    if H < h or W < w:
+        raise ValueError(f'ply_dir: the frame {(H, W)} is smaller than its map {(h, w)}: the map is not a crop of the frame')
+    out_file = osp.join(ply_dir, osp.splitext(meta['ori_filename'])[0] + '.ply')
+    depther.save_point_cloud(frame, [depth], meta['cam_intrinsic'], out_file, top=int(H - h), left=int((W - w) / 2))
+
+
+def _show_batch(model, data, result_depth, show, out_dir, format_only, ply_dir=None):
     depther = getattr(model, 'module', model)
     for meta, depth in zip(data['img_metas'][0], result_depth):
         name = meta['ori_filename']
+        if ply_dir:
+            _ply_file(depther, meta, depth, ply_dir)
+        if not (show or out_dir):
+            continue
         if not out_dir:
             out_file = None
         elif format_only:
@@ -48,7 +68,7 @@ def _show_batch(model, data, result_depth, show, out_dir, format_only):
         depther.show_result(name, [depth], show=show, out_file=out_file, format_only=format_only)
 
 
-def _device_eval(model, data_loader, pre_eval, format_only, show, out_dir):
+def _device_eval(model, data_loader, pre_eval, format_only, show, out_dir, ply_dir=None):
     """The ``device_eval`` loop of ``single_gpu_test``: the list of metric tuples ``pre_eval`` yields, in the sampler's order."""
     from ..core.evaluation import metrics_from_sums
     from ..datasets.ddad import DDADDataset
@@ -57,8 +77,8 @@ def _device_eval(model, data_loader, pre_eval, format_only, show, out_dir):
     dataset = data_loader.dataset
     if not pre_eval or format_only:
         raise NotImplementedError('device_eval reduces every map to metric sums on the device: it needs pre_eval=True and no format_only')
-    if show or out_dir:
-        raise NotImplementedError('device_eval with show / out_dir: the depth maps never reach the host')
+    if show or out_dir or ply_dir:
+        raise NotImplementedError('device_eval with show / out_dir / ply_dir: the depth maps never reach the host')
     name = type(dataset).__name__
     wants = 'ddad' if isinstance(dataset, DDADDataset) else 'kitti' if isinstance(dataset, KITTIDataset) else None
     if wants is None:
@@ -103,14 +123,22 @@ def _device_eval(model, data_loader, pre_eval, format_only, show, out_dir):
 
 
 def single_gpu_test(model, data_loader, pre_eval=False, format_only=False, format_args=None, device=None, *, show=False,
-                    out_dir=None, device_eval=False):
+                    out_dir=None, device_eval=False, ply_dir=None):
     """Returns a list with one entry per image: the metric tuple (``pre_eval``) or the ``(1, H, W)`` depth map.  ``show`` / ``out_dir``:
     ``show_result`` of every image's map, written to ``out_dir/replace_str(ori_filename)`` (``format_only``: the raw map as
-    ``out_dir/<ori_filename without extension>.npy``).  ``device_eval`` (with ``pre_eval``; KITTI or DDAD protocol): the module docstring."""
+    ``out_dir/<ori_filename without extension>.npy``).  ``ply_dir``: every image's point cloud as ``ply_dir/<ori_filename with .ply>``
+    (``save_point_cloud`` with the image's ``cam_intrinsic`` meta and its KB-crop offsets).  ``device_eval`` (with ``pre_eval``; KITTI or
+    DDAD protocol): the module docstring."""
     model.eval()
     if device_eval:
-        return _device_eval(model, data_loader, pre_eval, format_only, show, out_dir)
+        return _device_eval(model, data_loader, pre_eval, format_only, show, out_dir, ply_dir)
     dataset = data_loader.dataset
+    if ply_dir:
+        from ..datasets.ddad import DDADDataset
+        if isinstance(dataset, DDADDataset):
+            raise NotImplementedError('ply_dir on a DDAD split: DDADResize makes the map an area-resized view of the frame, not a crop of '
+                                      'it, so no frame pixel colours a map pixel; depth.utils.depth_to_points with a caller-resized '
+                                      'image serves DDAD maps')
     device = device or next(model.parameters()).device
     results, idx = [], 0
     loader_indices = data_loader.batch_sampler
@@ -124,17 +152,17 @@ def single_gpu_test(model, data_loader, pre_eval=False, format_only=False, forma
             result, _ = dataset.pre_eval(result, indices=list(batch_indices))
         results.extend(result)
         idx += len(result)
-        if show or out_dir:
-            _show_batch(model, data, result_depth, show, out_dir, format_only)
+        if show or out_dir or ply_dir:
+            _show_batch(model, data, result_depth, show, out_dir, format_only, ply_dir)
     return results
 
 
 def multi_gpu_test(model, data_loader, pre_eval=False, format_only=False, format_args=None, device=None, *, show=False, out_dir=None,
-                   device_eval=False):
+                   device_eval=False, ply_dir=None):
     """Each rank evaluates its shard of a non-shuffled DistributedSampler; rank 0 receives the results in dataset order.  ``show`` /
-    ``out_dir`` / ``device_eval`` as in ``single_gpu_test``: every rank writes the files of its own shard."""
+    ``out_dir`` / ``ply_dir`` / ``device_eval`` as in ``single_gpu_test``: every rank writes the files of its own shard."""
     part = single_gpu_test(model, data_loader, pre_eval, format_only, format_args, device, show=show, out_dir=out_dir,
-                           device_eval=device_eval)
+                           device_eval=device_eval, ply_dir=ply_dir)
     rank, world = get_dist_info()
     if world == 1:
         return part

@@ -164,6 +164,27 @@ class BaseDepther(BaseModule, metaclass=ABCMeta):
             warnings.warn('show==False and out_file is not specified, only result depth will be returned')
             return depth
 
+    def save_point_cloud(self, img, result, cam_intrinsic, out_file, top=0, left=0, **cloud_kw):
+        """Write ``depth = result[0]`` (a host or device map) as a coloured point cloud, a binary PLY file (``depth.utils.write_ply``): the
+        host-map route to ``depth.utils.depth_to_points``, like ``show_result`` for pictures.  ``img``: the frame, a path or an (Hs, Ws, 3)
+        uint8 BGR array, whose pixel (top + r, left + c) colours map pixel (r, c) (KB crop: ``top = Hs - 352``, ``left = (Ws - 1216) // 2``).
+        ``cam_intrinsic``: 3x3 or 3x4, in FRAME coordinates (the ``cam_intrinsic`` meta of the test pipeline); the crop is subtracted here.
+        ``cloud_kw``: ``min_depth`` / ``max_depth`` (default: the decode head's), ``row0``, ``step``, ``alpha``.  Returns the points."""
+        from ...apis.inference import _decode
+        from ...utils.point_cloud import _fxfycxcy, depth_to_points, records_to_points, write_ply
+        depth = result[0]
+        if np.ndim(depth) == 3 and np.shape(depth)[0] != 1 or np.ndim(depth) not in (2, 3):
+            raise ValueError(f'save_point_cloud writes one cloud: result[0] must be one depth map, got shape {np.shape(depth)}')
+        fx, fy, cx, cy = _fxfycxcy(cam_intrinsic)
+        K = [[fx, 0.0, cx - left], [0.0, fy, cy - top], [0.0, 0.0, 1.0]]
+        cloud_kw.setdefault('min_depth', self.decode_head.min_depth)
+        cloud_kw.setdefault('max_depth', self.decode_head.max_depth)
+        points = depth_to_points(depth, K, _decode(img), top, left, **cloud_kw)
+        if isinstance(points, tuple):
+            points = records_to_points(*points)
+        write_ply(out_file, points)
+        return points
+
     @staticmethod
     def _parse_losses(losses):
         log_vars = OrderedDict()

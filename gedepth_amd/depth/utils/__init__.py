@@ -1,4 +1,5 @@
 from .color_depth import colorize
+from .point_cloud import POINT_DTYPE, depth_to_points, kitti_intrinsics, write_ply
 from .position_encoding import SinePositionalEncoding
 
-__all__ = ['SinePositionalEncoding', 'colorize']
+__all__ = ['SinePositionalEncoding', 'colorize', 'POINT_DTYPE', 'depth_to_points', 'write_ply', 'kitti_intrinsics']

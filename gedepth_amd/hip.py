@@ -1,11 +1,11 @@
-"""ctypes binding of libgedepth_hip.so (C ABI: include/gedepth_hip.h, include/gedepth_eval.h for the KITTI evaluation entry points and
-include/gedepth_ddad.h for the DDAD test protocol).
+"""ctypes binding of libgedepth_hip.so (C ABI: include/gedepth_hip.h, include/gedepth_eval.h for the KITTI evaluation entry points,
+include/gedepth_ddad.h for the DDAD test protocol and include/gedepth_cloud.h for the point clouds).
 
 The header is the only statement of the ABI: ``SIGNATURES`` (name -> (restype, argtypes)) is parsed from it at import, so a new entry
 point is declared there and nowhere else.  ``call(name, *args)`` launches an entry point that returns an error code and raises on a
 non-zero one; size queries and predicates that return a value are called on ``lib()`` directly.  ``EVAL_SIGNATURES`` is the same table
-for include/gedepth_eval.h and ``DDAD_SIGNATURES`` for include/gedepth_ddad.h, whose entry points stay outside the versioned ABI of
-gedepth_hip.h; ``lib()`` binds all three.
+for include/gedepth_eval.h, ``DDAD_SIGNATURES`` for include/gedepth_ddad.h and ``CLOUD_SIGNATURES`` for include/gedepth_cloud.h, whose
+entry points stay outside the versioned ABI of gedepth_hip.h; ``lib()`` binds all four.
 
 There is deliberately NO fallback: if the shared library is missing, or a tensor is not a
 contiguous CUDA(HIP) tensor of the expected dtype, the call raises.  Build the library with
@@ -22,6 +22,7 @@ LIB_PATH = os.environ.get('GE_LIB') or os.path.join(_HERE, 'csrc', 'libgedepth_h
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), 'include', 'gedepth_hip.h')
 EVAL_HEADER_PATH = os.path.join(os.path.dirname(_HERE), 'include', 'gedepth_eval.h')
 DDAD_HEADER_PATH = os.path.join(os.path.dirname(_HERE), 'include', 'gedepth_ddad.h')
+CLOUD_HEADER_PATH = os.path.join(os.path.dirname(_HERE), 'include', 'gedepth_cloud.h')
 GE_F32, GE_BF16 = 0, 1
 GE_COLORIZE_VMIN_DATA, GE_COLORIZE_VMAX_DATA, GE_COLORIZE_EQUAL = 1, 2, 4      # ge_depth_colorize flags
 
@@ -59,6 +60,8 @@ with open(EVAL_HEADER_PATH) as _fh:
     EVAL_SIGNATURES = parse_header(_fh.read())
 with open(DDAD_HEADER_PATH) as _fh:
     DDAD_SIGNATURES = parse_header(_fh.read())
+with open(CLOUD_HEADER_PATH) as _fh:
+    CLOUD_SIGNATURES = parse_header(_fh.read())
 
 _lib = None
 
@@ -76,7 +79,8 @@ def lib():
                 f'{LIB_PATH} is missing: the gfx950 HIP kernels are not built. '
                 f'Run gedepth_amd/csrc/build.sh (hipcc --offload-arch=gfx950). There is no CPU/eager fallback.')
         handle = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in list(SIGNATURES.items()) + list(EVAL_SIGNATURES.items()) + list(DDAD_SIGNATURES.items()):
+        for name, (res, args) in (list(SIGNATURES.items()) + list(EVAL_SIGNATURES.items()) + list(DDAD_SIGNATURES.items())
+                                  + list(CLOUD_SIGNATURES.items())):
             fn = getattr(handle, name)       # AttributeError here == ABI mismatch: fail loudly
             fn.restype, fn.argtypes = res, args
         _lib = handle

@@ -2100,3 +2100,6 @@ def depth_colorize(value, vmin, vmax, lut):
 # --------------------------------------------------------------------- evaluation metric sums (csrc/eval.hip, include/gedepth_eval.h)
 # and the DDAD test protocol (include/gedepth_ddad.h)
 from .eval_kernels import depth_metric_sums, depth_metric_sums_resized, infer_front_ddad  # noqa: E402,F401
+
+# --------------------------------------------------------------------- point clouds (csrc/cloud.hip, include/gedepth_cloud.h)
+from .cloud_kernels import depth_points  # noqa: E402,F401
