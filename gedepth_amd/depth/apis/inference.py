@@ -18,6 +18,7 @@ A DDAD config (``front_spec(cfg)['protocol'] == 'ddad'``) takes LoadDDADImageFro
 (1, 5, Hd, Wd) buffer, the camera's height goes into a static (1,) tensor (the adaptive ground embedding reads it through a device pointer,
 so a replayed graph follows it) and the forward's (1, Hd, Wd) map is the output.  The frame's camera names the ground depth
 (``<pe_root>/<camera>/ddad_pe.npz``) and the height: the ``camera=`` argument, else the image path's parent directory.
+``_KITTIFront`` / ``_DDADFront`` hold what the protocols do differently per frame; ``engine_for`` keeps a model's engines for every caller.
 """
 import os.path as osp
 
@@ -28,7 +29,9 @@ from PIL import Image
 from ... import kernels as K
 from ...mmrt.checkpoint import load_checkpoint
 from ...mmrt.config import Config
+from ..datasets.pipelines import loading    # _DDAD_CAMERA_HEIGHT is read through the module at every use, so a changed table is seen
 from ..models import build_depther
+from ..utils.pinned import PinnedUpload
 
 __all__ = ['init_depther', 'inference_depther', 'inference_point_cloud', 'DepthInferencer', 'kitti_front_spec', 'ddad_front_spec',
            'front_spec']
@@ -63,6 +66,20 @@ def init_depther(config, checkpoint=None, device='cuda:0'):
     return model
 
 
+def _aug_spec(aug, allowed, front_end, name, steps):
+    """Both protocols' MultiScaleFlipAug -> ``(inner transform types, the spec fields of its Normalize)``; errors in the caller's words."""
+    inner = [t['type'] for t in aug['transforms']]
+    for t in inner:
+        if t not in allowed:
+            raise NotImplementedError(f'MultiScaleFlipAug transform {t}: no {front_end} for it ({steps})')
+    norm = next((t for t in aug['transforms'] if t['type'] == 'Normalize'), None)
+    if norm is None:
+        raise NotImplementedError(f'MultiScaleFlipAug without Normalize: not the {name} protocol {steps}')
+    # Normalize holds mean / std as float32 and widens them to float64 (imageops.imnormalize)
+    return inner, dict(mean=[float(np.float32(v)) for v in norm['mean']], std=[float(np.float32(v)) for v in norm['std']],
+                       to_rgb=bool(norm.get('to_rgb', True)), depth_scale=float(norm.get('depth_scale', 200)))
+
+
 def kitti_front_spec(cfg):
     """The parameters of the configured test pipeline the device front end needs; ``NotImplementedError`` for any other protocol."""
     pipeline = cfg.data.test.pipeline
@@ -78,22 +95,13 @@ def kitti_front_spec(cfg):
         raise NotImplementedError(f'test pipeline {types}: inference_depther implements the KITTI protocol {_PROTOCOL} only')
     if load.get('LOAD_DYNAMIC_PE', False):
         raise NotImplementedError('LoadImageFromFile(LOAD_DYNAMIC_PE=True): no device front end for it')
-    inner = [t['type'] for t in aug['transforms']]
-    for t in inner:
-        if t not in _FRONT_TRANSFORMS:
-            raise NotImplementedError(f'MultiScaleFlipAug transform {t}: no device front end for it ({_PROTOCOL})')
-    norm = next((t for t in aug['transforms'] if t['type'] == 'Normalize'), None)
-    if norm is None:
-        raise NotImplementedError(f'MultiScaleFlipAug without Normalize: not the KITTI protocol {_PROTOCOL}')
+    inner, common = _aug_spec(aug, _FRONT_TRANSFORMS, 'device front end', 'KITTI', _PROTOCOL)
     directions = aug.get('flip_direction', 'horizontal')
     directions = directions if isinstance(directions, list) else [directions]
     flip = bool(aug.get('flip', False)) and 'RandomFlip' in inner
     if aug.get('img_ratios') is not None or (flip and directions != ['horizontal']):
         raise NotImplementedError('multi-scale or vertical-flip test-time augmentation: no device front end for it')
-    return dict(height=int(kb.get('height', 352)), width=int(kb.get('width', 1216)), views=2 if flip else 1,
-                # Normalize holds mean / std as float32 and widens them to float64 (imageops.imnormalize)
-                mean=[float(np.float32(v)) for v in norm['mean']], std=[float(np.float32(v)) for v in norm['std']],
-                to_rgb=bool(norm.get('to_rgb', True)), depth_scale=float(norm.get('depth_scale', 200)),
+    return dict(common, height=int(kb.get('height', 352)), width=int(kb.get('width', 1216)), views=2 if flip else 1,
                 pe_max=float(load.get('pe_max', 200)), pe_root=load.get('pe_root'))
 
 
@@ -116,21 +124,13 @@ def ddad_front_spec(cfg):
         raise NotImplementedError('LoadDDADImageFromFile(to_float32=True): no device front end for it')
     if resize.get('depth', True):
         raise NotImplementedError('DDADResize(depth=True): the test protocol resizes no depth; no device front end for it')
-    inner = [t['type'] for t in aug['transforms']]
-    for t in inner:
-        if t not in _DDAD_TRANSFORMS:
-            raise NotImplementedError(f'MultiScaleFlipAug transform {t}: no DDAD device front end for it ({_DDAD_PROTOCOL})')
-    norm = next((t for t in aug['transforms'] if t['type'] == 'Normalize'), None)
-    if norm is None:
-        raise NotImplementedError(f'MultiScaleFlipAug without Normalize: not the DDAD protocol {_DDAD_PROTOCOL}')
+    _, common = _aug_spec(aug, _DDAD_TRANSFORMS, 'DDAD device front end', 'DDAD', _DDAD_PROTOCOL)
     if aug.get('flip', False):
         raise NotImplementedError('MultiScaleFlipAug(flip=True): no flip test-time augmentation on the DDAD device front end')
     if aug.get('img_ratios') is not None:
         raise NotImplementedError('MultiScaleFlipAug(img_ratios=...): no multi-scale test-time augmentation on the DDAD device front end')
     shape = tuple(int(v) for v in resize['shape'])
-    return dict(protocol='ddad', height=shape[0], width=shape[1], views=1,
-                mean=[float(np.float32(v)) for v in norm['mean']], std=[float(np.float32(v)) for v in norm['std']],
-                to_rgb=bool(norm.get('to_rgb', True)), depth_scale=float(norm.get('depth_scale', 200)),
+    return dict(common, protocol='ddad', height=shape[0], width=shape[1], views=1,
                 pe_max=250.0,                                          # LoadDDADImageFromFile's constant
                 pe_root=load.get('pe_root') if load.get('pe_root') is not None else osp.join('data', 'DDAD', 'pe_public_debug'))
 
@@ -143,15 +143,10 @@ def front_spec(cfg):
     return dict(kitti_front_spec(cfg), protocol='kitti')
 
 
-def _ddad_cameras():
-    from ..datasets.pipelines.loading import _DDAD_CAMERA_HEIGHT
-    return _DDAD_CAMERA_HEIGHT
-
-
 def _ddad_camera(camera, path):
     """The frame's camera: ``camera``, else the image path's parent directory (as LoadDDADCamIntrinsic takes it); None when neither names
     one.  A ``camera`` argument that is not a DDAD camera with a known height is a ``ValueError``."""
-    known = _ddad_cameras()
+    known = loading._DDAD_CAMERA_HEIGHT
     if camera is not None:
         if camera not in known:
             raise ValueError(f'camera {camera!r}: the cameras with a known height are {", ".join(sorted(known))}')
@@ -197,33 +192,83 @@ def _decode(img):
     return np.ascontiguousarray(a)
 
 
+class _KITTIFront:
+    """KITTI's own part of a frame's way through ``DepthInferencer``; no state, the engine is handed in."""
+
+    def frame(self, eng, H, W, path, camera):
+        """The frame's argument errors, before any device work -> ``(camera, ori_shape of the metas)``; DDAD's also sets ``eng.frame_size``."""
+        s = eng.spec
+        if H < s['height'] or W < s['width']:
+            raise ValueError(f'frame {(H, W)} is smaller than the KB crop {(s["height"], s["width"])}')
+        return None, (s['height'], s['width'], 5)
+
+    def fill(self, eng, bgr, path, cam, pe, calib, cam_height):
+        """On the engine's stream, outside its graph: ground depth, upload, front kernel into ``static_in``; returns ``last_frame``."""
+        s = eng.spec
+        H, W = bgr.shape[:2]
+        top, left = int(H - s['height']), int((W - s['width']) / 2)       # KBCrop
+        raw = eng.ground_depth(H, W, path, pe, calib, cam_height)
+        dev = eng.upload(bgr)
+        K.infer_front(dev, raw, eng.static_in, top, left, s['mean'], s['std'], s['to_rgb'], s['pe_max'], s['depth_scale'])
+        return dev, top, left
+
+
+class _DDADFront:
+    """DDAD's: the camera names ground depth and height, the frames of one engine have one size."""
+
+    def frame(self, eng, H, W, path, camera):
+        s = eng.spec
+        cam = _ddad_camera(camera, path)
+        if cam is None:
+            raise ValueError(f'no camera for this frame: pass camera= (one of {", ".join(sorted(loading._DDAD_CAMERA_HEIGHT))}) or an '
+                             'image path whose parent directory is the camera name')
+        if H < s['height'] or W < s['width']:
+            raise ValueError(f'frame {(H, W)} is smaller than DDADResize\'s shape {(s["height"], s["width"])}')
+        if eng.frame_size is not None and eng.frame_size != (H, W):
+            raise ValueError(f'frame {(H, W)}: this engine takes frames of {eng.frame_size} (reset() to change)')
+        eng.frame_size = (H, W)
+        return cam, (H, W, 5)                        # LoadDDADImageFromFile: ori_shape = the frame's
+
+    def fill(self, eng, bgr, path, cam, pe, calib, cam_height):
+        s = eng.spec
+        raw = eng.ground_depth_ddad(cam, *bgr.shape[:2], pe)
+        dev = eng.upload(bgr)
+        K.infer_front_ddad(dev, raw, eng.static_in, s['mean'], s['std'], s['to_rgb'], s['pe_max'], s['depth_scale'])
+        eng.static_height.fill_(float(loading._DDAD_CAMERA_HEIGHT[cam]))
+
+
+def _config_of(model):
+    """``(front_spec, image prefix)`` of ``model.cfg``; host work only, so argument errors can be read off it before any device work."""
+    cfg = getattr(model, 'cfg', None)
+    if cfg is None:
+        raise ValueError('model.cfg is missing: build the model with init_depther (or set model.cfg to its Config)')
+    return front_spec(cfg), _img_prefix(cfg)
+
+
 class DepthInferencer:
     """The flip-TTA engine of one model and precision (module docstring).  ``captures`` counts hipGraph captures; ``reset()`` drops them.
 
     A capture is keyed by the precision and the ``kernel_variant`` of every module that has one.  It bakes in the addresses of the
     parameters, buffers and static tensors: parameters must be updated IN PLACE (``load_state_dict``, ``param.data.copy_``) for a replay to
     see them; replacing a parameter tensor needs ``reset()``.  Host-side heuristics evaluated at capture time (the cross-attention's query
-    order) are frozen into the graph as in mmrt/graph.py; results do not depend on them."""
+    order) are frozen into the graph as in mmrt/graph.py; results do not depend on them.  ``front``: the protocol's own part of a frame."""
 
     WARMUP = 2
 
-    def __init__(self, model, bf16=False):
+    def __init__(self, model, bf16=False, config=None):
         self.model, self.bf16 = model, bool(bf16)
-        cfg = getattr(model, 'cfg', None)
-        if cfg is None:
-            raise ValueError('model.cfg is missing: build the model with init_depther (or set model.cfg to its Config)')
-        self.spec = front_spec(cfg)
+        self.spec, self.prefix = config or _config_of(model)
         self.ddad = self.spec['protocol'] == 'ddad'
-        self.prefix = _img_prefix(cfg)
+        self.front = _DDADFront() if self.ddad else _KITTIFront()
         self.device = next(model.parameters()).device
         s = self.spec
         self.static_in = torch.empty(s['views'], 5, s['height'], s['width'], device=self.device, dtype=torch.float32)
         self.static_out = torch.empty(1, s['height'], s['width'], device=self.device, dtype=torch.float32)
         # DDAD: the camera height, filled per frame outside the graph; ground_embed_adaptive reads it through its device pointer
         self.static_height = torch.zeros(1, device=self.device, dtype=torch.float32) if self.ddad else None
+        self._forward_kw = dict(height=self.static_height) if self.ddad else {}      # no ``test`` key: _height takes the tensor as it is
         self.stream = torch.cuda.Stream(self.device)
-        self._pinned = None
-        self._uploaded = None                    # event after the last copy out of ``_pinned``
+        self._staging = PinnedUpload()
         self._pe = {}
         self.last_frame = None                   # KITTI: (device uint8 BGR frame, top, left) of the last call, for ``points``
         self.reset()
@@ -256,44 +301,35 @@ class DepthInferencer:
         npy = _pe_file(self.spec, self.prefix, path)
         if npy is None:
             raise ValueError(_NO_PE)
-
-        def load():
-            a = np.load(npy).astype(np.float32)
-            if a.shape != (H, W):
-                raise ValueError(f'{npy} has shape {a.shape}, the frame is {(H, W)}')
-            return torch.from_numpy(a).to(self.device).contiguous()
-        return self._cache(('npy', npy, H, W), load)
+        return self._cache(('npy', npy, H, W), lambda: self._load_pe(npy, np.load(npy), H, W))
 
     def ground_depth_ddad(self, camera, H, W, pe=None):
         """Raw (H, W) f32 ground depth of ``camera`` on the device: ``pe``, else ``<pe_root>/<camera>/ddad_pe.npz['pe']`` (once per camera)."""
         if pe is not None:
             return self.ground_depth(H, W, pe=pe)
         npz = osp.join(self.spec['pe_root'], camera, 'ddad_pe.npz')
+        return self._cache(('ddad', npz, H, W), lambda: self._load_pe(npz, np.load(npz)['pe'], H, W))
 
-        def load():
-            a = np.load(npz)['pe'].astype(np.float32)
-            if a.shape != (H, W):
-                raise ValueError(f'{npz} has shape {a.shape}, the frame is {(H, W)}')
-            return torch.from_numpy(a).to(self.device).contiguous()
-        return self._cache(('ddad', npz, H, W), load)
+    def _load_pe(self, file, a, H, W):
+        a = a.astype(np.float32)
+        if a.shape != (H, W):
+            raise ValueError(f'{file} has shape {a.shape}, the frame is {(H, W)}')
+        return torch.from_numpy(a).to(self.device).contiguous()
 
     # ---- one frame
     def _key(self):
         return (self.bf16,) + tuple(m.kernel_variant for m in self.model.modules() if hasattr(m, 'kernel_variant'))
 
-    def _metas(self, filename, shape):
+    def _metas(self, filename, shape, ori_shape):
         s = self.spec
-        kb = tuple(shape) + (5,) if self.ddad else (s['height'], s['width'], 5)     # LoadDDADImageFromFile: ori_shape = the frame's
         norm = dict(mean=np.float32(s['mean']), std=np.float32(s['std']), to_rgb=s['to_rgb'])
-        return [dict(filename=filename, ori_filename=filename, ori_shape=kb, img_shape=tuple(shape) + (5,), pad_shape=tuple(shape) + (5,),
-                     scale_factor=1.0, flip=bool(v), flip_direction='horizontal', img_norm_cfg=norm) for v in range(s['views'])]
+        return [dict(filename=filename, ori_filename=filename, ori_shape=ori_shape, img_shape=tuple(shape) + (5,),
+                     pad_shape=tuple(shape) + (5,), scale_factor=1.0, flip=bool(v), flip_direction='horizontal', img_norm_cfg=norm)
+                for v in range(s['views'])]
 
     def _body(self, metas):
         with torch.no_grad(), torch.autocast('cuda', dtype=torch.bfloat16, enabled=self.bf16):
-            if self.ddad:                        # no ``test`` key: _height takes the tensor as it is
-                pred = self.model.encode_decode(self.static_in, metas, rescale=True, height=self.static_height)
-            else:
-                pred = self.model.encode_decode(self.static_in, metas, rescale=True)
+            pred = self.model.encode_decode(self.static_in, metas, rescale=True, **self._forward_kw)
         pred = pred.float().contiguous()
         if self.spec['views'] == 2:
             K.tta_merge(pred, self.static_out)
@@ -301,18 +337,8 @@ class DepthInferencer:
             self.static_out.copy_(pred[0])
 
     def upload(self, bgr):
-        """Host uint8 frame -> device, through a reused pinned buffer and a non-blocking copy on the current stream."""
-        n = bgr.size
-        if self._uploaded is not None:
-            self._uploaded.synchronize()             # ``to_host=False`` lets the host run ahead: the last copy must have read the buffer
-        if self._pinned is None or self._pinned.numel() < n:
-            self._pinned = torch.empty(n, dtype=torch.uint8, pin_memory=True)
-        host = self._pinned[:n].view(bgr.shape)
-        host.numpy()[...] = bgr
-        dev = host.to(self.device, non_blocking=True)
-        self._uploaded = torch.cuda.Event()
-        self._uploaded.record()
-        return dev
+        """Host uint8 frame -> device, through a reused pinned buffer and a non-blocking copy on the current stream (``PinnedUpload``)."""
+        return self._staging(bgr, self.device)
 
     def __call__(self, img, pe=None, calib=None, cam_height=1.65, graph=True, to_host=True, camera=None):
         """One frame -> its (1, 352, 1216) float32 map (DDAD: (1, Hd, Wd) of DDADResize's shape): a fresh host array, or with
@@ -321,35 +347,13 @@ class DepthInferencer:
         path's parent directory; ``calib`` / ``cam_height`` belong to the KITTI protocol."""
         bgr = _decode(img)
         H, W = bgr.shape[:2]
-        s = self.spec
-        cam = None
-        if self.ddad:
-            cam = _ddad_camera(camera, img if isinstance(img, str) else None)
-            if cam is None:
-                raise ValueError(f'no camera for this frame: pass camera= (one of {", ".join(sorted(_ddad_cameras()))}) or an image path '
-                                 'whose parent directory is the camera name')
-            if H < s['height'] or W < s['width']:
-                raise ValueError(f'frame {(H, W)} is smaller than DDADResize\'s shape {(s["height"], s["width"])}')
-            if self.frame_size is not None and self.frame_size != (H, W):
-                raise ValueError(f'frame {(H, W)}: this engine takes frames of {self.frame_size} (reset() to change)')
-            self.frame_size = (H, W)
-        elif H < s['height'] or W < s['width']:
-            raise ValueError(f'frame {(H, W)} is smaller than the KB crop {(s["height"], s["width"])}')
-        metas = self._metas(img if isinstance(img, str) else None, (H, W))
+        path = img if isinstance(img, str) else None
+        cam, ori_shape = self.front.frame(self, H, W, path, camera)
+        metas = self._metas(path, (H, W), ori_shape)
         cur = torch.cuda.current_stream(self.device)
         self.stream.wait_stream(cur)
         with torch.cuda.stream(self.stream):
-            if self.ddad:
-                raw = self.ground_depth_ddad(cam, H, W, pe)
-                dev = self.upload(bgr)
-                K.infer_front_ddad(dev, raw, self.static_in, s['mean'], s['std'], s['to_rgb'], s['pe_max'], s['depth_scale'])
-                self.static_height.fill_(float(_ddad_cameras()[cam]))
-            else:
-                top, left = int(H - s['height']), int((W - s['width']) / 2)       # KBCrop
-                raw = self.ground_depth(H, W, img if isinstance(img, str) else None, pe, calib, cam_height)
-                dev = self.upload(bgr)
-                K.infer_front(dev, raw, self.static_in, top, left, s['mean'], s['std'], s['to_rgb'], s['pe_max'], s['depth_scale'])
-                self.last_frame = (dev, top, left)
+            self.last_frame = self.front.fill(self, bgr, path, cam, pe, calib, cam_height)     # per frame: outside the graph
             key = self._key()
             g = self.graphs.get(key) if graph else None
             if graph and g is None and self.calls.get(key, 0) >= self.WARMUP:
@@ -398,6 +402,24 @@ _DDAD_NO_POINTS = ('point clouds on a DDAD engine: DDADResize feeds the network 
                    'a frame the caller has resized serves DDAD maps')
 
 
+def engine_for(model, bf16=False, config=None):
+    """The engine of ``model`` and ``bf16`` in ``model._ge_inferencers``, rebuilt when ``config`` (default ``_config_of(model)``) has changed."""
+    spec, prefix = config = config or _config_of(model)
+    engines = model.__dict__.setdefault('_ge_inferencers', {})
+    bf16 = bool(bf16)
+    if bf16 not in engines or engines[bf16].spec != spec or engines[bf16].prefix != prefix:
+        engines[bf16] = DepthInferencer(model, bf16, config)
+    return engines[bf16]
+
+
+def _per_frame(value, n, error):
+    """``value`` for each of ``n`` frames: a list holds one per frame (else ``ValueError(error)``), anything else serves every frame."""
+    values = value if isinstance(value, list) else [value] * n
+    if len(values) != n:
+        raise ValueError(error.format(n=len(values), m=n))
+    return values
+
+
 def inference_depther(model, img, pe=None, calib=None, cam_height=1.65, bf16=False, graph=True, camera=None):
     """Depth for each frame of ``img`` (a path, an (H, W, 3) uint8 BGR array, or a list of these): a list with one (1, 352, 1216)
     float32 array per frame — what ``model(return_loss=False, rescale=True, **data)`` returns for that frame through the config's test
@@ -410,29 +432,18 @@ def inference_depther(model, img, pe=None, calib=None, cam_height=1.65, bf16=Fal
     directory.  The result is one (1, Hd, Wd) map per frame at DDADResize's shape — what ``simple_test`` returns; the ground depth comes
     from ``pe``, else from ``<pe_root>/<camera>/ddad_pe.npz``.  Without a camera: ``NotImplementedError``."""
     imgs = img if isinstance(img, list) else [img]
-    pes = pe if isinstance(pe, list) else [pe] * len(imgs)
-    if len(pes) != len(imgs):
-        raise ValueError(f'{len(pes)} ground-depth maps for {len(imgs)} frames')
-    cfg = getattr(model, 'cfg', None)
-    if cfg is None:
-        raise ValueError('model.cfg is missing: build the model with init_depther (or set model.cfg to its Config)')
-    spec, prefix = front_spec(cfg), _img_prefix(cfg)                          # argument errors before any device work
-    cams = camera if isinstance(camera, list) else [camera] * len(imgs)
-    if len(cams) != len(imgs):
-        raise ValueError(f'{len(cams)} cameras for {len(imgs)} frames')
+    pes = _per_frame(pe, len(imgs), '{n} ground-depth maps for {m} frames')
+    spec, prefix = config = _config_of(model)                                 # argument errors before any device work
+    cams = _per_frame(camera, len(imgs), '{n} cameras for {m} frames')
     if spec['protocol'] == 'ddad':
-        cams = [_ddad_camera(c, i) for c, i in zip(cams, imgs)]
-        if any(c is None for c in cams):
+        if any(cam is None for cam in [_ddad_camera(c, i) for c, i in zip(cams, imgs)]):
             raise NotImplementedError('test pipeline step(s) LoadDDADImageFromFile, DDADResize: the device front end for them needs each '
                                       f'frame\'s camera (its ground depth and its height): pass camera= (one of '
-                                      f'{", ".join(sorted(_ddad_cameras()))}) or an image path whose parent directory is the camera name')
+                                      f'{", ".join(sorted(loading._DDAD_CAMERA_HEIGHT))}) or an image path whose parent directory is '
+                                      'the camera name')
     elif calib is None and any(p is None and _pe_file(spec, prefix, i) is None for i, p in zip(imgs, pes)):
         raise ValueError(_NO_PE)
-    engines = model.__dict__.setdefault('_ge_inferencers', {})
-    bf16 = bool(bf16)
-    if bf16 not in engines or engines[bf16].spec != spec or engines[bf16].prefix != prefix:     # model.cfg replaced: a new engine
-        engines[bf16] = DepthInferencer(model, bf16)
-    eng = engines[bf16]
+    eng = engine_for(model, bf16, config)
     return [eng(i, p, calib, cam_height, graph, camera=c) for i, p, c in zip(imgs, pes, cams)]
 
 
@@ -446,27 +457,17 @@ def inference_point_cloud(model, img, pe=None, calib=None, cam_height=1.65, bf16
     A DDAD config raises ``NotImplementedError`` (DDADResize: no uint8 frame at the map's size); ``depth_to_points`` serves DDAD maps."""
     from ..utils.point_cloud import kitti_intrinsics, records_to_points, write_ply
     imgs = img if isinstance(img, list) else [img]
-    pes = pe if isinstance(pe, list) else [pe] * len(imgs)
-    if len(pes) != len(imgs):
-        raise ValueError(f'{len(pes)} ground-depth maps for {len(imgs)} frames')
-    outs = out_file if isinstance(out_file, list) else [out_file] * len(imgs)
-    if len(outs) != len(imgs) or (out_file is not None and not isinstance(out_file, list) and len(imgs) != 1):
-        raise ValueError(f'out_file must be a list with one path per frame ({len(imgs)} frames)')
-    cfg = getattr(model, 'cfg', None)
-    if cfg is None:
-        raise ValueError('model.cfg is missing: build the model with init_depther (or set model.cfg to its Config)')
-    spec, prefix = front_spec(cfg), _img_prefix(cfg)                          # argument errors before any device work
+    pes = _per_frame(pe, len(imgs), '{n} ground-depth maps for {m} frames')
+    outs = _per_frame(out_file if out_file is None or isinstance(out_file, list) else [out_file], len(imgs),
+                      'out_file must be a list with one path per frame ({m} frames)')
+    spec, prefix = config = _config_of(model)                                 # argument errors before any device work
     if spec['protocol'] == 'ddad':
         raise NotImplementedError(_DDAD_NO_POINTS)
     if calib is None and any(p is None and _pe_file(spec, prefix, i) is None for i, p in zip(imgs, pes)):
         raise ValueError(_NO_PE)
     for i in imgs:
         kitti_intrinsics(i if isinstance(i, str) else None, calib, K, prefix)
-    engines = model.__dict__.setdefault('_ge_inferencers', {})
-    bf16 = bool(bf16)
-    if bf16 not in engines or engines[bf16].spec != spec or engines[bf16].prefix != prefix:
-        engines[bf16] = DepthInferencer(model, bf16)
-    eng = engines[bf16]
+    eng = engine_for(model, bf16, config)
     clouds = []
     for i, p, o in zip(imgs, pes, outs):
         pts = records_to_points(*eng.points(i, p, calib, cam_height, graph, K, **cloud_kw))

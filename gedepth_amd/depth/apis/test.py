@@ -71,49 +71,37 @@ def _show_batch(model, data, result_depth, show, out_dir, format_only, ply_dir=N
 def _device_eval(model, data_loader, pre_eval, format_only, show, out_dir, ply_dir=None):
     """The ``device_eval`` loop of ``single_gpu_test``: the list of metric tuples ``pre_eval`` yields, in the sampler's order."""
     from ..core.evaluation import metrics_from_sums
-    from ..datasets.ddad import DDADDataset
-    from ..datasets.kitti import KITTIDataset
-    from .inference import DepthInferencer, _img_prefix, front_spec
+    from ..datasets.pipelines import loading
+    from .inference import _config_of, engine_for
     dataset = data_loader.dataset
     if not pre_eval or format_only:
         raise NotImplementedError('device_eval reduces every map to metric sums on the device: it needs pre_eval=True and no format_only')
     if show or out_dir or ply_dir:
         raise NotImplementedError('device_eval with show / out_dir / ply_dir: the depth maps never reach the host')
-    name = type(dataset).__name__
-    wants = 'ddad' if isinstance(dataset, DDADDataset) else 'kitti' if isinstance(dataset, KITTIDataset) else None
+    name, wants = type(dataset).__name__, getattr(dataset, 'device_protocol', None)
     if wants is None:
         raise NotImplementedError(f'device_eval: {name} has no pre_eval_device (the KITTI and the DDAD protocol are evaluated on the device)')
     depther = getattr(model, 'module', model)
-    cfg = getattr(depther, 'cfg', None)
-    if cfg is None:
+    if getattr(depther, 'cfg', None) is None:                            # this loop's own words for it
         raise NotImplementedError('device_eval: model.cfg is missing (the engine reads the test protocol from it): build the model with '
                                   'init_depther or set model.cfg to its Config')
-    spec, prefix = front_spec(cfg), _img_prefix(cfg)                     # NotImplementedError names what the device front end lacks
+    spec, _ = config = _config_of(depther)                               # NotImplementedError names what the device front end lacks
     if spec['protocol'] != wants:                                        # before any attribute of the dataset is touched
         raise NotImplementedError(f'device_eval: {name} is evaluated by the {wants} protocol, the model\'s test pipeline is the '
                                   f'{spec["protocol"]} protocol')
-    ddad = wants == 'ddad'
-    if not ddad and (spec['height'], spec['width']) != (352, 1216):
+    if wants == 'kitti' and (spec['height'], spec['width']) != (352, 1216):
         raise NotImplementedError(f'device_eval: KBCrop {(spec["height"], spec["width"])}, the evaluation protocol crops (352, 1216)')
     bf16 = bool(torch.is_autocast_enabled('cuda') and torch.get_autocast_dtype('cuda') == torch.bfloat16)      # what the caller asks for
-    engines = depther.__dict__.setdefault('_ge_inferencers', {})
-    if bf16 not in engines or engines[bf16].spec != spec or engines[bf16].prefix != prefix:
-        engines[bf16] = DepthInferencer(depther, bf16)
-    eng = engines[bf16]
+    eng = engine_for(depther, bf16, config)
     indices = [i for batch in data_loader.batch_sampler for i in batch]
-    if ddad:                                         # every frame's camera needs a known height: found before the first frame runs
-        from .inference import _ddad_cameras
-        cams = {dataset.img_infos[i]['ann']['depth_map'].split('/')[-2] for i in indices}
-        if cams - set(_ddad_cameras()):
-            raise ValueError(f'device_eval: the split holds frames of {", ".join(sorted(cams - set(_ddad_cameras())))}; the cameras with '
-                             f'a known height are {", ".join(sorted(_ddad_cameras()))} (set the dataset\'s cameras to these)')
+    frames = [dataset.engine_frame(i) for i in indices]
+    unknown = {f['camera'] for f in frames if 'camera' in f} - set(loading._DDAD_CAMERA_HEIGHT)       # DDAD; before the first frame runs
+    if unknown:
+        raise ValueError(f'device_eval: the split holds frames of {", ".join(sorted(unknown))}; the cameras with '
+                         f'a known height are {", ".join(sorted(loading._DDAD_CAMERA_HEIGHT))} (set the dataset\'s cameras to these)')
     sums = torch.empty(max(len(indices), 1), 10, device=eng.device, dtype=torch.float64)
-    for row, i in enumerate(indices):
-        info = dataset.img_infos[i]
-        if ddad:                                     # the split holds full paths; the camera as LoadDDADImageFromFile takes it
-            pred = eng(info['filename'], to_host=False, camera=info['ann']['depth_map'].split('/')[-2])
-        else:
-            pred = eng(osp.join(dataset.img_dir, info['filename']), to_host=False)
+    for row, (i, frame) in enumerate(zip(indices, frames)):
+        pred = eng(to_host=False, **frame)
         with torch.cuda.stream(eng.stream):
             dataset.pre_eval_device(pred, i, sums[row])
     with torch.cuda.stream(eng.stream):
@@ -140,9 +128,8 @@ def single_gpu_test(model, data_loader, pre_eval=False, format_only=False, forma
                                       'it, so no frame pixel colours a map pixel; depth.utils.depth_to_points with a caller-resized '
                                       'image serves DDAD maps')
     device = device or next(model.parameters()).device
-    results, idx = [], 0
-    loader_indices = data_loader.batch_sampler
-    for batch_indices, data in zip(loader_indices, data_loader):
+    results = []
+    for batch_indices, data in zip(data_loader.batch_sampler, data_loader):
         with torch.no_grad():
             result = model(return_loss=False, **_to_device(data, device))
         result_depth = list(result)                 # the maps, before format_results / pre_eval replace them
@@ -151,7 +138,6 @@ def single_gpu_test(model, data_loader, pre_eval=False, format_only=False, forma
         if pre_eval:
             result, _ = dataset.pre_eval(result, indices=list(batch_indices))
         results.extend(result)
-        idx += len(result)
         if show or out_dir or ply_dir:
             _show_batch(model, data, result_depth, show, out_dir, format_only, ply_dir)
     return results

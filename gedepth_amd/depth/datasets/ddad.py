@@ -9,8 +9,10 @@ import torch.nn.functional as F
 from torch.utils.data import Dataset
 
 from ..core.evaluation import METRIC_NAMES, metrics, pre_eval_to_metrics
+from ..utils.pinned import PinnedUpload
 from .builder import DATASETS
 from .pipelines import Compose
+from .pipelines.loading import ddad_camera_of
 
 _CAM_K = {
     'CAMERA_01': [[2.1815303e+03, 0.0, 9.2802191e+02, 0], [0.0, 2.1816035e+03, 6.1595679e+02, 0], [0.0, 0.0, 1.0, 0]],
@@ -22,6 +24,7 @@ _CAM_K = {
 
 @DATASETS.register_module()
 class DDADDataset(Dataset):
+    device_protocol = 'ddad'                     # the front end of apis/inference.py that ``device_eval`` runs this split through
 
     def __init__(self, pipeline, cameras=('CAMERA_01', 'CAMERA_05', 'CAMERA_06', 'CAMERA_07', 'CAMERA_08', 'CAMERA_09'),
                  split=None, test_mode=False, garg_crop=False, eigen_crop=False, min_depth=1e-3, max_depth=200):
@@ -42,7 +45,7 @@ class DDADDataset(Dataset):
                 parts = line.strip().split(' ')
                 if len(parts) < 2:
                     continue
-                if parts[1].split('/')[-2] in self.cameras:
+                if ddad_camera_of(parts[1]) in self.cameras:
                     infos.append(dict(filename=parts[0], ann=dict(depth_map=parts[1].replace('depth_val', 'depth'))))
         return sorted(infos, key=lambda x: x['filename'])
 
@@ -59,6 +62,13 @@ class DDADDataset(Dataset):
         return self.pipeline(results)
 
     prepare_train_img = prepare_test_img = __getitem__
+
+    def camera_of(self, index):
+        return ddad_camera_of(self.img_infos[index]['ann']['depth_map'])
+
+    def engine_frame(self, index):
+        """Split entry ``index`` as the keyword arguments of ``DepthInferencer.__call__``: the split holds full paths."""
+        return dict(img=self.img_infos[index]['filename'], camera=self.camera_of(index))
 
     def format_results(self, results, imgfile_prefix=None, indices=None, **kwargs):
         results[0] = results[0].astype(np.uint16)
@@ -103,17 +113,7 @@ class DDADDataset(Dataset):
         gt = np.load(path)['depth']
         if gt.ndim != 2:
             raise TypeError(f'{path}: the ground truth must be a 2-D depth array, got shape {gt.shape}')
-        h, w = gt.shape
-        state = self.__dict__.setdefault('_gt_upload', dict(pinned=None, done=None))
-        if state['done'] is not None:
-            state['done'].synchronize()                 # the copy that last read the pinned buffer (usually long finished)
-        if state['pinned'] is None or state['pinned'].numel() < gt.size:
-            state['pinned'] = torch.empty(gt.size, dtype=torch.float32, pin_memory=True)
-        host = state['pinned'][:gt.size].view(h, w)
-        host.numpy()[...] = gt                          # astype(np.float32), as pre_eval
-        dev = host.to(pred.device, non_blocking=True)
-        state['done'] = torch.cuda.Event()
-        state['done'].record()
+        dev = self.__dict__.setdefault('_gt_upload', PinnedUpload())(np.asarray(gt, dtype=np.float32), pred.device)      # float32 as in pre_eval
         K.depth_metric_sums_resized(pred, dev, self.min_depth, self.max_depth, sums_row)
 
     def evaluate(self, results, metric='eigen', logger=None, **kwargs):

@@ -257,12 +257,12 @@ class DDADRawDataset:
         return len(self.img_infos)
 
     def __getitem__(self, idx):
-        from .pipelines.loading import _DDAD_CAMERA_HEIGHT
+        from .pipelines.loading import _DDAD_CAMERA_HEIGHT, ddad_camera_of
         info = self.img_infos[idx]
         filename = info['filename']
         bgr = np.ascontiguousarray(np.asarray(Image.open(filename).convert('RGB'))[..., ::-1])
         depth_file = info['ann']['depth_map']
-        camera = depth_file.split('/')[-2]
+        camera = ddad_camera_of(depth_file)
         out = dict(filename=filename, ori_filename=filename, date=camera, camera=camera, bgr=torch.from_numpy(bgr),
                    height=next(h for cam, h in _DDAD_CAMERA_HEIGHT.items() if cam in filename))
         if osp.isfile(depth_file):

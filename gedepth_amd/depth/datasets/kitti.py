@@ -13,6 +13,7 @@ from PIL import Image
 from torch.utils.data import Dataset
 
 from ..core.evaluation import METRIC_NAMES, metrics, pre_eval_to_metrics
+from ..utils.pinned import PinnedUpload
 from .builder import DATASETS
 from .pipelines import Compose
 
@@ -36,6 +37,7 @@ class KITTIDataset(Dataset):
     """Layout (reference docstring, kitti.py:103-134): ``data_root/input/<date>/<drive>/image_02/data/*.png``,
     ``data_root/gt_depth/<drive>/proj_depth/groundtruth/image_02/*.png`` (uint16, metres * 256), split lines
     ``<image> <depth|None> <focal>``; plus ``input/<date>/pe/pe_165.npy`` and ``slope_range_5_5_interval_1/...npz``."""
+    device_protocol = 'kitti'                    # the front end of apis/inference.py that ``device_eval`` runs this split through
 
     def __init__(self, pipeline, img_dir, ann_dir=None, split=None, data_root=None, test_mode=False, depth_scale=256,
                  garg_crop=True, eigen_crop=False, min_depth=1e-3, max_depth=80, mask_pe=False, mask_pe_gt=False):
@@ -92,6 +94,10 @@ class KITTIDataset(Dataset):
         return self.pipeline(results)
 
     prepare_train_img = prepare_test_img = __getitem__
+
+    def engine_frame(self, index):
+        """Split entry ``index`` as the keyword arguments of ``DepthInferencer.__call__``."""
+        return dict(img=osp.join(self.img_dir, self.img_infos[index]['filename']))
 
     def format_results(self, results, imgfile_prefix=None, indices=None, **kwargs):
         results[0] = (results[0] * self.depth_scale).astype(np.uint16)
@@ -151,16 +157,7 @@ class KITTIDataset(Dataset):
         h, w = raw.shape
         if h < 352 or w < 1216:
             raise ValueError(f'{path}: ground truth {(h, w)} is smaller than the KB crop (352, 1216)')
-        state = self.__dict__.setdefault('_gt_upload', dict(pinned=None, done=None))
-        if state['done'] is not None:
-            state['done'].synchronize()                 # the copy that last read the pinned buffer (usually long finished)
-        if state['pinned'] is None or state['pinned'].numel() < raw.size:
-            state['pinned'] = torch.empty(raw.size, dtype=torch.uint16, pin_memory=True)
-        host = state['pinned'][:raw.size].view(h, w)
-        host.numpy()[...] = raw
-        dev = host.to(pred.device, non_blocking=True)
-        state['done'] = torch.cuda.Event()
-        state['done'].record()
+        dev = self.__dict__.setdefault('_gt_upload', PinnedUpload())(raw, pred.device)      # the staging buffer, made on first use
         top, left = int(h - 352), int((w - 1216) / 2)                   # eval_kb_crop
         K.depth_metric_sums(pred, dev, top, left, self.eval_rect(352, 1216), self.depth_scale, self.min_depth, self.max_depth, sums_row)
 

@@ -113,12 +113,17 @@ class LoadImageFromFile:
 _DDAD_CAMERA_HEIGHT = {'CAMERA_01': 1.56, 'CAMERA_05': 1.57, 'CAMERA_06': 1.53, 'CAMERA_09': 1.53}
 
 
+def ddad_camera_of(path):
+    """The camera directory of a DDAD image or depth path, ``.../<camera>/<frame>``."""
+    return path.split('/')[-2]
+
+
 @PIPELINES.register_module()
 class LoadDDADCamIntrinsic:
     """loading.py:958-978: the camera name is the parent directory of the image."""
 
     def __call__(self, results):
-        results['cam_intrinsic'] = results['cam_intrinsic_dict'][results['filename'].split('/')[-2]]
+        results['cam_intrinsic'] = results['cam_intrinsic_dict'][ddad_camera_of(results['filename'])]
         return results
 
     def __repr__(self):
@@ -173,7 +178,7 @@ class LoadDDADImageFromFile:
         results['filename'] = filename
         results['ori_filename'] = name
         if self.USEPE:
-            camera = results['ann_info']['depth_map'].split('/')[-2]
+            camera = ddad_camera_of(results['ann_info']['depth_map'])
             pe_raw = np.load(osp.join(self.pe_root, camera, 'ddad_pe.npz'))['pe']
             pe = pe_raw.copy()
             pe[pe > 250] = 0

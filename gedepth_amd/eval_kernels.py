@@ -76,17 +76,11 @@ def infer_front_ddad(bgr, pe, out, mean, std, to_rgb=True, pe_max=250.0, depth_s
     normalised, and its camera's raw ground depth ``pe`` (H, W) f32 resized nearest-neighbour into channels 3 (clamped to [0, pe_max],
     / depth_scale) and 4 (raw), like LoadDDADImageFromFile -> DDADResize -> Normalize of the host test pipeline.  ``mean`` / ``std``: three
     floats each (widened to float64 as Normalize does with its float32 arrays)."""
-    from .kernels import _launch
-    if bgr.dtype != torch.uint8 or bgr.dim() != 3 or bgr.shape[2] != 3:
-        raise TypeError(f'bgr must be a (H, W, 3) uint8 tensor, got {tuple(bgr.shape)} {bgr.dtype}')
-    H, W = bgr.shape[:2]
-    if tuple(pe.shape) != (H, W):
-        raise ValueError(f'ground depth {tuple(pe.shape)} does not match the frame {(H, W)}')
+    from .kernels import _front_args, _launch
+    H, W, m, s = _front_args(bgr, pe, mean, std)
     if out.dim() != 4 or tuple(out.shape[:2]) != (1, 5):
         raise ValueError(f'out must be (1, 5, Hd, Wd), got {tuple(out.shape)}')
     Hd, Wd = out.shape[2:]
-    m = (ctypes.c_double * 3)(*[float(v) for v in mean])
-    s = (ctypes.c_double * 3)(*[float(v) for v in std])
     _launch('infer_front_ddad', 3 * H * W + 8 * Hd * Wd + 20 * Hd * Wd, 'ge_infer_front_ddad', hip.ptr(bgr, torch.uint8, 'bgr'),
             hip.ptr(pe, torch.float32, 'pe'), hip.ptr(out, torch.float32, 'out'), H, W, Hd, Wd, float(pe_max),
             ctypes.cast(m, ctypes.c_void_p), ctypes.cast(s, ctypes.c_void_p), float(depth_scale), int(bool(to_rgb)), hip.stream())

@@ -5,7 +5,7 @@ The header is the only statement of the ABI: ``SIGNATURES`` (name -> (restype, a
 point is declared there and nowhere else.  ``call(name, *args)`` launches an entry point that returns an error code and raises on a
 non-zero one; size queries and predicates that return a value are called on ``lib()`` directly.  ``EVAL_SIGNATURES`` is the same table
 for include/gedepth_eval.h, ``DDAD_SIGNATURES`` for include/gedepth_ddad.h and ``CLOUD_SIGNATURES`` for include/gedepth_cloud.h, whose
-entry points stay outside the versioned ABI of gedepth_hip.h; ``lib()`` binds all four.
+entry points stay outside the versioned ABI of gedepth_hip.h; ``HEADERS`` names the four and ``lib()`` binds them all.
 
 There is deliberately NO fallback: if the shared library is missing, or a tensor is not a
 contiguous CUDA(HIP) tensor of the expected dtype, the call raises.  Build the library with
@@ -19,10 +19,8 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('GE_LIB') or os.path.join(_HERE, 'csrc', 'libgedepth_hip.so')     # GE_LIB: a differently built library (A/B timing)
-HEADER_PATH = os.path.join(os.path.dirname(_HERE), 'include', 'gedepth_hip.h')
-EVAL_HEADER_PATH = os.path.join(os.path.dirname(_HERE), 'include', 'gedepth_eval.h')
-DDAD_HEADER_PATH = os.path.join(os.path.dirname(_HERE), 'include', 'gedepth_ddad.h')
-CLOUD_HEADER_PATH = os.path.join(os.path.dirname(_HERE), 'include', 'gedepth_cloud.h')
+HEADERS = {'SIGNATURES': 'gedepth_hip.h', 'EVAL_SIGNATURES': 'gedepth_eval.h', 'DDAD_SIGNATURES': 'gedepth_ddad.h',
+           'CLOUD_SIGNATURES': 'gedepth_cloud.h'}      # table name -> its header under include/, in binding order
 GE_F32, GE_BF16 = 0, 1
 GE_COLORIZE_VMIN_DATA, GE_COLORIZE_VMAX_DATA, GE_COLORIZE_EQUAL = 1, 2, 4      # ge_depth_colorize flags
 
@@ -54,14 +52,9 @@ def parse_header(text):
     return sigs
 
 
-with open(HEADER_PATH) as _fh:
-    SIGNATURES = parse_header(_fh.read())          # name -> (restype, argtypes)
-with open(EVAL_HEADER_PATH) as _fh:
-    EVAL_SIGNATURES = parse_header(_fh.read())
-with open(DDAD_HEADER_PATH) as _fh:
-    DDAD_SIGNATURES = parse_header(_fh.read())
-with open(CLOUD_HEADER_PATH) as _fh:
-    CLOUD_SIGNATURES = parse_header(_fh.read())
+for _table, _header in HEADERS.items():            # SIGNATURES, EVAL_SIGNATURES, ...: name -> (restype, argtypes)
+    with open(os.path.join(os.path.dirname(_HERE), 'include', _header)) as _fh:
+        globals()[_table] = parse_header(_fh.read())
 
 _lib = None
 
@@ -79,10 +72,10 @@ def lib():
                 f'{LIB_PATH} is missing: the gfx950 HIP kernels are not built. '
                 f'Run gedepth_amd/csrc/build.sh (hipcc --offload-arch=gfx950). There is no CPU/eager fallback.')
         handle = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in (list(SIGNATURES.items()) + list(EVAL_SIGNATURES.items()) + list(DDAD_SIGNATURES.items())
-                                  + list(CLOUD_SIGNATURES.items())):
-            fn = getattr(handle, name)       # AttributeError here == ABI mismatch: fail loudly
-            fn.restype, fn.argtypes = res, args
+        for table in HEADERS:
+            for name, (res, args) in globals()[table].items():
+                fn = getattr(handle, name)   # AttributeError here == ABI mismatch: fail loudly
+                fn.restype, fn.argtypes = res, args
         _lib = handle
         if os.environ.get('GE_MSDA_MODE'):           # kernel-selection knob of the deformable attention (kernels.msda_mode), e.g.
             handle.ge_msda_mode(int(os.environ['GE_MSDA_MODE']))      # 60 = default without the bf16-tap-weight window forward

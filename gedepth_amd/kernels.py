@@ -2025,19 +2025,26 @@ def pe_channels(raw, depth_scale=200.0):
 
 
 # --------------------------------------------------------------------- single-frame inference (csrc/infer.hip)
-def infer_front(bgr, pe, out, top, left, mean, std, to_rgb=True, pe_max=200.0, depth_scale=200.0):
-    """KITTI test front end into ``out`` (views, 5, Hc, Wc) f32: view 0 = the (Hc, Wc) window of the uint8 HWC BGR frame ``bgr`` and its
-    raw ground depth ``pe`` (H, W) f32 at (top, left), normalised like the host test pipeline; view 1 (views == 2) = its mirror.
-    ``mean`` / ``std``: three floats each (widened to float64 as Normalize does with its float32 arrays)."""
+def _front_args(bgr, pe, mean, std):
+    """What both front ends check and pack: ``(H, W, mean, std)`` of a (H, W, 3) uint8 frame and its (H, W) ground depth, ``mean`` /
+    ``std`` as ``double[3]`` arrays (widened to float64 as Normalize does with its float32 arrays)."""
     if bgr.dtype != torch.uint8 or bgr.dim() != 3 or bgr.shape[2] != 3:
         raise TypeError(f'bgr must be a (H, W, 3) uint8 tensor, got {tuple(bgr.shape)} {bgr.dtype}')
     H, W = bgr.shape[:2]
     if tuple(pe.shape) != (H, W):
         raise ValueError(f'ground depth {tuple(pe.shape)} does not match the frame {(H, W)}')
-    views, C, Hc, Wc = out.shape
-    assert C == 5
     m = (ctypes.c_double * 3)(*[float(v) for v in mean])
     s = (ctypes.c_double * 3)(*[float(v) for v in std])
+    return H, W, m, s
+
+
+def infer_front(bgr, pe, out, top, left, mean, std, to_rgb=True, pe_max=200.0, depth_scale=200.0):
+    """KITTI test front end into ``out`` (views, 5, Hc, Wc) f32: view 0 = the (Hc, Wc) window of the uint8 HWC BGR frame ``bgr`` and its
+    raw ground depth ``pe`` (H, W) f32 at (top, left), normalised like the host test pipeline; view 1 (views == 2) = its mirror.
+    ``mean`` / ``std``: three floats each (widened to float64 as Normalize does with its float32 arrays)."""
+    H, W, m, s = _front_args(bgr, pe, mean, std)
+    views, C, Hc, Wc = out.shape
+    assert C == 5
     hip.call('ge_infer_front', hip.ptr(bgr, torch.uint8, 'bgr'), hip.ptr(pe, _f32, 'pe'), hip.ptr(out, _f32, 'out'), H, W, int(top), int(left), Hc,
              Wc, views, float(pe_max), ctypes.cast(m, ctypes.c_void_p), ctypes.cast(s, ctypes.c_void_p), float(depth_scale), int(bool(to_rgb)),
              hip.stream())

@@ -259,3 +259,22 @@ def test_ddad_dataset_pipeline_and_eval(tmp_path):
     gt = np.load(dt.img_infos[0]['ann']['depth_map'])['depth']
     res, _ = dt.pre_eval([np.where(gt > 0, gt, 1.0)[None].astype(np.float32)], [0])      # full-resolution prediction
     assert dt.evaluate(res)['abs_rel'] == pytest.approx(0.0, abs=1e-6)
+
+
+def test_datasets_say_how_their_frames_reach_the_engine(toy, tmp_path):
+    """``device_protocol`` and ``engine_frame(i)`` against the expressions ``single_gpu_test(device_eval=True)`` used to spell out."""
+    from gedepth_amd.depth.datasets import DDADDataset
+    root, split = toy
+    kitti = build_dataset(_cfg(root, split).data.test, dict(test_mode=True))
+    assert KITTIDataset.device_protocol == 'kitti' and KITTIDataset.__new__(KITTIDataset).device_protocol == 'kitti'
+    assert len(kitti) > 0
+    for i, info in enumerate(kitti.img_infos):
+        assert kitti.engine_frame(i) == dict(img=os.path.join(kitti.img_dir, info['filename']))
+    ddad = build_dataset(dict(type='DDADDataset', pipeline=[], split=_make_toy_ddad(str(tmp_path)), test_mode=True,
+                              cameras=['CAMERA_01', 'CAMERA_05', 'CAMERA_07']))
+    assert DDADDataset.device_protocol == 'ddad' and DDADDataset.__new__(DDADDataset).device_protocol == 'ddad'
+    assert len(ddad) == 6
+    for i, info in enumerate(ddad.img_infos):
+        assert ddad.camera_of(i) == info['ann']['depth_map'].split('/')[-2]
+        assert ddad.engine_frame(i) == dict(img=info['filename'], camera=info['ann']['depth_map'].split('/')[-2])
+    assert [ddad.camera_of(i) for i in range(6)] == ['CAMERA_01'] * 2 + ['CAMERA_05'] * 2 + ['CAMERA_07'] * 2

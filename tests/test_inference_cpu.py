@@ -78,6 +78,44 @@ def test_kitti_front_spec_reads_the_config():
         kitti_front_spec(cfg)
 
 
+def test_engine_for_keeps_one_engine_per_config_and_precision(monkeypatch):
+    """``engine_for`` with a stub in the engine's place (building the real one is device work): the same object while ``model.cfg`` says
+    the same, a new one after the test pipeline or the image prefix changes, one per precision, a caller's ``config`` used as given, and
+    the ``ValueError`` of a model without ``cfg``."""
+    import types
+    from gedepth_amd.depth.apis import inference
+    from gedepth_amd.mmrt.config import Config
+    built = []
+
+    class Engine:
+        def __init__(self, model, bf16=False, config=None):
+            (self.spec, self.prefix), self.bf16 = config, bf16
+            built.append(self)
+    monkeypatch.setattr(inference, 'DepthInferencer', Engine)
+    model = types.SimpleNamespace(cfg=Config.fromfile(os.path.join(CFG, 'depthformer_swint_v.py')))
+    first = inference.engine_for(model, False)
+    assert (first.spec, first.prefix) == (inference.front_spec(model.cfg), inference._img_prefix(model.cfg))
+    assert inference.engine_for(model, False) is first and inference.engine_for(model, 0) is first and built == [first]
+    assert model._ge_inferencers == {False: first}
+    half = inference.engine_for(model, True)
+    assert half is not first and half.bf16 is True and model._ge_inferencers == {False: first, True: half}
+    kb = next(t for t in model.cfg.data.test.pipeline if t['type'] == 'KBCrop')
+    kb['height'], kb['width'] = 320, 1184
+    second = inference.engine_for(model, False)
+    assert second is not first and (second.spec['height'], second.spec['width']) == (320, 1184)
+    assert inference.engine_for(model, False) is second and model._ge_inferencers[False] is second
+    model.cfg.data.test.data_root = '/another/tree'
+    third = inference.engine_for(model, False)
+    assert third is not second and third.prefix != second.prefix and len(built) == 4
+    config = inference._config_of(model)
+    assert config == (third.spec, third.prefix) and inference.engine_for(model, False, config) is third and len(built) == 4
+    with pytest.raises(ValueError, match='model.cfg is missing: build the model with init_depther'):
+        inference.engine_for(types.SimpleNamespace(), False)
+    with pytest.raises(ValueError, match='model.cfg is missing: build the model with init_depther'):
+        inference.engine_for(types.SimpleNamespace(cfg=None), True)
+    assert len(built) == 4
+
+
 def test_benchmark_cli_parses():
     out = subprocess.run([sys.executable, os.path.join(ROOT, 'tools', 'benchmark.py'), '--help'], capture_output=True, text=True,
                          timeout=300)

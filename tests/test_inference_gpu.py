@@ -273,3 +273,25 @@ def test_checkpoint_round_trip(vanilla, tmp_path):
     a = inference_depther(loaded, frame, pe=pe, graph=False)[0]
     b = inference_depther(vanilla, frame, pe=pe, graph=False)[0]
     assert np.abs(a - b).max() <= 1e-6 * np.abs(b).max(), np.abs(a - b).max()
+
+
+def test_pinned_upload_keeps_three_arrays_apart_without_synchronising():
+    """``PinnedUpload`` alone, one instance: an array, a second of another dtype that fits in the first one's bytes (the same pinned
+    buffer, rewritten by the host), a third that makes the buffer grow; nothing synchronises in between.  After one synchronisation at
+    the end every device tensor holds its source's bytes: no later host write reached a buffer an earlier copy still read."""
+    from gedepth_amd.depth.utils.pinned import PinnedUpload
+    rng = np.random.default_rng(7)
+    sources = [rng.integers(0, 256, (3, 5, 3), dtype=np.uint8), rng.integers(0, 65536, (2, 7), dtype=np.uint16),
+               rng.integers(0, 256, (64, 64, 3), dtype=np.uint8)]
+    assert sources[1].nbytes <= sources[0].nbytes < sources[2].nbytes
+    upload, sent, buffers = PinnedUpload(), [], []
+    for a in sources:
+        sent.append(upload(a, torch.device('cuda')))
+        buffers.append(upload.buffer)
+    assert buffers[0] is buffers[1] and buffers[0].numel() == sources[0].nbytes and buffers[0].is_pinned()
+    assert buffers[2] is not buffers[0] and buffers[2].numel() == sources[2].nbytes and buffers[2].is_pinned()
+    torch.cuda.synchronize()
+    for a, t in zip(sources, sent):
+        assert t.is_cuda and tuple(t.shape) == a.shape and t.element_size() == a.itemsize
+        assert t.cpu().view(torch.uint8).numpy().tobytes() == a.tobytes(), (a.shape, a.dtype)
+    assert sent[1].dtype == torch.uint16 and sent[0].dtype == sent[2].dtype == torch.uint8
