@@ -8,6 +8,7 @@
 // reference's ATen / numpy code.  Must precede every include: contraction flags are attached per operation.
 #pragma clang fp contract(off)
 #include "common.h"
+#include "../../include/gedepth_ground.h"
 
 // ====================================================================================== bilinear
 // Forward: a lane produces VN consecutive outputs of one row (one 16-byte store, the row interpolation weights and the
@@ -318,6 +319,121 @@ extern "C" int ge_ground_vanilla_bwd(const float* pe_norm, long pe_bs, float gai
   ground_vanilla_bwd_k<<<ge_blocks(total, 256, 65536), 256, 0, s>>>(pe_norm, pe_bs, gain, d_pe_mask, d_y_hr, scratch, B, (long)H * W);
   GE_LAUNCH_CHECK();
   return bilinear_bwd_launch<float>(scratch, d_y_lr, B, 1, h, w, H, W, 0, (long)H * W, (long)H * W, (long)h * w, (long)h * w, s);
+}
+
+// =========================================================================== merged ground maps (inference)
+// include/gedepth_ground.h.  One launch for the V (1 or 2) views of the inference engine: the per-view quantities come from ground_pixel /
+// tap4 above, evaluated as ground_embed_fwd_k / ground_vanilla_fwd_k evaluate them, so attention, ground_term and valid carry the training
+// path's bits; the 11 up-sampled logits stay in registers.  A lane owns four consecutive columns of one row: VEC stores each plane as one
+// float4 and valid as one 32-bit word, the scalar path stores the same registers one by one (and handles W % 4 != 0).
+struct GroundView { float y, t, off, deg; bool ok; };
+
+template <bool ADAPTIVE>
+__device__ __forceinline__ GroundView ground_view(const float* __restrict__ logits_lr, const float* __restrict__ y_lr, float pe,
+                                                  const float* __restrict__ height, float depth_scale, float gain, int v, int h, int w,
+                                                  const Lerp& ly, const Lerp& lx) {
+  GroundView o;
+  if (ADAPTIVE) {
+    float lg[GE_NSLOPE];
+    GroundPix r;
+    const float hcam = height ? height[v] : 1.65f;
+    ground_pixel(logits_lr, y_lr, pe, hcam, depth_scale, v, h, w, ly, lx, lg, r);
+    o.y = r.y;
+    o.t = (r.off * r.m) * r.y;         // pe_mask of ground_embed_fwd_k
+    o.off = r.off;
+    o.deg = r.deg;
+    o.ok = r.m == 1.f;
+  } else {
+    o.y = tap4(y_lr + (long)v * h * w, w, ly, lx);
+    o.t = pe * o.y * gain;             // pe_mask of ground_vanilla_fwd_k
+    o.off = pe * gain;
+    o.deg = 0.f;
+    o.ok = pe > 0.f;
+  }
+  return o;
+}
+
+template <bool ADAPTIVE, bool VEC>
+__global__ void __launch_bounds__(256) ground_maps_k(const float* __restrict__ logits_lr, const float* __restrict__ y_lr,
+                                                     const float* __restrict__ pe, long pe_bs, const float* __restrict__ height,
+                                                     float depth_scale, float gain, int flip, float* __restrict__ maps,
+                                                     uint8_t* __restrict__ valid, int V, int h, int w, int H, int W) {
+  const float sy = ge_scale(h, H, false), sx = ge_scale(w, W, false);
+  const int Wg = (W + 3) >> 2;                               // VEC: W % 4 == 0 (checked by the launcher)
+  const long HW = (long)H * W, total = (long)H * Wg;
+  for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long)gridDim.x * blockDim.x) {
+    const int Y = (int)(idx / Wg), X0 = (int)(idx - (long)Y * Wg) << 2;
+    const Lerp ly = ge_lerp(Y, h, sy, false);
+    const long row = (long)Y * W;
+    float att[4], term[4], gd[4], deg[4];
+    uint8_t cnt[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int X = X0 + k;
+      att[k] = term[k] = gd[k] = deg[k] = 0.f;
+      cnt[k] = 0;
+      if (!VEC && X >= W) continue;
+      const GroundView a = ground_view<ADAPTIVE>(logits_lr, y_lr, pe[row + X], height, depth_scale, gain, 0, h, w, ly,
+                                                 ge_lerp(X, w, sx, false));
+      if (V == 2) {
+        const int X1 = flip ? W - 1 - X : X;                 // view 1 is the mirrored frame: its pixel of output column X
+        const GroundView b = ground_view<ADAPTIVE>(logits_lr, y_lr, pe[pe_bs + row + X1], height, depth_scale, gain, 1, h, w, ly,
+                                                   ge_lerp(X1, w, sx, false));
+        att[k] = (a.y + b.y) * 0.5f;
+        term[k] = (a.t + b.t) * 0.5f;
+        gd[k] = a.ok && b.ok ? (a.off + b.off) * 0.5f : a.ok ? a.off : b.ok ? b.off : 0.f;
+        deg[k] = (a.deg + b.deg) * 0.5f;
+        cnt[k] = (uint8_t)((a.ok ? 1 : 0) + (b.ok ? 1 : 0));
+      } else {
+        att[k] = a.y;
+        term[k] = a.t;
+        gd[k] = a.ok ? a.off : 0.f;
+        deg[k] = a.deg;
+        cnt[k] = (uint8_t)(a.ok ? 1 : 0);
+      }
+    }
+    float* o = maps + row + X0;
+    if (VEC) {
+      Vec<float, 4>::st(o, att);
+      Vec<float, 4>::st(o + HW, term);
+      Vec<float, 4>::st(o + 2 * HW, gd);
+      Vec<float, 4>::st(o + 3 * HW, deg);
+      *(uint32_t*)(valid + row + X0) = (uint32_t)cnt[0] | ((uint32_t)cnt[1] << 8) | ((uint32_t)cnt[2] << 16) | ((uint32_t)cnt[3] << 24);
+    } else {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        if (X0 + k >= W) break;
+        o[k] = att[k];
+        o[HW + k] = term[k];
+        o[2 * HW + k] = gd[k];
+        o[3 * HW + k] = deg[k];
+        valid[row + X0 + k] = cnt[k];
+      }
+    }
+  }
+}
+
+template <bool ADAPTIVE>
+static int ground_maps_launch(const float* logits_lr, const float* y_lr, const float* pe, long pe_bs, const float* height,
+                              float depth_scale, float gain, int flip, float* maps, uint8_t* valid, int V, int h, int w, int H, int W,
+                              hipStream_t s) {
+  const bool vec = W % 4 == 0 && (((uintptr_t)maps | (uintptr_t)valid) & 15) == 0;
+  const unsigned blocks = ge_blocks((long)H * ((W + 3) >> 2), 256, 65536);
+  if (vec)
+    ground_maps_k<ADAPTIVE, true><<<blocks, 256, 0, s>>>(logits_lr, y_lr, pe, pe_bs, height, depth_scale, gain, flip, maps, valid, V, h, w, H, W);
+  else
+    ground_maps_k<ADAPTIVE, false><<<blocks, 256, 0, s>>>(logits_lr, y_lr, pe, pe_bs, height, depth_scale, gain, flip, maps, valid, V, h, w, H, W);
+  GE_LAUNCH_CHECK();
+  return GE_OK;
+}
+
+extern "C" int ge_ground_maps(const float* logits_lr, const float* y_lr, const float* pe, long pe_bs, const float* height,
+                              float depth_scale, float gain, int flip, float* maps, uint8_t* valid, int V, int h, int w, int H, int W,
+                              void* stream) {
+  if (!y_lr || !pe || !maps || !valid || (V != 1 && V != 2) || h <= 0 || w <= 0 || H <= 0 || W <= 0) return GE_ERR_BAD_ARG;
+  if (logits_lr)
+    return ground_maps_launch<true>(logits_lr, y_lr, pe, pe_bs, height, depth_scale, gain, flip, maps, valid, V, h, w, H, W, ge_stream(stream));
+  return ground_maps_launch<false>(logits_lr, y_lr, pe, pe_bs, height, depth_scale, gain, flip, maps, valid, V, h, w, H, W, ge_stream(stream));
 }
 
 // ================================================================================== depth fusion

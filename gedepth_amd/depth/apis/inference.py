@@ -20,6 +20,7 @@ so a replayed graph follows it) and the forward's (1, Hd, Wd) map is the output.
 (``<pe_root>/<camera>/ddad_pe.npz``) and the height: the ``camera=`` argument, else the image path's parent directory.
 ``_KITTIFront`` / ``_DDADFront`` hold what the protocols do differently per frame; ``engine_for`` keeps a model's engines for every caller.
 """
+import gc
 import os.path as osp
 
 import numpy as np
@@ -27,13 +28,14 @@ import torch
 from PIL import Image
 
 from ... import kernels as K
+from ...ground_kernels import PLANES
 from ...mmrt.checkpoint import load_checkpoint
 from ...mmrt.config import Config
 from ..datasets.pipelines import loading    # _DDAD_CAMERA_HEIGHT is read through the module at every use, so a changed table is seen
 from ..models import build_depther
 from ..utils.pinned import PinnedUpload
 
-__all__ = ['init_depther', 'inference_depther', 'inference_point_cloud', 'DepthInferencer', 'kitti_front_spec', 'ddad_front_spec',
+__all__ = ['init_depther', 'inference_depther', 'inference_point_cloud', 'inference_ground', 'DepthInferencer', 'kitti_front_spec', 'ddad_front_spec',
            'front_spec']
 
 # test-time transforms of MultiScaleFlipAug the device front end restates (ImageToTensor / Collect are layout only)
@@ -271,6 +273,7 @@ class DepthInferencer:
         self._staging = PinnedUpload()
         self._pe = {}
         self.last_frame = None                   # KITTI: (device uint8 BGR frame, top, left) of the last call, for ``points``
+        self.static_ground = self.static_ground_valid = None      # (4, H, W) f32 / (H, W) u8 of ``ground_maps``, allocated at its first call
         self.reset()
 
     def reset(self):
@@ -317,8 +320,9 @@ class DepthInferencer:
         return torch.from_numpy(a).to(self.device).contiguous()
 
     # ---- one frame
-    def _key(self):
-        return (self.bf16,) + tuple(m.kernel_variant for m in self.model.modules() if hasattr(m, 'kernel_variant'))
+    def _key(self, ground=False):
+        key = (self.bf16,) + tuple(m.kernel_variant for m in self.model.modules() if hasattr(m, 'kernel_variant'))
+        return key + ('ground',) if ground else key
 
     def _metas(self, filename, shape, ori_shape):
         s = self.spec
@@ -327,14 +331,26 @@ class DepthInferencer:
                      pad_shape=tuple(shape) + (5,), scale_factor=1.0, flip=bool(v), flip_direction='horizontal', img_norm_cfg=norm)
                 for v in range(s['views'])]
 
-    def _body(self, metas):
-        with torch.no_grad(), torch.autocast('cuda', dtype=torch.bfloat16, enabled=self.bf16):
-            pred = self.model.encode_decode(self.static_in, metas, rescale=True, **self._forward_kw)
+    def _body(self, metas, ground=False):
+        model = self.model
+        model.keep_ground_lr = ground                # the forward keeps the two ground necks' low-resolution outputs for ge_ground_maps
+        try:
+            with torch.no_grad(), torch.autocast('cuda', dtype=torch.bfloat16, enabled=self.bf16):
+                pred = model.encode_decode(self.static_in, metas, rescale=True, **self._forward_kw)
+            lr, model.ground_lr = model.ground_lr, None
+        finally:
+            model.keep_ground_lr = False
         pred = pred.float().contiguous()
         if self.spec['views'] == 2:
             K.tta_merge(pred, self.static_out)
         else:
             self.static_out.copy_(pred[0])
+        if ground:
+            if lr is None:
+                raise NotImplementedError('ground_maps: the model has no ground embedding (no pe_mask_neck)')
+            # the model's own arguments: its depth_scale (the configs set it to the pipeline's), the vanilla branch's constant 200
+            K.ground_maps(*lr, self.static_in, self.static_height, model.depth_scale, 200.0, flip=self.spec['views'] == 2,
+                          out=self.static_ground, valid=self.static_ground_valid)
 
     def upload(self, bgr):
         """Host uint8 frame -> device, through a reused pinned buffer and a non-blocking copy on the current stream (``PinnedUpload``)."""
@@ -345,6 +361,21 @@ class DepthInferencer:
         ``to_host=False`` the static device buffer ``static_out`` itself, without synchronising: valid until the next call, and ordered on
         ``self.stream`` (the caller's current stream waits for it, as always).  ``camera`` (DDAD): the frame's camera, else the image
         path's parent directory; ``calib`` / ``cam_height`` belong to the KITTI protocol."""
+        return self._frame(img, pe, calib, cam_height, graph, to_host, camera, False)
+
+    def ground_maps(self, img, pe=None, calib=None, cam_height=1.65, graph=True, to_host=True, camera=None):
+        """One frame -> a dict with its map and the ground embedding's own maps, merged over the views as the map is: ``depth``
+        (1, H, W) as ``__call__`` returns it; ``attention`` (the ground attention y: the depth is ``relu(c) * (1 - y) + ground_term +
+        min_depth``), ``ground_term`` (the ground's share of that sum) and ``ground_depth`` (the slope-adjusted ground plane in metres,
+        averaged over the views where it is valid, 0 where none is), each (H, W) float32; ``slope_deg`` (H, W), the predicted road slope
+        in degrees, for an adaptive model only; ``valid`` (H, W) uint8, the number of views with a valid ground depth.  Arguments as in
+        ``__call__``.  ``ge_ground_maps`` (include/gedepth_ground.h) runs right after the merge, inside the captured graph, on the
+        low-resolution outputs of the two ground necks; the capture is keyed apart from ``__call__``'s, so the two modes keep one graph
+        each.  ``to_host=False``: views of the static buffers ``static_out`` / ``static_ground`` / ``static_ground_valid`` (allocated at
+        the first call of this method), valid until the next call and ordered on ``self.stream``."""
+        return self._frame(img, pe, calib, cam_height, graph, to_host, camera, True)
+
+    def _frame(self, img, pe, calib, cam_height, graph, to_host, camera, ground):
         bgr = _decode(img)
         H, W = bgr.shape[:2]
         path = img if isinstance(img, str) else None
@@ -354,32 +385,54 @@ class DepthInferencer:
         self.stream.wait_stream(cur)
         with torch.cuda.stream(self.stream):
             self.last_frame = self.front.fill(self, bgr, path, cam, pe, calib, cam_height)     # per frame: outside the graph
-            key = self._key()
+            if ground and self.static_ground is None:
+                s = self.spec
+                self.static_ground = torch.empty(4, s['height'], s['width'], device=self.device, dtype=torch.float32)
+                self.static_ground_valid = torch.empty(s['height'], s['width'], device=self.device, dtype=torch.uint8)
+            key = self._key(ground)
             g = self.graphs.get(key) if graph else None
             if graph and g is None and self.calls.get(key, 0) >= self.WARMUP:
                 g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g, stream=self.stream):
-                    self._body(metas)
+                # The cycle collector must not run inside the capture (torch.cuda.graph does not collect before it by default): a dead
+                # cycle it frees there (a model and the engine it kept, with pinned buffer, events and device tensors) makes runtime
+                # calls that a capturing thread may not make, and an error raised inside a destructor ends the process.  It runs again
+                # right after the capture.
+                collecting = gc.isenabled()
+                gc.disable()
+                try:
+                    with torch.cuda.graph(g, stream=self.stream):
+                        self._body(metas, ground)
+                finally:
+                    if collecting:
+                        gc.enable()
                 self.graphs[key] = g
                 self.captures += 1
             if g is not None:
                 g.replay()
             else:
-                self._body(metas)
+                self._body(metas, ground)
                 if graph:
                     self.calls[key] = self.calls.get(key, 0) + 1
             # to_host: synchronises the engine's stream; a fresh host array per frame
-            out = self.static_out.cpu().numpy() if to_host else self.static_out
+            if ground:
+                out = dict(zip(PLANES, self.static_ground), depth=self.static_out, valid=self.static_ground_valid)
+                if not self.model.dynamic_pe_neck_FLAGS:
+                    del out['slope_deg']
+                if to_host:
+                    out = {k: v.cpu().numpy() for k, v in out.items()}
+            else:
+                out = self.static_out.cpu().numpy() if to_host else self.static_out
         cur.wait_stream(self.stream)
         return out
 
-    def points(self, img, pe=None, calib=None, cam_height=1.65, graph=True, K=None, **cloud_kw):
+    def points(self, img, pe=None, calib=None, cam_height=1.65, graph=True, K=None, ground=False, **cloud_kw):
         """One frame -> the coloured points of its map, ``(records, count)`` device tensors as ``depth.utils.depth_to_points`` returns
         them for a CUDA map, without synchronising.  The frame runs as in ``__call__`` with ``to_host=False``; ``ge_depth_points`` then
         reads ``static_out``, the frame uploaded for this call and its KB-crop offsets on ``self.stream``, outside the captured graph (the
         capture and its key are those of ``__call__``).  Intrinsics: ``kitti_intrinsics(img, calib, K, the test tree)``, in frame
-        coordinates, shifted by the crop (``cx - left``, ``cy - top``).  ``cloud_kw``: ``min_depth`` / ``max_depth`` (default: the decode
-        head's), ``row0``, ``step``, ``alpha``."""
+        coordinates, shifted by the crop (``cx - left``, ``cy - top``).  ``ground``: run the frame as ``ground_maps`` does instead (its
+        graph; ``static_ground`` holds the frame's maps afterwards): the points need ``static_out`` and ``last_frame`` only, which both
+        modes fill.  ``cloud_kw``: ``min_depth`` / ``max_depth`` (default: the decode head's), ``row0``, ``step``, ``alpha``."""
         if self.ddad:
             raise NotImplementedError(_DDAD_NO_POINTS)
         from ...kernels import depth_points                  # the module's ``K`` is this method's intrinsics argument
@@ -388,7 +441,8 @@ class DepthInferencer:
         head = self.model.decode_head
         cloud_kw.setdefault('min_depth', head.min_depth)
         cloud_kw.setdefault('max_depth', head.max_depth)
-        depth = self(img, pe, calib, cam_height, graph, to_host=False)
+        depth = self.ground_maps(img, pe, calib, cam_height, graph, to_host=False)['depth'] if ground else \
+            self(img, pe, calib, cam_height, graph, to_host=False)
         dev, top, left = self.last_frame
         cur = torch.cuda.current_stream(self.device)
         with torch.cuda.stream(self.stream):
@@ -431,9 +485,16 @@ def inference_depther(model, img, pe=None, calib=None, cam_height=1.65, bf16=Fal
     With a DDAD config every frame needs its camera: ``camera`` (a name, or a list with one per frame), else the image path's parent
     directory.  The result is one (1, Hd, Wd) map per frame at DDADResize's shape — what ``simple_test`` returns; the ground depth comes
     from ``pe``, else from ``<pe_root>/<camera>/ddad_pe.npz``.  Without a camera: ``NotImplementedError``."""
+    imgs, pes, cams, config = _frames(model, img, pe, calib, camera)         # argument errors before any device work
+    eng = engine_for(model, bf16, config)
+    return [eng(i, p, calib, cam_height, graph, camera=c) for i, p, c in zip(imgs, pes, cams)]
+
+
+def _frames(model, img, pe, calib, camera):
+    """The per-frame lists and the argument errors of ``inference_depther``, before any device work -> (imgs, pes, cams, config)."""
     imgs = img if isinstance(img, list) else [img]
     pes = _per_frame(pe, len(imgs), '{n} ground-depth maps for {m} frames')
-    spec, prefix = config = _config_of(model)                                 # argument errors before any device work
+    spec, prefix = config = _config_of(model)
     cams = _per_frame(camera, len(imgs), '{n} cameras for {m} frames')
     if spec['protocol'] == 'ddad':
         if any(cam is None for cam in [_ddad_camera(c, i) for c, i in zip(cams, imgs)]):
@@ -443,8 +504,17 @@ def inference_depther(model, img, pe=None, calib=None, cam_height=1.65, bf16=Fal
                                       'the camera name')
     elif calib is None and any(p is None and _pe_file(spec, prefix, i) is None for i, p in zip(imgs, pes)):
         raise ValueError(_NO_PE)
+    return imgs, pes, cams, config
+
+
+def inference_ground(model, img, pe=None, calib=None, cam_height=1.65, bf16=False, graph=True, camera=None):
+    """The ground embedding's maps for each frame of ``img``: a list with one dict of host arrays per frame, as
+    ``DepthInferencer.ground_maps`` returns it (``depth``, ``attention``, ``ground_term``, ``ground_depth``, ``valid``, and ``slope_deg``
+    for an adaptive model).  Frames, ground depth, camera, ``bf16`` and ``graph`` as in ``inference_depther``, with the same argument
+    errors before any device work; ``BaseDepther.show_ground`` writes one such dict as pictures."""
+    imgs, pes, cams, config = _frames(model, img, pe, calib, camera)
     eng = engine_for(model, bf16, config)
-    return [eng(i, p, calib, cam_height, graph, camera=c) for i, p, c in zip(imgs, pes, cams)]
+    return [eng.ground_maps(i, p, calib, cam_height, graph, camera=c) for i, p, c in zip(imgs, pes, cams)]
 
 
 def inference_point_cloud(model, img, pe=None, calib=None, cam_height=1.65, bf16=False, graph=True, K=None, out_file=None, **cloud_kw):

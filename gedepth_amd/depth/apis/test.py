@@ -8,7 +8,11 @@ engine (apis/inference.py: flip-TTA for KITTI, the single view of DDADResize's s
 map to ten float64 sums on the engine's stream (csrc/eval.hip); the whole split comes back in one copy at the end.  For DDAD the kernel
 resamples the prediction at the ground-truth pixels in float32 (include/gedepth_ddad.h), which is not bit-equal to the host's
 ``F.interpolate``: the largest relative difference measured is 3.4e-7, so a threshold count can move by the pixels whose ratio lies that
-close to 1.25^p.  ``show`` / ``out_dir`` and ``mask_pe`` are not covered.  Speed: not measured."""
+close to 1.25^p.  ``show`` / ``out_dir`` and ``mask_pe`` are not covered.  Speed: not measured.
+
+``ground_dir`` writes every image's ground maps (``DepthInferencer.ground_maps`` -> ``show_ground``: attention, slope and ground-depth
+pictures, or one ``.npz`` under ``format_only``).  The maps exist on the engine's route only, so the frames go through the engine: alone
+(no result list), or in the same pass as ``device_eval``; with the host loop's ``pre_eval`` it raises.  Speed: not measured."""
 import os.path as osp
 
 import torch
@@ -68,42 +72,69 @@ def _show_batch(model, data, result_depth, show, out_dir, format_only, ply_dir=N
         depther.show_result(name, [depth], show=show, out_file=out_file, format_only=format_only)
 
 
-def _device_eval(model, data_loader, pre_eval, format_only, show, out_dir, ply_dir=None):
-    """The ``device_eval`` loop of ``single_gpu_test``: the list of metric tuples ``pre_eval`` yields, in the sampler's order."""
-    from ..core.evaluation import metrics_from_sums
+def _engine_frames(model, data_loader, what, evaluates=True):
+    """What the engine-backed loops share -> ``(depther, engine, indices in the sampler's order, their engine_frame arguments)``; every
+    refusal is raised before the first frame runs, in the words of loop ``what``."""
     from ..datasets.pipelines import loading
     from .inference import _config_of, engine_for
     dataset = data_loader.dataset
-    if not pre_eval or format_only:
-        raise NotImplementedError('device_eval reduces every map to metric sums on the device: it needs pre_eval=True and no format_only')
-    if show or out_dir or ply_dir:
-        raise NotImplementedError('device_eval with show / out_dir / ply_dir: the depth maps never reach the host')
     name, wants = type(dataset).__name__, getattr(dataset, 'device_protocol', None)
     if wants is None:
-        raise NotImplementedError(f'device_eval: {name} has no pre_eval_device (the KITTI and the DDAD protocol are evaluated on the device)')
+        raise NotImplementedError(f'{what}: {name} has no pre_eval_device (the KITTI and the DDAD protocol are evaluated on the device)')
     depther = getattr(model, 'module', model)
     if getattr(depther, 'cfg', None) is None:                            # this loop's own words for it
-        raise NotImplementedError('device_eval: model.cfg is missing (the engine reads the test protocol from it): build the model with '
+        raise NotImplementedError(f'{what}: model.cfg is missing (the engine reads the test protocol from it): build the model with '
                                   'init_depther or set model.cfg to its Config')
     spec, _ = config = _config_of(depther)                               # NotImplementedError names what the device front end lacks
     if spec['protocol'] != wants:                                        # before any attribute of the dataset is touched
-        raise NotImplementedError(f'device_eval: {name} is evaluated by the {wants} protocol, the model\'s test pipeline is the '
+        raise NotImplementedError(f'{what}: {name} is evaluated by the {wants} protocol, the model\'s test pipeline is the '
                                   f'{spec["protocol"]} protocol')
-    if wants == 'kitti' and (spec['height'], spec['width']) != (352, 1216):
-        raise NotImplementedError(f'device_eval: KBCrop {(spec["height"], spec["width"])}, the evaluation protocol crops (352, 1216)')
+    if evaluates and wants == 'kitti' and (spec['height'], spec['width']) != (352, 1216):
+        raise NotImplementedError(f'{what}: KBCrop {(spec["height"], spec["width"])}, the evaluation protocol crops (352, 1216)')
     bf16 = bool(torch.is_autocast_enabled('cuda') and torch.get_autocast_dtype('cuda') == torch.bfloat16)      # what the caller asks for
     eng = engine_for(depther, bf16, config)
     indices = [i for batch in data_loader.batch_sampler for i in batch]
     frames = [dataset.engine_frame(i) for i in indices]
     unknown = {f['camera'] for f in frames if 'camera' in f} - set(loading._DDAD_CAMERA_HEIGHT)       # DDAD; before the first frame runs
     if unknown:
-        raise ValueError(f'device_eval: the split holds frames of {", ".join(sorted(unknown))}; the cameras with '
+        raise ValueError(f'{what}: the split holds frames of {", ".join(sorted(unknown))}; the cameras with '
                          f'a known height are {", ".join(sorted(loading._DDAD_CAMERA_HEIGHT))} (set the dataset\'s cameras to these)')
+    return depther, eng, indices, frames
+
+
+def _ground_file(dataset, index, ground_dir):
+    """``ground_dir/replace_str(<the image's name in the split>)``: the name ``show_ground`` derives its files from."""
+    return osp.join(ground_dir, replace_str(dataset.img_infos[index]['filename']))
+
+
+def _ground_only(model, data_loader, ground_dir, format_only):
+    """``ground_dir`` without an evaluation: every frame through ``DepthInferencer.ground_maps`` and ``show_ground``; no results."""
+    depther, eng, indices, frames = _engine_frames(model, data_loader, 'ground_dir', evaluates=False)
+    for i, frame in zip(indices, frames):
+        depther.show_ground(eng.ground_maps(to_host=False, **frame), _ground_file(data_loader.dataset, i, ground_dir), format_only)
+    return []
+
+
+def _device_eval(model, data_loader, pre_eval, format_only, show, out_dir, ply_dir=None, ground_dir=None):
+    """The ``device_eval`` loop of ``single_gpu_test``: the list of metric tuples ``pre_eval`` yields, in the sampler's order."""
+    from ..core.evaluation import metrics_from_sums
+    dataset = data_loader.dataset
+    if not pre_eval or format_only:
+        raise NotImplementedError('device_eval reduces every map to metric sums on the device: it needs pre_eval=True and no format_only')
+    if show or out_dir or ply_dir:
+        raise NotImplementedError('device_eval with show / out_dir / ply_dir: the depth maps never reach the host')
+    depther, eng, indices, frames = _engine_frames(model, data_loader, 'device_eval')
     sums = torch.empty(max(len(indices), 1), 10, device=eng.device, dtype=torch.float64)
     for row, (i, frame) in enumerate(zip(indices, frames)):
-        pred = eng(to_host=False, **frame)
+        if ground_dir:
+            maps = eng.ground_maps(to_host=False, **frame)
+            pred = maps['depth']
+        else:
+            pred = eng(to_host=False, **frame)
         with torch.cuda.stream(eng.stream):
             dataset.pre_eval_device(pred, i, sums[row])
+        if ground_dir:
+            depther.show_ground(maps, _ground_file(dataset, i, ground_dir))
     with torch.cuda.stream(eng.stream):
         host = sums[:len(indices)].cpu().numpy()                       # the one copy (and the one synchronisation) of the loop
     torch.cuda.current_stream(eng.device).wait_stream(eng.stream)
@@ -111,15 +142,23 @@ def _device_eval(model, data_loader, pre_eval, format_only, show, out_dir, ply_d
 
 
 def single_gpu_test(model, data_loader, pre_eval=False, format_only=False, format_args=None, device=None, *, show=False,
-                    out_dir=None, device_eval=False, ply_dir=None):
+                    out_dir=None, device_eval=False, ply_dir=None, ground_dir=None):
     """Returns a list with one entry per image: the metric tuple (``pre_eval``) or the ``(1, H, W)`` depth map.  ``show`` / ``out_dir``:
     ``show_result`` of every image's map, written to ``out_dir/replace_str(ori_filename)`` (``format_only``: the raw map as
     ``out_dir/<ori_filename without extension>.npy``).  ``ply_dir``: every image's point cloud as ``ply_dir/<ori_filename with .ply>``
     (``save_point_cloud`` with the image's ``cam_intrinsic`` meta and its KB-crop offsets).  ``device_eval`` (with ``pre_eval``; KITTI or
-    DDAD protocol): the module docstring."""
+    DDAD protocol): the module docstring.  ``ground_dir``: every image's ground maps (module docstring); without ``device_eval`` the
+    result is an empty list."""
     model.eval()
     if device_eval:
-        return _device_eval(model, data_loader, pre_eval, format_only, show, out_dir, ply_dir)
+        return _device_eval(model, data_loader, pre_eval, format_only, show, out_dir, ply_dir, ground_dir)
+    if ground_dir:
+        if pre_eval:
+            raise NotImplementedError('ground_dir with the host loop\'s pre_eval: the ground maps exist on the engine\'s route only; '
+                                      'evaluate with device_eval=True (tools/test.py: --device-eval) in the same pass')
+        if show or out_dir or ply_dir:
+            raise NotImplementedError('ground_dir with show / out_dir / ply_dir: those are outputs of the host loop; run them apart')
+        return _ground_only(model, data_loader, ground_dir, format_only)
     dataset = data_loader.dataset
     if ply_dir:
         from ..datasets.ddad import DDADDataset
@@ -144,11 +183,11 @@ def single_gpu_test(model, data_loader, pre_eval=False, format_only=False, forma
 
 
 def multi_gpu_test(model, data_loader, pre_eval=False, format_only=False, format_args=None, device=None, *, show=False, out_dir=None,
-                   device_eval=False, ply_dir=None):
+                   device_eval=False, ply_dir=None, ground_dir=None):
     """Each rank evaluates its shard of a non-shuffled DistributedSampler; rank 0 receives the results in dataset order.  ``show`` /
-    ``out_dir`` / ``ply_dir`` / ``device_eval`` as in ``single_gpu_test``: every rank writes the files of its own shard."""
+    ``out_dir`` / ``ply_dir`` / ``ground_dir`` / ``device_eval`` as in ``single_gpu_test``: every rank writes the files of its own shard."""
     part = single_gpu_test(model, data_loader, pre_eval, format_only, format_args, device, show=show, out_dir=out_dir,
-                           device_eval=device_eval, ply_dir=ply_dir)
+                           device_eval=device_eval, ply_dir=ply_dir, ground_dir=ground_dir)
     rank, world = get_dist_info()
     if world == 1:
         return part

@@ -164,7 +164,30 @@ class BaseDepther(BaseModule, metaclass=ABCMeta):
             warnings.warn('show==False and out_file is not specified, only result depth will be returned')
             return depth
 
-    def save_point_cloud(self, img, result, cam_intrinsic, out_file, top=0, left=0, **cloud_kw):
+    def show_ground(self, result, out_file, format_only=False):
+        """Write one frame's ground maps, ``result`` = a dict of ``inference_ground`` / ``DepthInferencer.ground_maps`` (host arrays or
+        device tensors).  With ``<stem>`` = ``out_file`` without its extension: ``<stem>_attention.png`` (the ground attention over
+        [0, 1]), ``<stem>_slope.png`` (``slope_deg`` over [-5, 5]; skipped when the key is absent: a vanilla model) and
+        ``<stem>_ground.png`` (``ground_depth`` over ``[decode_head.min_depth, decode_head.max_depth]``), each ``colorize``d with
+        'magma_r' and written as ``show_result`` writes its picture.  ``format_only``: one ``<stem>.npz`` with every array of ``result``
+        as it is.  Parent directories are created."""
+        stem = osp.splitext(out_file)[0]
+        if format_only:
+            os.makedirs(osp.dirname(osp.abspath(stem)), exist_ok=True)
+            np.savez(stem + '.npz', **{k: _to_host(v) for k, v in result.items()})
+            return
+        from ...utils import colorize
+        head = self.decode_head
+        for key, suffix, vmin, vmax in (('attention', 'attention', 0.0, 1.0), ('slope_deg', 'slope', -5.0, 5.0),
+                                        ('ground_depth', 'ground', head.min_depth, head.max_depth)):
+            if key == 'slope_deg' and key not in result:
+                continue
+            bgr = _to_host(colorize(result[key], vmin=vmin, vmax=vmax))
+            if bgr.ndim != 3:
+                raise ValueError(f'show_ground writes one image per map: result[{key!r}] must be (H, W), got shape {np.shape(result[key])}')
+            _imwrite_bgr(bgr, f'{stem}_{suffix}.png')
+
+    def save_point_cloud(self,img, result, cam_intrinsic, out_file, top=0, left=0, **cloud_kw):
         """Write ``depth = result[0]`` (a host or device map) as a coloured point cloud, a binary PLY file (``depth.utils.write_ply``): the
         host-map route to ``depth.utils.depth_to_points``, like ``show_result`` for pictures.  ``img``: the frame, a path or an (Hs, Ws, 3)
         uint8 BGR array, whose pixel (top + r, left + c) colours map pixel (r, c) (KB crop: ``top = Hs - 352``, ``left = (Ws - 1216) // 2``).

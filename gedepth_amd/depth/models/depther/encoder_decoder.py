@@ -39,6 +39,10 @@ class DepthEncoderDecoder(BaseDepther):
         self.train_cfg, self.test_cfg = train_cfg, test_cfg
         assert self.with_decode_head
         self.last_valid_mask = None      # u8 (B,H,W) "pe_offset_mask" of the latest adaptive forward
+        # opt-in (the inference engine sets it around its forward): extract_feat keeps the low-resolution outputs of the two ground necks
+        # of that call in ``ground_lr`` = (slope logits or None, y), for kernels.ground_maps; off: nothing is retained
+        self.keep_ground_lr = False
+        self.ground_lr = None
 
     # ------------------------------------------------------------------ ground embedding
     @staticmethod
@@ -51,6 +55,8 @@ class DepthEncoderDecoder(BaseDepther):
     def dynamic_pe(self, x, y_lr, img, img_metas, **kwargs):
         """-> (pe_mask, slope logits at image resolution, y at image resolution)."""
         logits_lr = self.dynamic_pe_neck(x)
+        if self.keep_ground_lr:
+            self.ground_lr = (logits_lr, y_lr)
         pe_mask, logits_hr, y_hr, valid = ground_embed_adaptive(logits_lr, y_lr, img, self._height(kwargs),
                                                                 self.depth_scale)
         self.last_valid_mask = valid
@@ -68,6 +74,8 @@ class DepthEncoderDecoder(BaseDepther):
         if self.dynamic_pe_neck_FLAGS:
             pe_mask, logits_hr, y = self.dynamic_pe(x, y_lr, img, img_metas, **kwargs)
             return x, y, pe_mask, logits_hr
+        if self.keep_ground_lr:
+            self.ground_lr = (None, y_lr)
         pe_mask, y = ground_embed_vanilla(y_lr, img, 200.0)       # hard-coded 200 (reference :122)
         return x, y, pe_mask, None
 

@@ -1,11 +1,13 @@
 """ctypes binding of libgedepth_hip.so (C ABI: include/gedepth_hip.h, include/gedepth_eval.h for the KITTI evaluation entry points,
-include/gedepth_ddad.h for the DDAD test protocol and include/gedepth_cloud.h for the point clouds).
+include/gedepth_ddad.h for the DDAD test protocol, include/gedepth_cloud.h for the point clouds and include/gedepth_ground.h for the ground
+embedding's maps).
 
 The header is the only statement of the ABI: ``SIGNATURES`` (name -> (restype, argtypes)) is parsed from it at import, so a new entry
 point is declared there and nowhere else.  ``call(name, *args)`` launches an entry point that returns an error code and raises on a
 non-zero one; size queries and predicates that return a value are called on ``lib()`` directly.  ``EVAL_SIGNATURES`` is the same table
-for include/gedepth_eval.h, ``DDAD_SIGNATURES`` for include/gedepth_ddad.h and ``CLOUD_SIGNATURES`` for include/gedepth_cloud.h, whose
-entry points stay outside the versioned ABI of gedepth_hip.h; ``HEADERS`` names the four and ``lib()`` binds them all.
+for include/gedepth_eval.h, ``DDAD_SIGNATURES`` for include/gedepth_ddad.h, ``CLOUD_SIGNATURES`` for include/gedepth_cloud.h and
+``GROUND_SIGNATURES`` for include/gedepth_ground.h, whose entry points stay outside the versioned ABI of gedepth_hip.h; ``HEADERS`` names the
+five and ``lib()`` binds them all.
 
 There is deliberately NO fallback: if the shared library is missing, or a tensor is not a
 contiguous CUDA(HIP) tensor of the expected dtype, the call raises.  Build the library with
@@ -20,7 +22,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('GE_LIB') or os.path.join(_HERE, 'csrc', 'libgedepth_hip.so')     # GE_LIB: a differently built library (A/B timing)
 HEADERS = {'SIGNATURES': 'gedepth_hip.h', 'EVAL_SIGNATURES': 'gedepth_eval.h', 'DDAD_SIGNATURES': 'gedepth_ddad.h',
-           'CLOUD_SIGNATURES': 'gedepth_cloud.h'}      # table name -> its header under include/, in binding order
+           'CLOUD_SIGNATURES': 'gedepth_cloud.h', 'GROUND_SIGNATURES': 'gedepth_ground.h'}      # table name -> its header under include/, in binding order
 GE_F32, GE_BF16 = 0, 1
 GE_COLORIZE_VMIN_DATA, GE_COLORIZE_VMAX_DATA, GE_COLORIZE_EQUAL = 1, 2, 4      # ge_depth_colorize flags
 

@@ -2110,3 +2110,6 @@ from .eval_kernels import depth_metric_sums, depth_metric_sums_resized, infer_fr
 
 # --------------------------------------------------------------------- point clouds (csrc/cloud.hip, include/gedepth_cloud.h)
 from .cloud_kernels import depth_points  # noqa: E402,F401
+
+# --------------------------------------------------------------------- the ground embedding's maps (csrc/ground.hip, include/gedepth_ground.h)
+from .ground_kernels import ground_maps  # noqa: E402,F401

@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """Evaluate / run a depther — CLI of the reference's tools/test.py:21-68 (config, checkpoint, --eval, --options, --out,
---format-only, --show, --show-dir, --eval-options, --launcher), plus --ply-dir.
+--format-only, --show, --show-dir, --eval-options, --launcher), plus --ply-dir and --ground-dir.
 
 With a KITTI tree at ``cfg.data.test.data_root`` this is the Eigen-split protocol of the reference: test pipeline with
 flip test-time augmentation, ``forward_test`` (``return_loss=False``), KB crop + Garg crop, per-image metrics, nan-mean
@@ -13,6 +13,12 @@ raw maps as ``.npy``, ``--out FILE.pkl`` pickles the results list (metric tuples
 ``--launcher pytorch`` (tools/dist_test.sh) evaluates one shard per rank with ``multi_gpu_test``.  ``--ply-dir DIR`` writes one coloured
 point cloud per test image, ``DIR/<ori_filename with .ply>`` (binary PLY; ``BaseDepther.save_point_cloud`` with the image's ``cam_intrinsic``
 meta and its KB-crop offsets); it combines with ``--show-dir``.
+
+``--ground-dir DIR`` writes the ground embedding's maps of every test image: ``DIR/<name>_attention.png`` (where the model relies on the
+ground, over [0, 1]), ``<name>_slope.png`` (the predicted slope over [-5, 5] degrees; adaptive models) and ``<name>_ground.png`` (the
+slope-adjusted ground depth), or with ``--format-only`` one ``<name>.npz`` of the raw arrays (``BaseDepther.show_ground``).  The frames go
+through the graphed engine (``DepthInferencer.ground_maps``): alone, or with ``--eval ... --device-eval`` in the same pass; with a host-loop
+``--eval`` it raises.
 
 ``--device-eval`` (with ``--eval`` and ``--synthetic 0``; KITTI or DDAD protocol) evaluates on the device: frames go through the graphed
 engine (flip-TTA for KITTI, the single view for DDAD) and each map is reduced to its metric sums by a HIP kernel, so no map is copied to the
@@ -53,6 +59,8 @@ def parse_args(argv=None):
     p.add_argument('--show', action='store_true', help='show results (no display support here: warns and shows nothing)')
     p.add_argument('--show-dir', help='directory where the colorized depth maps (or, with --format-only, the raw .npy maps) are saved')
     p.add_argument('--ply-dir', help='directory where one coloured point cloud per test image is saved as a binary .ply')
+    p.add_argument('--ground-dir', help='directory where the ground attention / slope / ground-depth pictures of every test image (or, with '
+                                        '--format-only, one .npz of the raw maps) are saved; runs the graphed engine')
     p.add_argument('--eval-options', nargs='+', default=None, help='k=v options for evaluate / format_results')
     p.add_argument('--launcher', choices=['none', 'pytorch'], default='none', help='job launcher (pytorch: torch.distributed.run)')
     p.add_argument('--local_rank', '--local-rank', type=int, default=0)
@@ -66,6 +74,10 @@ def parse_args(argv=None):
         raise ValueError('--eval and --format-only cannot be both specified')
     if args.device_eval and (not args.eval or args.synthetic != 0 or args.show or args.show_dir or args.ply_dir):
         raise ValueError('--device-eval needs --eval and --synthetic 0, and cannot be combined with --show / --show-dir / --ply-dir')
+    if args.ground_dir and args.eval and not args.device_eval:
+        raise ValueError('--ground-dir with --eval needs --device-eval: the ground maps come from the graphed engine, not from the host loop')
+    if args.ground_dir and (args.show or args.show_dir or args.ply_dir or args.out):
+        raise ValueError('--ground-dir cannot be combined with --show / --show-dir / --ply-dir / --out: those are outputs of the host loop')
     if args.out is not None and not args.out.endswith(('.pkl', '.pickle')):
         raise ValueError('The output file must be a pkl file.')
     return args
@@ -95,7 +107,8 @@ def run_dataset(args, cfg):
     test = multi_gpu_test if distributed else single_gpu_test
     with torch.autocast('cuda', dtype=torch.bfloat16, enabled=args.bf16):
         results = test(model, loader, pre_eval=args.eval is not None, format_only=args.format_only, format_args=eval_kwargs,
-                       show=args.show, out_dir=args.show_dir, device_eval=args.device_eval, ply_dir=args.ply_dir)
+                       show=args.show, out_dir=args.show_dir, device_eval=args.device_eval, ply_dir=args.ply_dir,
+                       ground_dir=args.ground_dir)
     rank, _ = get_dist_info()
     if rank == 0:
         if args.out:
@@ -116,7 +129,7 @@ def main():
         cfg.merge_from_dict(DictAction.parse(args.options))
     cfg.model.pretrained = None
     cfg.model.train_cfg = None
-    if args.out or args.format_only or args.show or args.show_dir or args.ply_dir or args.launcher == 'pytorch':
+    if args.out or args.format_only or args.show or args.show_dir or args.ply_dir or args.ground_dir or args.launcher == 'pytorch':
         return run_dataset(args, cfg)
     model = build_depther(cfg.model, test_cfg=cfg.get('test_cfg'))
     if args.checkpoint:
