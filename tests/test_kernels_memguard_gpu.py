@@ -23,7 +23,9 @@ import pytest
 import torch
 
 import memguard
+import conv_exact
 import test_conv1x1_bn_gpu as CB
+import test_conv_exact_gpu as TX
 import test_inference_gpu as TI
 import test_kernels_gpu as TK
 import test_msda_hist_batched_gpu as HB
@@ -112,6 +114,20 @@ CASES = [
                       ((2, 64, 7, 9), 1024, True))], CB.test_one_row(c.dev))),
     Case('conv1x1 as token GEMM', set(), lambda c: TK.test_conv1x1_as_token_gemm_vs_fp32_conv(c.dev, (2, 96, 24, 40), 512)),
     Case('conv1x1_wgrad', {'ge_conv1x1_nhwc_wgrad'}, lambda c: TK.test_conv1x1_wgrad_vs_float64(c.dev, (1, 64, 544, 30, 33), c.monkeypatch)),
+    # ---- the convolution kernels bit for bit on integer data (test_conv_exact_gpu.py): the prefetching, persistent and split-K loops past their
+    # first tile / unit / stage, and a Cout that is a multiple of 8 only
+    Case('conv3x3 exact v1', {'ge_conv3x3_nhwc_fwd', 'ge_conv3x3_nhwc_wgrad', 'ge_bias_act_nhwc_bwd'},
+         lambda c: TX.test_conv3x3_exact(c.dev, (2, 96, 96, 9, 33), 0.5, '1', c.monkeypatch)),
+    Case('conv3x3 exact v2', {'ge_conv3x3_nhwc_fwd', 'ge_conv3x3_nhwc_wgrad', 'ge_bias_act_nhwc_bwd'},
+         lambda c: TX.test_conv3x3_exact(c.dev, (2, 96, 96, 17, 33), 0.0, '2', c.monkeypatch)),
+    Case('conv3x3 exact C ABI Cout 40', {'ge_conv3x3_nhwc_fwd', 'ge_conv3x3_nhwc_wgrad'},
+         _each(lambda c, v: TX.test_conv3x3_c_abi_partial_cout(c.dev, 40, v, c.monkeypatch), ('1', '2'))),
+    Case('conv3x3_wgrad exact several tiles per workgroup', {'ge_conv3x3_nhwc_wgrad'},
+         lambda c: TX.test_conv3x3_wgrad_several_tiles_per_workgroup(c.dev, 0.5)),
+    Case('conv3x3_c1 exact several units per workgroup', {'ge_conv3x3_c1_fwd', 'ge_conv3x3_c1_bwd'},
+         _each(lambda c, f: TX.test_conv3x3_c1_exact(c.dev, conv_exact.C1_MULTI_UNIT_BWD, 'bwd-walks', f), (False, True))),
+    Case('conv1x1_wgrad exact several stages per workgroup', {'ge_conv1x1_nhwc_wgrad'},
+         lambda c: TX.test_conv1x1_wgrad_exact(c.dev, 192, 544, 'stages', c.monkeypatch)),
     # ---- token GEMM and its epilogues
     Case('gemm_nt', {'ge_gemm_nt'}, _each(lambda c, s, b: TK.test_gemm_nt_vs_float64(c.dev, s, b), ((255, 8, 8), (257, 72, 8), (513, 136, 520), (1000, 520, 264)), (True, False))),
     Case('bias_gelu', {'ge_bias_gelu_fwd', 'ge_bias_gelu_bwd'},
@@ -208,7 +224,7 @@ def test_guarded(dev, monkeypatch, golden, case, poison):
     # cached per-stream workspaces / accumulators made by earlier (unguarded) tests would bypass the frames
     for cache in ('_LN_ACC', '_COLSUM_WS', '_POS_ROWS', '_TILE_ORDER_CACHE', '_MM_VALUE_CHOICE'):
         monkeypatch.setattr(kernels, cache, {})
-    guard.install(monkeypatch, [kernels, optim, TK, TI, HB, CB], binding=hip, frame_copies_on=dev)
+    guard.install(monkeypatch, [kernels, optim, TK, TI, HB, CB, TX], binding=hip, frame_copies_on=dev)
     failure = None
     try:
         case.run(Ctx(dev, monkeypatch, golden))           # 2. the value test's own comparisons, NaN-strict
