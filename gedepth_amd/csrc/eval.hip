@@ -11,57 +11,10 @@
 // its groups of four pixels, a wave folds its lanes with shuffles, a workgroup folds its four waves through LDS and stores ten doubles to
 // partials[block]; metrics_fold_k, one workgroup on the same stream, adds the partials in index order.  Same bits on every run.
 #pragma clang fp contract(off)
-#include "common.h"
+#include "eval_sums.h"
 #include "../../include/gedepth_eval.h"
 #include "../../include/gedepth_ddad.h"
 
-#define GE_EVAL_THREADS 256
-#define GE_EVAL_GROUPS 2           // groups of four pixels per lane before the grid-stride loop goes round again
-#define GE_EVAL_MAX_BLOCKS 1024
-#define GE_EVAL_SUMS 10
-
-struct EvalArgs { int W, top, left, Hc, Wc, r0, r1, c0, c1; float scale, lo, hi; };
-
-// One pixel: `gt` in metres (f32), `inside` = it lies in the protocol's rectangle; it counts when also lo < gt < hi.
-__device__ __forceinline__ void metric_pixel(float p, float gt, bool inside, float lo, float hi, double acc[GE_EVAL_SUMS]) {
-  if (!(inside && gt > lo && gt < hi)) return;
-  const float q0 = gt / p, q1 = p / gt;
-  const float ratio = (q0 > q1 || q0 != q0) ? q0 : q1;               // numpy.maximum: NaN wins
-  acc[0] += 1.0;
-  acc[1] += ratio < 1.25f ? 1.0 : 0.0;
-  acc[2] += ratio < 1.5625f ? 1.0 : 0.0;
-  acc[3] += ratio < 1.953125f ? 1.0 : 0.0;
-  const double g = (double)gt, q = (double)p;
-  const double d = g - q, d2 = d * d;
-  const double l = log(q) - log(g);
-  acc[4] += fabs(d) / g;
-  acc[5] += d2 / g;
-  acc[6] += d2;
-  acc[7] += l;
-  acc[8] += l * l;
-  acc[9] += fabs(log10(g) - log10(q));
-}
-
-// lane sums -> wave (shuffles) -> workgroup (LDS across the four waves) -> partials[block]
-__device__ __forceinline__ void metrics_block_fold(double acc[GE_EVAL_SUMS], double (*red)[GE_EVAL_SUMS], double* __restrict__ partials) {
-#pragma unroll
-  for (int k = 0; k < GE_EVAL_SUMS; ++k)
-    for (int s = GE_WAVE / 2; s > 0; s >>= 1) acc[k] += __shfl_down(acc[k], s, GE_WAVE);
-  const int wave = threadIdx.x / GE_WAVE, lane = threadIdx.x % GE_WAVE;
-  if (lane == 0) {
-#pragma unroll
-    for (int k = 0; k < GE_EVAL_SUMS; ++k) red[wave][k] = acc[k];
-  }
-  __syncthreads();
-  if (threadIdx.x < GE_EVAL_SUMS) {
-    double s = red[0][threadIdx.x];
-    for (int w = 1; w < GE_EVAL_THREADS / GE_WAVE; ++w) s += red[w][threadIdx.x];
-    partials[(long)blockIdx.x * GE_EVAL_SUMS + threadIdx.x] = s;
-  }
-}
-
-// PV: pred is 16-byte aligned and Wc % 4 == 0 (one float4 per group).  GV (only with PV): every group's four ground-truth values are
-// 8-byte aligned (W % 4 == 0, left % 4 == 0, base 8-byte aligned).  Otherwise element loads, each one bounds-checked against Wc.
 template <bool PV, bool GV>
 __global__ void __launch_bounds__(GE_EVAL_THREADS) metrics_partial_k(const float* __restrict__ pred, const uint16_t* __restrict__ gt_raw,
                                                                      EvalArgs a, double* __restrict__ partials) {
@@ -69,34 +22,8 @@ __global__ void __launch_bounds__(GE_EVAL_THREADS) metrics_partial_k(const float
   double acc[GE_EVAL_SUMS];
 #pragma unroll
   for (int k = 0; k < GE_EVAL_SUMS; ++k) acc[k] = 0.0;
-  const int G = (a.Wc + 3) >> 2;                                      // groups per row
-  const long items = (long)a.Hc * G;
-  for (long it = (long)blockIdx.x * GE_EVAL_THREADS + threadIdx.x; it < items; it += (long)gridDim.x * GE_EVAL_THREADS) {
-    const int r = (int)(it / G), c = 4 * (int)(it - (long)r * G);
-    if (r < a.r0 || r >= a.r1 || c + 4 <= a.c0 || c >= a.c1) continue;        // nothing of this group is in the rectangle: no loads
-    const float* ps = pred + (long)r * a.Wc + c;
-    const uint16_t* gs = gt_raw + (long)(a.top + r) * a.W + a.left + c;
-    float p[4];
-    uint16_t raw[4];
-    if (PV) {
-      const float4 t = *(const float4*)ps;
-      p[0] = t.x; p[1] = t.y; p[2] = t.z; p[3] = t.w;
-    } else {
-#pragma unroll
-      for (int k = 0; k < 4; ++k) p[k] = c + k < a.Wc ? ps[k] : 1.f;
-    }
-    if (PV && GV) {
-      const uint2 t = *(const uint2*)gs;
-      raw[0] = (uint16_t)t.x; raw[1] = (uint16_t)(t.x >> 16); raw[2] = (uint16_t)t.y; raw[3] = (uint16_t)(t.y >> 16);
-    } else {
-#pragma unroll
-      for (int k = 0; k < 4; ++k) raw[k] = c + k < a.Wc ? gs[k] : (uint16_t)0;
-    }
-#pragma unroll
-    for (int k = 0; k < 4; ++k)                                                   // gt = (float)raw / depth_scale; c1 <= Wc covers the row's tail
-      metric_pixel(p[k], (float)raw[k] / a.scale, c + k >= a.c0 && c + k < a.c1, a.lo, a.hi, acc);
-  }
-  metrics_block_fold(acc, red, partials);
+  metrics_window_sums<PV, GV>(pred, gt_raw, a, acc);                  // eval_sums.h
+  metrics_block_fold(acc, red, partials + (long)blockIdx.x * GE_EVAL_SUMS);
 }
 
 // DDAD protocol (depth/datasets/ddad.py pre_eval): the (h, w) prediction is resized bilinearly, align_corners = True, to the (H, W) ground
@@ -146,7 +73,7 @@ __global__ void __launch_bounds__(GE_EVAL_THREADS) metrics_resized_partial_k(con
       metric_pixel(p, g[k], inside, a.lo, a.hi, acc);
     }
   }
-  metrics_block_fold(acc, red, partials);
+  metrics_block_fold(acc, red, partials + (long)blockIdx.x * GE_EVAL_SUMS);
 }
 
 __global__ void __launch_bounds__(GE_WAVE) metrics_fold_k(const double* __restrict__ partials, int blocks, double* __restrict__ sums) {
@@ -154,10 +81,6 @@ __global__ void __launch_bounds__(GE_WAVE) metrics_fold_k(const double* __restri
   double s = 0.0;
   for (int b = 0; b < blocks; ++b) s += partials[(long)b * GE_EVAL_SUMS + threadIdx.x];
   sums[threadIdx.x] = s;
-}
-
-static inline unsigned metrics_blocks(int Hc, int Wc) {
-  return ge_blocks((long)Hc * ((Wc + 3) >> 2), GE_EVAL_THREADS * GE_EVAL_GROUPS, GE_EVAL_MAX_BLOCKS);
 }
 
 extern "C" size_t ge_depth_metrics_workspace(int Hc, int Wc) {

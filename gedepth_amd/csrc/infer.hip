@@ -11,44 +11,14 @@
 #include "common.h"
 #include "../../include/gedepth_ddad.h"
 
-struct InferNorm { double mean[3], stdinv[3]; float pe_max, depth_scale; int to_rgb; };
-
 // dst (views, 5, Hc, Wc) planar f32; view 1 = view 0 mirrored horizontally.  Wc % 4 == 0, dst 16-byte aligned (checked by the caller).
+// The group's body is ge_infer_front_group of common.h, which ge_infer_front_batch (infer_batch.hip) runs per frame too.
 __global__ void __launch_bounds__(256) infer_front_k(const uint8_t* __restrict__ bgr, const float* __restrict__ pe, float* __restrict__ dst,
                                                      int W, int top, int left, int Hc, int Wc, int views, InferNorm p) {
   const int G = Wc >> 2;                                   // float4 groups per output row
   const long n = (long)Hc * Wc, groups = (long)Hc * G;
-  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < groups; i += (long)gridDim.x * 256) {
-    const int y = (int)(i / G), g = (int)(i - (long)y * G);
-    const long s = (long)(y + top) * W + (left + 4 * g);
-    const uint8_t* px = bgr + s * 3;
-    float o[5][4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-#pragma unroll
-      for (int c = 0; c < 3; ++c) {
-        // ge_aug_load: (float)u8; ge_aug_color_normalize: truncf (a no-op on a uint8 value), BGR -> RGB, f64 (x - mean) * (1 / std)
-        const float t = truncf((float)px[3 * k + c]);
-        const int oc = p.to_rgb ? 2 - c : c;
-        o[oc][k] = (float)(((double)t - p.mean[oc]) * p.stdinv[oc]);
-      }
-      const float raw = pe[s + k];
-      float f = raw;                                        // LoadImageFromFile: > pe_max or < 0 zeroed; Normalize: / depth_scale where > 0
-      if (f > p.pe_max) f = 0.f;
-      if (f < 0.f) f = 0.f;
-      if (f > 0.f) f = f / p.depth_scale;
-      o[3][k] = f;
-      o[4][k] = raw;
-    }
-    const long r = (long)y * Wc;
-#pragma unroll
-    for (int c = 0; c < 5; ++c) *(float4*)(dst + c * n + r + 4 * g) = make_float4(o[c][0], o[c][1], o[c][2], o[c][3]);
-    if (views == 2) {
-      float* d1 = dst + 5 * n + r + (Wc - 4 - 4 * g);      // ge_aug_window(flip): x -> Wc - 1 - x
-#pragma unroll
-      for (int c = 0; c < 5; ++c) *(float4*)(d1 + c * n) = make_float4(o[c][3], o[c][2], o[c][1], o[c][0]);
-    }
-  }
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < groups; i += (long)gridDim.x * 256)
+    ge_infer_front_group(bgr, pe, dst, W, top, left, Wc, views, p, i, G, n);
 }
 extern "C" int ge_infer_front(const uint8_t* bgr_hwc, const float* pe, float* dst, int H, int W, int top, int left, int Hc, int Wc,
                               int views, float pe_max, const double* mean3, const double* std3, float depth_scale, int to_rgb,
@@ -127,13 +97,7 @@ extern "C" int ge_infer_front_ddad(const uint8_t* bgr_hwc, const float* pe, floa
 __global__ void __launch_bounds__(256) tta_merge_k(const float* __restrict__ src, float* __restrict__ dst, int H, int W) {
   const int G = W >> 2;
   const long n = (long)H * W, groups = (long)H * G;
-  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < groups; i += (long)gridDim.x * 256) {
-    const int y = (int)(i / G), g = (int)(i - (long)y * G);
-    const long r = (long)y * W;
-    const float4 a = *(const float4*)(src + r + 4 * g);
-    const float4 b = *(const float4*)(src + n + r + (W - 4 - 4 * g));
-    *(float4*)(dst + r + 4 * g) = make_float4((a.x + b.w) / 2.f, (a.y + b.z) / 2.f, (a.z + b.y) / 2.f, (a.w + b.x) / 2.f);
-  }
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < groups; i += (long)gridDim.x * 256) ge_tta_merge_group(src, dst, W, i, G, n);
 }
 extern "C" int ge_tta_merge(const float* src, float* dst, int H, int W, void* stream) {
   if (!src || !dst || H <= 0 || W <= 0) return GE_ERR_BAD_ARG;

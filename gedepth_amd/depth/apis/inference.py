@@ -19,6 +19,7 @@ A DDAD config (``front_spec(cfg)['protocol'] == 'ddad'``) takes LoadDDADImageFro
 so a replayed graph follows it) and the forward's (1, Hd, Wd) map is the output.  The frame's camera names the ground depth
 (``<pe_root>/<camera>/ddad_pe.npz``) and the height: the ``camera=`` argument, else the image path's parent directory.
 ``_KITTIFront`` / ``_DDADFront`` hold what the protocols do differently per frame; ``engine_for`` keeps a model's engines for every caller.
+``inference_depther(batch=F)`` runs F KITTI frames per forward instead (apis/batch_inference.py); ``batch=1``, the default, is this engine.
 """
 import gc
 import os.path as osp
@@ -456,14 +457,21 @@ _DDAD_NO_POINTS = ('point clouds on a DDAD engine: DDADResize feeds the network 
                    'a frame the caller has resized serves DDAD maps')
 
 
-def engine_for(model, bf16=False, config=None):
-    """The engine of ``model`` and ``bf16`` in ``model._ge_inferencers``, rebuilt when ``config`` (default ``_config_of(model)``) has changed."""
+def engine_for(model, bf16=False, config=None, batch=1):
+    """The engine of ``model``, ``bf16`` and ``batch`` frame slots in ``model._ge_inferencers``, rebuilt when ``config`` (default
+    ``_config_of(model)``) has changed.  ``batch=1``: the ``DepthInferencer`` under key ``bf16``; ``batch=F > 1``: a
+    ``BatchDepthInferencer`` (apis/batch_inference.py) under key ``(bf16, F)``."""
     spec, prefix = config = config or _config_of(model)
     engines = model.__dict__.setdefault('_ge_inferencers', {})
     bf16 = bool(bf16)
-    if bf16 not in engines or engines[bf16].spec != spec or engines[bf16].prefix != prefix:
-        engines[bf16] = DepthInferencer(model, bf16, config)
-    return engines[bf16]
+    key = bf16 if batch == 1 else (bf16, batch)
+    if key not in engines or engines[key].spec != spec or engines[key].prefix != prefix:
+        if batch == 1:
+            engines[key] = DepthInferencer(model, bf16, config)
+        else:
+            from .batch_inference import BatchDepthInferencer
+            engines[key] = BatchDepthInferencer(model, batch, bf16, config)
+    return engines[key]
 
 
 def _per_frame(value, n, error):
@@ -474,7 +482,7 @@ def _per_frame(value, n, error):
     return values
 
 
-def inference_depther(model, img, pe=None, calib=None, cam_height=1.65, bf16=False, graph=True, camera=None):
+def inference_depther(model, img, pe=None, calib=None, cam_height=1.65, bf16=False, graph=True, camera=None, batch=1):
     """Depth for each frame of ``img`` (a path, an (H, W, 3) uint8 BGR array, or a list of these): a list with one (1, 352, 1216)
     float32 array per frame — what ``model(return_loss=False, rescale=True, **data)`` returns for that frame through the config's test
     pipeline.  The raw (H, W) ground depth at frame size comes from ``pe`` (array or device tensor; a list: one per frame), else from
@@ -482,10 +490,25 @@ def inference_depther(model, img, pe=None, calib=None, cam_height=1.65, bf16=Fal
     size), else from ``<date>/pe/pe_165.npy`` of an image path inside ``cfg.data.test.data_root/img_dir``.  ``bf16``: the forward under
     bf16 autocast.  ``graph``: replay a captured hipGraph of forward + merge after two eager calls (``DepthInferencer``).
 
+    ``batch=F`` (2 .. 8; KITTI protocol): the list runs F frames per forward through a ``BatchDepthInferencer`` (apis/batch_inference.py),
+    the next batch's files decoding on a small thread pool meanwhile; the result is the same list in the same order.  The frames of a
+    batch may differ in size.  Every argument error — also a frame smaller than the crop — is raised for the whole list before any
+    device work.  With a DDAD config ``batch > 1`` raises ``NotImplementedError``.
+
     With a DDAD config every frame needs its camera: ``camera`` (a name, or a list with one per frame), else the image path's parent
     directory.  The result is one (1, Hd, Wd) map per frame at DDADResize's shape — what ``simple_test`` returns; the ground depth comes
     from ``pe``, else from ``<pe_root>/<camera>/ddad_pe.npz``.  Without a camera: ``NotImplementedError``."""
-    imgs, pes, cams, config = _frames(model, img, pe, calib, camera)         # argument errors before any device work
+    if batch != 1:                                                            # argument errors before any device work
+        from .batch_inference import check_batch, frame_size
+        check_batch(batch, _config_of(model)[0])
+    imgs, pes, cams, config = _frames(model, img, pe, calib, camera)
+    if batch != 1:
+        spec = config[0]
+        for i in imgs:
+            H, W = frame_size(i)
+            if H < spec['height'] or W < spec['width']:
+                raise ValueError(f'frame {(H, W)} is smaller than the KB crop {(spec["height"], spec["width"])}')
+        return engine_for(model, bf16, config, batch).run(imgs, pes, calib, cam_height, graph)
     eng = engine_for(model, bf16, config)
     return [eng(i, p, calib, cam_height, graph, camera=c) for i, p, c in zip(imgs, pes, cams)]
 

@@ -8,7 +8,9 @@ engine (apis/inference.py: flip-TTA for KITTI, the single view of DDADResize's s
 map to ten float64 sums on the engine's stream (csrc/eval.hip); the whole split comes back in one copy at the end.  For DDAD the kernel
 resamples the prediction at the ground-truth pixels in float32 (include/gedepth_ddad.h), which is not bit-equal to the host's
 ``F.interpolate``: the largest relative difference measured is 3.4e-7, so a threshold count can move by the pixels whose ratio lies that
-close to 1.25^p.  ``show`` / ``out_dir`` and ``mask_pe`` are not covered.  Speed: not measured.
+close to 1.25^p.  ``show`` / ``out_dir`` and ``mask_pe`` are not covered.  ``eval_batch=F`` (KITTI protocol, 2 .. 8) runs F frames per forward through the
+batched engine (apis/batch_inference.py) and one ``ge_depth_metrics_batch`` call per batch, the next batch's image and ground-truth PNGs
+decoding on a thread pool meanwhile; same rows, same tuples.  Speed: README "KITTI speed" (KITTI); DDAD not measured.
 
 ``ground_dir`` writes every image's ground maps (``DepthInferencer.ground_maps`` -> ``show_ground``: attention, slope and ground-depth
 pictures, or one ``.npz`` under ``format_only``).  The maps exist on the engine's route only, so the frames go through the engine: alone
@@ -72,7 +74,7 @@ def _show_batch(model, data, result_depth, show, out_dir, format_only, ply_dir=N
         depther.show_result(name, [depth], show=show, out_file=out_file, format_only=format_only)
 
 
-def _engine_frames(model, data_loader, what, evaluates=True):
+def _engine_frames(model, data_loader, what, evaluates=True, batch=1):
     """What the engine-backed loops share -> ``(depther, engine, indices in the sampler's order, their engine_frame arguments)``; every
     refusal is raised before the first frame runs, in the words of loop ``what``."""
     from ..datasets.pipelines import loading
@@ -92,8 +94,11 @@ def _engine_frames(model, data_loader, what, evaluates=True):
     if evaluates and wants == 'kitti' and (spec['height'], spec['width']) != (352, 1216):
         raise NotImplementedError(f'{what}: KBCrop {(spec["height"], spec["width"])}, the evaluation protocol crops (352, 1216)')
     bf16 = bool(torch.is_autocast_enabled('cuda') and torch.get_autocast_dtype('cuda') == torch.bfloat16)      # what the caller asks for
-    eng = engine_for(depther, bf16, config)
-    indices = [i for batch in data_loader.batch_sampler for i in batch]
+    if batch != 1:
+        from .batch_inference import check_batch
+        check_batch(batch, spec, 'eval_batch')
+    eng = engine_for(depther, bf16, config, batch)
+    indices = [i for part in data_loader.batch_sampler for i in part]
     frames = [dataset.engine_frame(i) for i in indices]
     unknown = {f['camera'] for f in frames if 'camera' in f} - set(loading._DDAD_CAMERA_HEIGHT)       # DDAD; before the first frame runs
     if unknown:
@@ -115,26 +120,48 @@ def _ground_only(model, data_loader, ground_dir, format_only):
     return []
 
 
-def _device_eval(model, data_loader, pre_eval, format_only, show, out_dir, ply_dir=None, ground_dir=None):
-    """The ``device_eval`` loop of ``single_gpu_test``: the list of metric tuples ``pre_eval`` yields, in the sampler's order."""
+def _device_eval_batches(dataset, eng, indices, frames, sums, size, graph):
+    """``_device_eval``'s frames in batches of ``size``: the pool decodes the next batch's image and ground-truth PNGs while the batched
+    engine and ``pre_eval_device_batch`` work on the current one; batch k fills rows ``k * size ..`` of ``sums``."""
+    from .batch_inference import decode_ahead
+    from .inference import _decode
+    jobs = [(lambda i=i, f=f: (_decode(f['img']), dataset.gt_raw(i))) for i, f in zip(indices, frames)]
+    row = 0
+    for decoded in decode_ahead(jobs, size):
+        n = len(decoded)
+        preds = eng.batch([d[0] for d in decoded], graph=graph, to_host=False, paths=[f['img'] for f in frames[row:row + n]])
+        with torch.cuda.stream(eng.stream):
+            dataset.pre_eval_device_batch(preds, indices[row:row + n], sums[row:row + n], raws=[d[1] for d in decoded])
+        row += n
+
+
+def _device_eval(model, data_loader, pre_eval, format_only, show, out_dir, ply_dir=None, ground_dir=None, eval_batch=1, engine_graph=True):
+    """The ``device_eval`` loop of ``single_gpu_test``: the list of metric tuples ``pre_eval`` yields, in the sampler's order.
+    ``eval_batch=F > 1``: the sampler's indices in batches of F through the batched engine and ``pre_eval_device_batch``, image and
+    ground-truth PNGs of the next batch decoding ahead; same rows of the same buffer, same one copy at the end."""
     from ..core.evaluation import metrics_from_sums
     dataset = data_loader.dataset
     if not pre_eval or format_only:
         raise NotImplementedError('device_eval reduces every map to metric sums on the device: it needs pre_eval=True and no format_only')
     if show or out_dir or ply_dir:
         raise NotImplementedError('device_eval with show / out_dir / ply_dir: the depth maps never reach the host')
-    depther, eng, indices, frames = _engine_frames(model, data_loader, 'device_eval')
+    if eval_batch != 1 and ground_dir:
+        raise NotImplementedError('ground_dir with eval_batch > 1: the ground maps come from the single-frame engine; use eval_batch=1')
+    depther, eng, indices, frames = _engine_frames(model, data_loader, 'device_eval', batch=eval_batch)
     sums = torch.empty(max(len(indices), 1), 10, device=eng.device, dtype=torch.float64)
-    for row, (i, frame) in enumerate(zip(indices, frames)):
-        if ground_dir:
-            maps = eng.ground_maps(to_host=False, **frame)
-            pred = maps['depth']
-        else:
-            pred = eng(to_host=False, **frame)
-        with torch.cuda.stream(eng.stream):
-            dataset.pre_eval_device(pred, i, sums[row])
-        if ground_dir:
-            depther.show_ground(maps, _ground_file(dataset, i, ground_dir))
+    if eval_batch != 1:
+        _device_eval_batches(dataset, eng, indices, frames, sums, eval_batch, engine_graph)
+    else:
+        for row, (i, frame) in enumerate(zip(indices, frames)):
+            if ground_dir:
+                maps = eng.ground_maps(to_host=False, graph=engine_graph, **frame)
+                pred = maps['depth']
+            else:
+                pred = eng(to_host=False, graph=engine_graph, **frame)
+            with torch.cuda.stream(eng.stream):
+                dataset.pre_eval_device(pred, i, sums[row])
+            if ground_dir:
+                depther.show_ground(maps, _ground_file(dataset, i, ground_dir))
     with torch.cuda.stream(eng.stream):
         host = sums[:len(indices)].cpu().numpy()                       # the one copy (and the one synchronisation) of the loop
     torch.cuda.current_stream(eng.device).wait_stream(eng.stream)
@@ -142,16 +169,19 @@ def _device_eval(model, data_loader, pre_eval, format_only, show, out_dir, ply_d
 
 
 def single_gpu_test(model, data_loader, pre_eval=False, format_only=False, format_args=None, device=None, *, show=False,
-                    out_dir=None, device_eval=False, ply_dir=None, ground_dir=None):
+                    out_dir=None, device_eval=False, ply_dir=None, ground_dir=None, eval_batch=1, engine_graph=True):
     """Returns a list with one entry per image: the metric tuple (``pre_eval``) or the ``(1, H, W)`` depth map.  ``show`` / ``out_dir``:
     ``show_result`` of every image's map, written to ``out_dir/replace_str(ori_filename)`` (``format_only``: the raw map as
     ``out_dir/<ori_filename without extension>.npy``).  ``ply_dir``: every image's point cloud as ``ply_dir/<ori_filename with .ply>``
     (``save_point_cloud`` with the image's ``cam_intrinsic`` meta and its KB-crop offsets).  ``device_eval`` (with ``pre_eval``; KITTI or
     DDAD protocol): the module docstring.  ``ground_dir``: every image's ground maps (module docstring); without ``device_eval`` the
-    result is an empty list."""
+    result is an empty list.  ``eval_batch=F`` (2 .. 8; with ``device_eval``, KITTI protocol, no ``ground_dir``): F frames per forward
+    (``_device_eval``).  ``engine_graph=False``: the engine of ``device_eval`` runs eagerly and captures no hipGraph."""
     model.eval()
+    if eval_batch != 1 and not device_eval:
+        raise NotImplementedError('eval_batch > 1 batches the device evaluation loop: it needs device_eval=True')
     if device_eval:
-        return _device_eval(model, data_loader, pre_eval, format_only, show, out_dir, ply_dir, ground_dir)
+        return _device_eval(model, data_loader, pre_eval, format_only, show, out_dir, ply_dir, ground_dir, eval_batch, engine_graph)
     if ground_dir:
         if pre_eval:
             raise NotImplementedError('ground_dir with the host loop\'s pre_eval: the ground maps exist on the engine\'s route only; '
@@ -183,11 +213,12 @@ def single_gpu_test(model, data_loader, pre_eval=False, format_only=False, forma
 
 
 def multi_gpu_test(model, data_loader, pre_eval=False, format_only=False, format_args=None, device=None, *, show=False, out_dir=None,
-                   device_eval=False, ply_dir=None, ground_dir=None):
+                   device_eval=False, ply_dir=None, ground_dir=None, eval_batch=1, engine_graph=True):
     """Each rank evaluates its shard of a non-shuffled DistributedSampler; rank 0 receives the results in dataset order.  ``show`` /
-    ``out_dir`` / ``ply_dir`` / ``ground_dir`` / ``device_eval`` as in ``single_gpu_test``: every rank writes the files of its own shard."""
+    ``out_dir`` / ``ply_dir`` / ``ground_dir`` / ``device_eval`` / ``eval_batch`` / ``engine_graph`` as in ``single_gpu_test``: every rank writes the
+    files of its own shard."""
     part = single_gpu_test(model, data_loader, pre_eval, format_only, format_args, device, show=show, out_dir=out_dir,
-                           device_eval=device_eval, ply_dir=ply_dir, ground_dir=ground_dir)
+                           device_eval=device_eval, ply_dir=ply_dir, ground_dir=ground_dir, eval_batch=eval_batch, engine_graph=engine_graph)
     rank, world = get_dist_info()
     if world == 1:
         return part

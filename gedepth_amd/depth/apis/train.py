@@ -18,6 +18,27 @@ def set_random_seed(seed, deterministic=False):
         torch.cuda.manual_seed_all(seed)
 
 
+def make_evaluate_fn(val_set, val_loader, device_eval=False, eval_batch=1, graph=True):
+    """``evaluate_fn(runner)`` for ``train_depther``: validate on ``val_loader``, put the model back into training mode, and return
+    ``val_set.evaluate``'s summary (None on the ranks that receive no results).  With the defaults it is the host loop,
+    ``multi_gpu_test(pre_eval=True)``.  ``device_eval``: the frames go through the inference engine and the metric-sum kernel instead
+    (``single_gpu_test(device_eval=True)``; the model needs ``model.cfg``), ``eval_batch`` frames per forward.  The engine's captured
+    graph holds the parameters' addresses and the optimizer updates them in place, so a replay at a later validation computes with the
+    weights of that iteration.  Precision: ``evaluate_fn`` runs outside autocast, so fp32 from the master weights, as the host loop.
+    ``graph=False``: the engine runs eagerly — for a run whose training step is itself a captured hipGraph, beside which no second graph
+    is captured."""
+    from .test import multi_gpu_test
+
+    def evaluate_fn(runner):
+        if device_eval:
+            res = multi_gpu_test(runner.model, val_loader, pre_eval=True, device_eval=True, eval_batch=eval_batch, engine_graph=graph)
+        else:
+            res = multi_gpu_test(runner.model, val_loader, pre_eval=True)
+        runner.model.train()
+        return val_set.evaluate(res, logger=None) if res is not None else None
+    return evaluate_fn
+
+
 def train_depther(model, dataset, cfg, distributed=False, validate=False, timestamp=None, meta=None, logger=print,
                   evaluate_fn=None, data_loaders=None, device=None, batch_transform=None, channels_last=False):
     """``dataset``: a map-style dataset (or list of them) yielding dict samples; alternatively pass ready

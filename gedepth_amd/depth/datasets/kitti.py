@@ -150,6 +150,15 @@ class KITTIDataset(Dataset):
         if not (torch.is_tensor(pred) and pred.is_cuda and tuple(pred.shape) == (1, 352, 1216) and pred.dtype == torch.float32):
             raise TypeError('pre_eval_device takes a CUDA (1, 352, 1216) float32 prediction, got '
                             f'{tuple(pred.shape) if torch.is_tensor(pred) else type(pred)}')
+        raw = self.gt_raw(index)
+        h, w = raw.shape
+        dev = self.__dict__.setdefault('_gt_upload', PinnedUpload())(raw, pred.device)      # the staging buffer, made on first use
+        top, left = int(h - 352), int((w - 1216) / 2)                   # eval_kb_crop
+        K.depth_metric_sums(pred, dev, top, left, self.eval_rect(352, 1216), self.depth_scale, self.min_depth, self.max_depth, sums_row)
+
+    def gt_raw(self, index):
+        """Split entry ``index``'s ground-truth PNG as it is on disk, an (H, W) uint16 array at least as large as the KB crop: host work
+        only, so a thread may decode it ahead of the device."""
         path = osp.join(self.ann_dir, self.img_infos[index]['ann']['depth_map'])
         raw = np.asarray(Image.open(path))
         if raw.dtype != np.uint16 or raw.ndim != 2:
@@ -157,9 +166,32 @@ class KITTIDataset(Dataset):
         h, w = raw.shape
         if h < 352 or w < 1216:
             raise ValueError(f'{path}: ground truth {(h, w)} is smaller than the KB crop (352, 1216)')
-        dev = self.__dict__.setdefault('_gt_upload', PinnedUpload())(raw, pred.device)      # the staging buffer, made on first use
-        top, left = int(h - 352), int((w - 1216) / 2)                   # eval_kb_crop
-        K.depth_metric_sums(pred, dev, top, left, self.eval_rect(352, 1216), self.depth_scale, self.min_depth, self.max_depth, sums_row)
+        return raw
+
+    def pre_eval_device_batch(self, preds, indices, sums_rows, raws=None):
+        """``pre_eval_device`` for n = ``len(indices)`` <= 8 images in one ``ge_depth_metrics_batch`` call (two launches instead of 2 n):
+        ``preds`` a CUDA ``(F, 1, 352, 1216)`` float32 tensor whose first n maps belong to ``indices``, ``sums_rows`` n rows of the device
+        ``(N, 10)`` float64 buffer.  Each row gets the bits ``pre_eval_device`` gives that image.  The n ground truths go up undivided,
+        each through its own reused pinned buffer, on the current stream; ``raws``: their ``gt_raw`` arrays when a thread has decoded them
+        ahead.  Does not synchronise."""
+        import torch
+        from ... import kernels as K
+        n = len(indices)
+        if not (torch.is_tensor(preds) and preds.is_cuda and preds.dim() == 4 and tuple(preds.shape[1:]) == (1, 352, 1216)
+                and preds.shape[0] >= n and preds.dtype == torch.float32):
+            raise TypeError(f'pre_eval_device_batch takes a CUDA (F >= {n}, 1, 352, 1216) float32 tensor, got '
+                            f'{tuple(preds.shape) if torch.is_tensor(preds) else type(preds)}')
+        if not 1 <= n <= 8 or tuple(sums_rows.shape) != (n, 10):
+            raise ValueError(f'pre_eval_device_batch takes 1 .. 8 images and one (10,) row each, got {n} and {tuple(sums_rows.shape)}')
+        raws = [self.gt_raw(i) for i in indices] if raws is None else raws
+        uploads = self.__dict__.setdefault('_gt_uploads', [])          # one staging buffer per slot: n copies are in flight at once
+        while len(uploads) < n:
+            uploads.append(PinnedUpload())
+        devs = [up(raw, preds.device) for up, raw in zip(uploads, raws)]
+        tops = [int(r.shape[0] - 352) for r in raws]                    # eval_kb_crop
+        lefts = [int((r.shape[1] - 1216) / 2) for r in raws]
+        K.depth_metric_sums_batch(preds, devs, tops, lefts, self.eval_rect(352, 1216), self.depth_scale, self.min_depth, self.max_depth,
+                                  sums_rows)
 
     def pre_eval(self, preds, indices):
         """Per-image metric tuples for predictions ``(1, 352, 1216)`` (kitti.py:502-552)."""

@@ -2113,3 +2113,7 @@ from .cloud_kernels import depth_points  # noqa: E402,F401
 
 # --------------------------------------------------------------------- the ground embedding's maps (csrc/ground.hip, include/gedepth_ground.h)
 from .ground_kernels import ground_maps  # noqa: E402,F401
+
+# --------------------------------------------------------------------- batched KITTI inference / evaluation (csrc/infer_batch.hip,
+# include/gedepth_batch.h)
+from .batch_kernels import depth_metric_sums_batch, infer_front_batch, tta_merge_batch  # noqa: E402,F401

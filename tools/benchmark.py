@@ -5,11 +5,15 @@ timed frames, ``torch.cuda.synchronize()`` around each frame, ``fps:`` lines), f
   reference  today's route: the host test pipeline (dataset ``__getitem__``: PIL decode, pe_165.npy, KB crop, flip copy, Normalize in
              numpy) and ``model(return_loss=False)`` = ``aug_test``, two batch-1 forwards launched from Python;
   engine     ``inference_depther(graph=False)``: PIL decode, ``ge_infer_front``, one batch-2 forward, ``ge_tta_merge``, eagerly;
-  graph      ``inference_depther(graph=True)``: the same with forward + merge replayed from a hipGraph.
+  graph      ``inference_depther(graph=True)``: the same with forward + merge replayed from a hipGraph;
+  batch      ``inference_depther(graph=True, batch=F)`` (``--batch F``, 2 .. 8): F frames per forward through the batched engine, the
+             next batch's files decoding on a thread pool meanwhile.  Timed per list of ``--batch-frames`` files (the pool decodes ahead
+             within a list) and reported per frame; the other modes run the same number of frames between two lists.
 
 Every mode is timed from the image file to the depth map on the host.  The reference mode also reports the model call alone
 (``reference_forward``), which is what the reference's tool times.  ``--mode all`` runs the three modes alternately, frame by frame, in
-one process.  Frames: a seeded synthetic 375 x 1242 tree with an analytic ground plane (default), or ``--data`` = a KITTI tree with
+one process; with ``--batch F`` the batch mode alternates with them (``--mode graph,batch``: those two alone).  Frames: a seeded
+synthetic 375 x 1242 tree with an analytic ground plane (default), or ``--data`` = a KITTI tree with
 ``input/<date>/pe/pe_165.npy`` (the frames of ``cfg.data.test``'s split).  The last line is one JSON object.
 """
 import argparse
@@ -37,12 +41,21 @@ def parse_args(argv=None):
     p.add_argument('config', help='test config file path')
     p.add_argument('checkpoint', nargs='?', default=None, help='checkpoint file (default: the initial weights)')
     p.add_argument('--log-interval', type=int, default=50, help='interval of logging')
-    p.add_argument('--mode', choices=MODES + ('all',), default='all')
+    p.add_argument('--mode', default='all', help='all, or a comma-separated list of reference, engine, graph, batch')
+    p.add_argument('--batch', type=int, default=0, help='F = 2 .. 8: also time the batched engine with F frames per forward (mode batch)')
+    p.add_argument('--batch-frames', type=int, default=0, help='files per timed list of the batch mode (default 5 F)')
     p.add_argument('--bf16', action='store_true', help='bf16 autocast forward')
     p.add_argument('--data', default=None, help='KITTI tree (data_root of cfg.data.test) instead of the synthetic frames')
     p.add_argument('--frames', type=int, default=200, help='timed frames per mode')
     p.add_argument('--seed', type=int, default=0)
-    return p.parse_args(argv)
+    args = p.parse_args(argv)
+    args.modes = list(MODES) + (['batch'] if args.batch else []) if args.mode == 'all' else args.mode.split(',')
+    if set(args.modes) - set(MODES + ('batch',)):
+        p.error(f'--mode: {args.mode}')
+    if ('batch' in args.modes) != bool(args.batch) or (args.batch and not 2 <= args.batch <= 8):
+        p.error('mode batch needs --batch F with F in 2 .. 8, and --batch F a mode list that holds batch')
+    args.batch_frames = args.batch_frames or 5 * args.batch
+    return args
 
 
 def make_synthetic_tree(root, frames=8, seed=0):
@@ -87,8 +100,12 @@ def main(argv=None):
     model = init_depther(cfg, args.checkpoint, device='cuda:0')
     ds = build_dataset(cfg.data.test, dict(test_mode=True))
     files = [osp.join(ds.img_dir, info['filename']) for info in ds.img_infos]
-    modes = list(MODES) if args.mode == 'all' else [args.mode]
-    num_warmup, total = 5, 5 + args.frames
+    modes = args.modes
+    # the batch mode is timed per list of L files; the per-frame modes then run L frames per round, so every mode sees the same files
+    L = args.batch_frames if args.batch else 1
+    num_warmup = (5 + L - 1) // L * L
+    total = num_warmup + (args.frames + L - 1) // L * L
+    timed = total - num_warmup
     spent = {m: 0.0 for m in modes}
     forward_only = 0.0
     amp = dict(device_type='cuda', dtype=torch.bfloat16, enabled=args.bf16)
@@ -104,23 +121,29 @@ def main(argv=None):
                 model(return_loss=False, rescale=True, **data)
             torch.cuda.synchronize()
             return time.perf_counter() - t0
+        if mode == 'batch':
+            inference_depther(model, [files[(i + k) % len(files)] for k in range(L)], bf16=args.bf16, graph=True, batch=args.batch)
+            return 0.0
         inference_depther(model, files[idx], bf16=args.bf16, graph=mode == 'graph')
         return 0.0
 
-    for i in range(total):
+    for i0 in range(0, total, L):
         for mode in modes:
-            torch.cuda.synchronize()
-            start = time.perf_counter()
-            fwd = run(mode, i)
-            torch.cuda.synchronize()
-            elapsed = time.perf_counter() - start
-            if i >= num_warmup:
-                spent[mode] += elapsed
-                if mode == 'reference':
-                    forward_only += fwd
-                if (i + 1) % args.log_interval == 0:
-                    fps = (i + 1 - num_warmup) / spent[mode]
-                    print(f'[{mode}] Done image [{i + 1:<3}/ {total}], fps: {fps:.2f} img / s')
+            for i in ([i0] if mode == 'batch' else range(i0, i0 + L)):
+                torch.cuda.synchronize()
+                start = time.perf_counter()
+                fwd = run(mode, i)
+                torch.cuda.synchronize()
+                elapsed = time.perf_counter() - start
+                if i >= num_warmup:
+                    spent[mode] += elapsed
+                    if mode == 'reference':
+                        forward_only += fwd
+                    done = i + (L if mode == 'batch' else 1)
+                    if done % args.log_interval == 0:
+                        fps = (done - num_warmup) / spent[mode]
+                        print(f'[{mode}] Done image [{done:<3}/ {total}], fps: {fps:.2f} img / s')
+    args.frames = timed
     result = dict(config=osp.basename(args.config), frames=args.frames, warmup=num_warmup, bf16=args.bf16,
                   source='synthetic 375x1242' if args.data is None else args.data, fps={}, ms_per_frame={})
     for mode in modes:
@@ -133,6 +156,9 @@ def main(argv=None):
         result['ms_per_frame']['reference_forward'] = round(1e3 * forward_only / args.frames, 3)
     if 'graph' in modes:
         result['captures'] = model._ge_inferencers[bool(args.bf16)].captures
+    if 'batch' in modes:
+        eng = model._ge_inferencers[(bool(args.bf16), args.batch)]
+        result.update(batch=args.batch, batch_frames=L, batch_captures=eng.captures, batch_replays=eng.replays)
     print(json.dumps(result))
     if tmp is not None:
         tmp.cleanup()

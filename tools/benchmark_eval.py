@@ -1,0 +1,96 @@
+#!/usr/bin/env python
+"""Time of the device evaluation loop per frame — ``single_gpu_test(pre_eval=True, device_eval=True, eval_batch=F)``, what
+``tools/test.py --eval ... --device-eval --eval-batch F`` and ``tools/train.py --device-eval`` run — for several F in one process.
+
+Frames: a seeded synthetic KITTI tree, 16 image / ground-truth PNG pairs of two sizes (375 x 1242 and 370 x 1224, each date with its
+analytic ground plane), listed ``--frames`` times in the split, so every pass decodes ``--frames`` image and ``--frames`` ground-truth PNGs
+from files.  Round 0 warms up (the engines capture their graphs there) and is not counted; the settings then alternate, pass by pass, for
+``--rounds`` rounds.  A pass is timed from the call to the returned list of metric tuples (the loop ends with its one synchronising copy).
+The last line is one JSON object: per F the median and the minimum of the passes in ms per frame."""
+import argparse
+import json
+import os
+import os.path as osp
+import statistics
+import sys
+import tempfile
+import time
+
+import numpy as np
+import torch
+from PIL import Image
+
+sys.path.insert(0, osp.dirname(osp.dirname(osp.abspath(__file__))))
+
+from gedepth_amd.depth.apis import init_depther  # noqa: E402
+from gedepth_amd.depth.apis.test import single_gpu_test  # noqa: E402
+from gedepth_amd.depth.datasets import build_dataloader, build_dataset  # noqa: E402
+from gedepth_amd.mmrt.config import Config  # noqa: E402
+
+
+def make_tree(root, frames, seed=0, unique=16):
+    rng = np.random.default_rng(seed)
+    files = []
+    for date, (H, W) in (('2011_09_26', (375, 1242)), ('2011_09_28', (370, 1224))):
+        drive = f'{date}_drive_0001_sync'
+        img_dir = osp.join(root, 'input', date, drive, 'image_02', 'data')
+        gt_dir = osp.join(root, 'gt_depth', drive, 'proj_depth', 'groundtruth', 'image_02')
+        for d in (img_dir, gt_dir, osp.join(root, 'input', date, 'pe')):
+            os.makedirs(d, exist_ok=True)
+        v = np.arange(H, dtype=np.float64).reshape(H, 1)
+        np.save(osp.join(root, 'input', date, 'pe', 'pe_165.npy'),
+                np.where(v > 173.0, 1.65 * 721.5377 / np.maximum(v - 172.854, 1e-6), -5.0) * np.ones((1, W)))
+        for f in range(unique // 2):
+            name = f'{f:010d}.png'
+            Image.fromarray(rng.integers(0, 256, (H, W, 3), dtype=np.uint8)).save(osp.join(img_dir, name))
+            depth = np.where(rng.random((H, W)) < 0.05, rng.uniform(1.0, 80.0, (H, W)), 0.0)      # about as sparse as a LiDAR ground truth
+            Image.fromarray((depth * 256).astype(np.uint16)).save(osp.join(gt_dir, name))
+            files.append(f'{date}/{drive}/image_02/data/{name} {drive}/proj_depth/groundtruth/image_02/{name} 721.5377')
+    split = osp.join(root, 'split.txt')
+    with open(split, 'w') as fh:
+        fh.write('\n'.join(files[i % len(files)] for i in range(frames)) + '\n')
+    return split
+
+
+def main(argv=None):
+    p = argparse.ArgumentParser(description='Time the device evaluation loop per frame for several --eval-batch settings')
+    p.add_argument('config')
+    p.add_argument('checkpoint', nargs='?', default=None)
+    p.add_argument('--eval-batch', type=int, nargs='+', default=[1, 2, 4, 8])
+    p.add_argument('--frames', type=int, default=96)
+    p.add_argument('--rounds', type=int, default=3)
+    p.add_argument('--bf16', action='store_true')
+    p.add_argument('--seed', type=int, default=0)
+    args = p.parse_args(argv)
+    assert torch.cuda.is_available(), 'tools/benchmark_eval.py measures the MI355X'
+    cfg = Config.fromfile(args.config)
+    with tempfile.TemporaryDirectory() as root:
+        cfg.data.test.data_root, cfg.data.test.split = root, make_tree(root, args.frames, args.seed)
+        torch.manual_seed(args.seed)
+        model = init_depther(cfg, args.checkpoint, device='cuda:0')
+        ds = build_dataset(cfg.data.test, dict(test_mode=True))
+        loader = build_dataloader(ds, 1, 0, dist=False, shuffle=False)
+        assert len(ds) == args.frames
+        spent = {F: [] for F in args.eval_batch}
+        summary = {}
+        for rnd in range(args.rounds + 1):
+            for F in args.eval_batch:
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                with torch.autocast('cuda', dtype=torch.bfloat16, enabled=args.bf16):
+                    res = single_gpu_test(model, loader, pre_eval=True, device_eval=True, eval_batch=F)
+                elapsed = time.perf_counter() - t0
+                if rnd:
+                    spent[F].append(1e3 * elapsed / args.frames)
+                    print(f'[eval_batch={F}] round {rnd}: {spent[F][-1]:.2f} ms / frame')
+                summary[F] = float(np.nanmean([r[3] for r in res]))                  # abs_rel, to see that the settings evaluate the same
+        result = dict(config=osp.basename(args.config), frames=args.frames, rounds=args.rounds, bf16=args.bf16,
+                      source='synthetic 375x1242 + 370x1224, image and ground-truth PNGs',
+                      ms_per_frame_median={str(F): round(statistics.median(v), 3) for F, v in spent.items()},
+                      ms_per_frame_min={str(F): round(min(v), 3) for F, v in spent.items()},
+                      abs_rel={str(F): summary[F] for F in spent})
+        print(json.dumps(result))
+
+
+if __name__ == '__main__':
+    main()

@@ -22,7 +22,8 @@ through the graphed engine (``DepthInferencer.ground_maps``): alone, or with ``-
 
 ``--device-eval`` (with ``--eval`` and ``--synthetic 0``; KITTI or DDAD protocol) evaluates on the device: frames go through the graphed
 engine (flip-TTA for KITTI, the single view for DDAD) and each map is reduced to its metric sums by a HIP kernel, so no map is copied to the
-host (``single_gpu_test(device_eval=True)``).
+host (``single_gpu_test(device_eval=True)``).  ``--eval-batch F`` (KITTI protocol, 2 .. 8) runs F frames per forward and one metric launch
+per batch, with the next batch's image and ground-truth PNGs decoding on a thread pool meanwhile.
 """
 import argparse
 import os
@@ -53,6 +54,8 @@ def parse_args(argv=None):
     p.add_argument('--bf16', action='store_true', help='bf16 autocast inference')
     p.add_argument('--device-eval', action='store_true',
                    help='with --eval and --synthetic 0: the graphed inference engine and the metric-sum kernel instead of the host loop')
+    p.add_argument('--eval-batch', type=int, default=1,
+                   help='with --device-eval (KITTI protocol): frames per forward, 1 .. 8; the next batch\'s PNGs decode on a thread pool')
     p.add_argument('--out', help='output result file in pickle format (.pkl / .pickle), written by rank 0')
     p.add_argument('--format-only', action='store_true',
                    help='format the results (dataset.format_results) without evaluating; with --show-dir the raw maps are saved as .npy')
@@ -74,6 +77,12 @@ def parse_args(argv=None):
         raise ValueError('--eval and --format-only cannot be both specified')
     if args.device_eval and (not args.eval or args.synthetic != 0 or args.show or args.show_dir or args.ply_dir):
         raise ValueError('--device-eval needs --eval and --synthetic 0, and cannot be combined with --show / --show-dir / --ply-dir')
+    if args.eval_batch != 1 and not args.device_eval:
+        raise ValueError('--eval-batch needs --device-eval: it batches the device evaluation loop')
+    if not 1 <= args.eval_batch <= 8:
+        raise ValueError(f'--eval-batch must be in 1 .. 8, got {args.eval_batch}')
+    if args.eval_batch != 1 and args.ground_dir:
+        raise ValueError('--eval-batch > 1 cannot be combined with --ground-dir: the ground maps come from the single-frame engine')
     if args.ground_dir and args.eval and not args.device_eval:
         raise ValueError('--ground-dir with --eval needs --device-eval: the ground maps come from the graphed engine, not from the host loop')
     if args.ground_dir and (args.show or args.show_dir or args.ply_dir or args.out):
@@ -108,7 +117,7 @@ def run_dataset(args, cfg):
     with torch.autocast('cuda', dtype=torch.bfloat16, enabled=args.bf16):
         results = test(model, loader, pre_eval=args.eval is not None, format_only=args.format_only, format_args=eval_kwargs,
                        show=args.show, out_dir=args.show_dir, device_eval=args.device_eval, ply_dir=args.ply_dir,
-                       ground_dir=args.ground_dir)
+                       ground_dir=args.ground_dir, eval_batch=args.eval_batch)
     rank, _ = get_dist_info()
     if rank == 0:
         if args.out:
@@ -143,7 +152,7 @@ def main():
         loader = build_dataloader(dataset, 1, cfg.data.workers_per_gpu, dist=False, shuffle=False)
         model.cfg = cfg
         with torch.autocast('cuda', dtype=torch.bfloat16, enabled=args.bf16):
-            results = single_gpu_test(model, loader, pre_eval=True, device_eval=args.device_eval)
+            results = single_gpu_test(model, loader, pre_eval=True, device_eval=args.device_eval, eval_batch=args.eval_batch)
         dataset.evaluate(results)
         return
     res = []
