@@ -11,12 +11,10 @@
 // The grid is capped by growing ipt, never by grid-striding, so a point's place is a pure function of its candidate index.
 // The arithmetic is numpy's float32 arithmetic: true IEEE division, no contraction.  Pure streaming work (1.7 MB read, up to 6.8 MB written
 // at 352 x 1216): launch-latency-sized.
+// The candidate grid, the keep rule, the record and the span geometry are those of cloud_points.h, which scene.hip shares.
 #pragma clang fp contract(off)
-#include "common.h"
+#include "cloud_points.h"
 #include "../../include/gedepth_cloud.h"
-
-#define GE_CLOUD_MIN_IPT 4          // candidates per thread: at least 4 (a span of 1024), more once the grid would pass GE_CLOUD_MAX_BLOCKS
-#define GE_CLOUD_MAX_BLOCKS 1024
 
 struct CloudArgs {
   int W, nc, n, row0, step, ipt;    // nc candidates per row, n in all
@@ -28,11 +26,9 @@ struct CloudArgs {
 // candidate i -> its pixel, its depth and whether it is kept (false beyond the last candidate)
 __device__ __forceinline__ bool cloud_keep(const float* __restrict__ depth, const CloudArgs& a, long i, int& r, int& c, float& z) {
   if (i >= a.n) return false;
-  const int ri = (int)i / a.nc;
-  r = a.row0 + ri * a.step;
-  c = ((int)i - ri * a.nc) * a.step;
+  cloud_pixel((int)i, a.nc, a.row0, a.step, r, c);
   z = depth[(long)r * a.W + c];
-  return a.dmin <= z && z <= a.dmax;
+  return cloud_in_range(z, a.dmin, a.dmax);
 }
 
 // pass 1: ws[b] = the number of kept candidates of block b's span
@@ -75,34 +71,12 @@ __global__ void __launch_bounds__(256) cloud_write_k(const float* __restrict__ d
     __syncthreads();
     const int c0 = wc[j & 1][0], c1 = wc[j & 1][1], c2 = wc[j & 1][2], c3 = wc[j & 1][3];
     if (keep) {
-      const int lower = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-      const long k = (long)run + (w > 0 ? c0 : 0) + (w > 1 ? c1 : 0) + (w > 2 ? c2 : 0) + lower;
-      const float x = ((float)c - a.cx) / a.fx * z;
-      const float y = ((float)r - a.cy) / a.fy * z;
-      uint32_t rgba = 0x00ffffffu;
-      if (bgr) {
-        const uint8_t* p = bgr + ((long)(a.top + r) * a.Ws + (a.left + c)) * 3;
-        rgba = (uint32_t)p[2] | ((uint32_t)p[1] << 8) | ((uint32_t)p[0] << 16);
-      }
-      const ge_u32x4 rec = {__float_as_uint(x), __float_as_uint(y), __float_as_uint(z), rgba | (a.alpha << 24)};
-      records[k] = rec;
+      const long k = (long)run + (w > 0 ? c0 : 0) + (w > 1 ? c1 : 0) + (w > 2 ? c2 : 0) + cloud_lower_lanes(m);
+      records[k] = cloud_record(r, c, z, a.fx, a.fy, a.cx, a.cy, cloud_frame_rgb(bgr, a.Ws, a.top, a.left, r, c), a.alpha);
     }
     run += c0 + c1 + c2 + c3;
   }
   if (blockIdx.x == gridDim.x - 1 && t == 0) *count = run;
-}
-
-// nc, n, ipt and the grid of a geometry; false for one ge_depth_points refuses
-static bool cloud_geometry(int H, int W, int row0, int step, int& nc, int& n, int& ipt, unsigned& blocks) {
-  if (H <= 0 || W <= 0 || row0 < 0 || row0 >= H || step < 1 || (long)H * W > 0x7fffffffL) return false;
-  const long nr = ((long)(H - row0) + step - 1) / step;
-  nc = (int)(((long)W + step - 1) / step);
-  n = (int)(nr * nc);                                 // <= H * W
-  const long per = 256L * GE_CLOUD_MAX_BLOCKS;
-  ipt = (int)((n + per - 1) / per);
-  if (ipt < GE_CLOUD_MIN_IPT) ipt = GE_CLOUD_MIN_IPT;
-  blocks = (unsigned)((n + 256L * ipt - 1) / (256L * ipt));
-  return true;
 }
 
 extern "C" size_t ge_depth_points_workspace(int H, int W, int row0, int step) {

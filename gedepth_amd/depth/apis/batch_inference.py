@@ -102,10 +102,10 @@ class BatchDepthInferencer(DepthInferencer):
             self.static_out.copy_(pred)
 
     def _single(self, *a, **kw):
-        raise NotImplementedError('a BatchDepthInferencer runs batch(imgs); single frames, points and ground_maps go through the '
+        raise NotImplementedError('a BatchDepthInferencer runs batch(imgs); single frames, points, scene_points and ground_maps go through the '
                                   'DepthInferencer of engine_for(model, bf16)')
 
-    __call__ = ground_maps = points = _single
+    __call__ = ground_maps = points = scene_points = _single
 
     def batch(self, imgs, pes=None, calib=None, cam_height=1.65, graph=True, to_host=True, paths=None):
         """n <= F frames -> their maps.  ``imgs``: paths, (H, W, 3) uint8 BGR arrays, or frames already decoded by ``decode_ahead`` (then

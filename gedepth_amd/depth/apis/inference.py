@@ -36,8 +36,8 @@ from ..datasets.pipelines import loading    # _DDAD_CAMERA_HEIGHT is read throug
 from ..models import build_depther
 from ..utils.pinned import PinnedUpload
 
-__all__ = ['init_depther', 'inference_depther', 'inference_point_cloud', 'inference_ground', 'DepthInferencer', 'kitti_front_spec', 'ddad_front_spec',
-           'front_spec']
+__all__ = ['init_depther', 'inference_depther', 'inference_point_cloud', 'inference_ground', 'inference_scene_cloud', 'DepthInferencer',
+           'kitti_front_spec', 'ddad_front_spec', 'front_spec', 'SCENE_LAYERS']
 
 # test-time transforms of MultiScaleFlipAug the device front end restates (ImageToTensor / Collect are layout only)
 _FRONT_TRANSFORMS = ('RandomFlip', 'Normalize', 'ImageToTensor', 'Collect')
@@ -210,7 +210,7 @@ class _KITTIFront:
         s = eng.spec
         H, W = bgr.shape[:2]
         top, left = int(H - s['height']), int((W - s['width']) / 2)       # KBCrop
-        raw = eng.ground_depth(H, W, path, pe, calib, cam_height)
+        raw = eng.last_ground_depth = eng.ground_depth(H, W, path, pe, calib, cam_height)       # kept for ``scene_points``
         dev = eng.upload(bgr)
         K.infer_front(dev, raw, eng.static_in, top, left, s['mean'], s['std'], s['to_rgb'], s['pe_max'], s['depth_scale'])
         return dev, top, left
@@ -274,6 +274,9 @@ class DepthInferencer:
         self._staging = PinnedUpload()
         self._pe = {}
         self.last_frame = None                   # KITTI: (device uint8 BGR frame, top, left) of the last call, for ``points``
+        self.last_ground_depth = None            # KITTI: the raw (H, W) f32 ground depth the last call's front end was given
+        self.last_gt = None                      # the (H, W) uint16 ground truth ``scene_points`` last uploaded
+        self._gt_staging = PinnedUpload()
         self.static_ground = self.static_ground_valid = None      # (4, H, W) f32 / (H, W) u8 of ``ground_maps``, allocated at its first call
         self.reset()
 
@@ -376,8 +379,8 @@ class DepthInferencer:
         the first call of this method), valid until the next call and ordered on ``self.stream``."""
         return self._frame(img, pe, calib, cam_height, graph, to_host, camera, True)
 
-    def _frame(self, img, pe, calib, cam_height, graph, to_host, camera, ground):
-        bgr = _decode(img)
+    def _frame(self, img, pe, calib, cam_height, graph, to_host, camera, ground, bgr=None):
+        bgr = _decode(img) if bgr is None else bgr           # ``bgr``: ``img`` as a caller has decoded it already
         H, W = bgr.shape[:2]
         path = img if isinstance(img, str) else None
         cam, ori_shape = self.front.frame(self, H, W, path, camera)
@@ -450,6 +453,89 @@ class DepthInferencer:
             out = depth_points(depth, fx, fy, cx - left, cy - top, dev, top, left, **cloud_kw)
         cur.wait_stream(self.stream)
         return out
+
+    def scene_points(self, img, gt=None, layers=None, pe=None, calib=None, cam_height=1.65, graph=True, K=None, gt_scale=256.0, **cloud_kw):
+        """One frame -> the scene cloud of its map (role of the reference's visualize_point-cloud_kitti_gt_pe_pred.py):
+        ``(records, counts)`` device tensors as ``kernels.scene_points`` returns them, without synchronising.  The layers, always in the
+        order of ``SCENE_LAYERS`` whatever order ``layers`` names them in: ``'prediction'``, ``static_out`` coloured from the frame;
+        ``'ground'`` (255, 0, 0), the raw ground depth this frame's front end was given, in the KB-crop window; ``'gt'`` (0, 255, 0),
+        ``gt`` — a 16-bit PNG path or an (H, W) uint16 array of the frame's size, uploaded through a pinned buffer on the engine's
+        stream and divided by ``gt_scale`` in the kernel — in the KB-crop window; ``'adjusted'`` (0, 0, 255), the ``ground_depth`` plane
+        of ``static_ground``.  ``layers=None``: all of them, without ``'gt'`` when ``gt`` is None.  The frame runs as ``ground_maps`` with
+        ``to_host=False`` when ``'adjusted'`` is among the layers and as ``__call__`` otherwise (their captures and keys); the kernel
+        launches on ``self.stream`` outside the graph.  Intrinsics as in ``points``.  ``cloud_kw``: ``min_depth`` / ``max_depth``
+        (default: the decode head's), shared by all layers, ``row0``, ``step``, ``alpha``.  With ``min_depth > 0`` the pixels of the
+        ``adjusted`` plane without a valid ground depth (0) and the ground truth's pixels without a LiDAR return (0) drop out."""
+        if self.ddad:
+            raise NotImplementedError(_DDAD_NO_POINTS)
+        from ...kernels import SceneLayer, scene_points            # the module's ``K`` is this method's intrinsics argument
+        from ..utils.point_cloud import kitti_intrinsics
+        names = _scene_layer_names(layers, gt)                       # every argument error before any device work
+        fx, fy, cx, cy = kitti_intrinsics(img if isinstance(img, str) else None, calib, K, self.prefix)
+        bgr = _decode(img)
+        H, W = bgr.shape[:2]
+        self.front.frame(self, H, W, None, None)
+        raw_gt = _scene_gt(gt, H, W) if 'gt' in names else None
+        head = self.model.decode_head
+        dmin, dmax = float(cloud_kw.pop('min_depth', head.min_depth)), float(cloud_kw.pop('max_depth', head.max_depth))
+        unknown = set(cloud_kw) - {'row0', 'step', 'alpha'}
+        if unknown:
+            raise TypeError(f'scene_points: unknown argument(s) {", ".join(sorted(unknown))}')
+        s = self.spec
+        self._frame(img, pe, calib, cam_height, graph, False, None, 'adjusted' in names, bgr)
+        dev, top, left = self.last_frame
+        cur = torch.cuda.current_stream(self.device)
+        with torch.cuda.stream(self.stream):
+            made = []
+            for name in names:
+                kw = dict(min_depth=dmin, max_depth=dmax, colour=_SCENE_COLOURS[name])
+                if name == 'prediction':
+                    made.append(SceneLayer(self.static_out[0], **kw))
+                elif name == 'ground':
+                    made.append(SceneLayer(self.last_ground_depth, top=top, left=left, **kw))
+                elif name == 'gt':
+                    self.last_gt = self._gt_staging(raw_gt, self.device)
+                    made.append(SceneLayer(self.last_gt, 'u16', top=top, left=left, scale=gt_scale, **kw))
+                else:
+                    made.append(SceneLayer(self.static_ground[PLANES.index('ground_depth')], **kw))
+            out = scene_points(made, fx, fy, cx - left, cy - top, s['height'], s['width'], dev, top, left, **cloud_kw)
+        cur.wait_stream(self.stream)
+        return out
+
+
+SCENE_LAYERS = ('prediction', 'ground', 'gt', 'adjusted')          # the reference's concatenation order
+_SCENE_COLOURS = {'prediction': None, 'ground': (255, 0, 0), 'gt': (0, 255, 0), 'adjusted': (0, 0, 255)}
+
+
+def _scene_layer_names(layers, gt):
+    """The layers of a scene cloud in ``SCENE_LAYERS``' order; an unknown name, an empty list or ``'gt'`` without ``gt`` is a ``ValueError``."""
+    if layers is None:
+        return [n for n in SCENE_LAYERS if n != 'gt' or gt is not None]
+    asked = [layers] if isinstance(layers, str) else list(layers)
+    unknown = [n for n in asked if n not in SCENE_LAYERS]
+    if unknown:
+        raise ValueError(f'unknown scene layer(s) {", ".join(map(repr, unknown))}: the layers are {", ".join(SCENE_LAYERS)}')
+    if not asked:
+        raise ValueError(f'no scene layer asked for: the layers are {", ".join(SCENE_LAYERS)}')
+    if 'gt' in asked and gt is None:
+        raise ValueError('the \'gt\' layer needs gt= (a 16-bit PNG path or an (H, W) uint16 array)')
+    return [n for n in SCENE_LAYERS if n in asked]
+
+
+def _scene_gt(gt, H, W, load=True):
+    """``gt`` (a path, read as ``KITTIDataset.gt_raw`` reads it, or an array) -> the contiguous (H, W) uint16 array; a TypeError for another
+    dtype, a ValueError for another size.  ``load=False``: the checks alone, a path's from the PNG header."""
+    if isinstance(gt, str) and not load:
+        with Image.open(gt) as im:
+            ok, shape, what = im.mode == 'I;16', (im.size[1], im.size[0]), f'mode {im.mode}'
+    else:
+        raw = np.asarray(Image.open(gt)) if isinstance(gt, str) else np.asarray(gt)
+        ok, shape, what = raw.dtype == np.uint16 and raw.ndim == 2, raw.shape, f'{raw.dtype} {raw.shape}'
+    if not ok:
+        raise TypeError(f'gt must be a 16-bit single-channel PNG or an (H, W) uint16 array, got {what}')
+    if tuple(shape) != (H, W):
+        raise ValueError(f'gt has shape {tuple(shape)}, the frame is {(H, W)}')
+    return np.ascontiguousarray(raw) if load else None
 
 
 _DDAD_NO_POINTS = ('point clouds on a DDAD engine: DDADResize feeds the network an area-resized frame that exists only normalised, so there '
@@ -567,4 +653,43 @@ def inference_point_cloud(model, img, pe=None, calib=None, cam_height=1.65, bf16
         if o is not None:
             write_ply(o, pts)
         clouds.append(pts)
+    return clouds
+
+
+def inference_scene_cloud(model, img, gt=None, layers=None, out_file=None, pe=None, calib=None, cam_height=1.65, bf16=False, graph=True, K=None,
+                          **cloud_kw):
+    """The scene cloud of each frame of ``img`` (a path, an (H, W, 3) uint8 BGR array, or a list of these): a list with one
+    ``(points, counts)`` per frame, from ``DepthInferencer.scene_points`` — ``points`` a ``depth.utils.POINT_DTYPE`` array, the layers one
+    after the other, ``counts`` an ordered ``{layer name: its number of points}``.  ``gt`` (a 16-bit PNG path or an (H, W) uint16 array; a
+    list: one per frame) feeds the ``'gt'`` layer; ``layers``: names out of ``SCENE_LAYERS`` (default: all, without ``'gt'`` when there is
+    no ``gt``).  Frames, ground depth, intrinsics, ``bf16`` and ``graph`` as in ``inference_point_cloud``; ``out_file`` (a path, or a list
+    with one per frame): the ``.ply`` files are written too (``depth.utils.write_scene_ply``).  ``cloud_kw``: ``min_depth``, ``max_depth``,
+    ``row0``, ``step``, ``alpha``, ``gt_scale``.  A DDAD config raises ``NotImplementedError``, as for ``inference_point_cloud``."""
+    from ..utils.point_cloud import kitti_intrinsics, scene_records_to_points, write_scene_ply
+    imgs = img if isinstance(img, list) else [img]
+    pes = _per_frame(pe, len(imgs), '{n} ground-depth maps for {m} frames')
+    gts = _per_frame(gt, len(imgs), '{n} ground truths for {m} frames')
+    outs = _per_frame(out_file if out_file is None or isinstance(out_file, list) else [out_file], len(imgs),
+                      'out_file must be a list with one path per frame ({m} frames)')
+    spec, prefix = config = _config_of(model)                                 # argument errors before any device work
+    if spec['protocol'] == 'ddad':
+        raise NotImplementedError(_DDAD_NO_POINTS)
+    names = [_scene_layer_names(layers, g) for g in gts]
+    if calib is None and any(p is None and _pe_file(spec, prefix, i) is None for i, p in zip(imgs, pes)):
+        raise ValueError(_NO_PE)
+    from .batch_inference import frame_size
+    for i, g, n in zip(imgs, gts, names):
+        kitti_intrinsics(i if isinstance(i, str) else None, calib, K, prefix)
+        H, W = frame_size(i)
+        if H < spec['height'] or W < spec['width']:
+            raise ValueError(f'frame {(H, W)} is smaller than the KB crop {(spec["height"], spec["width"])}')
+        if 'gt' in n:
+            _scene_gt(g, H, W, load=False)
+    eng = engine_for(model, bf16, config)
+    clouds = []
+    for i, g, p, o, n in zip(imgs, gts, pes, outs, names):
+        pts, counts = scene_records_to_points(*eng.scene_points(i, g, layers, p, calib, cam_height, graph, K, **cloud_kw), n)
+        if o is not None:
+            write_scene_ply(o, pts, counts)
+        clouds.append((pts, counts))
     return clouds

@@ -14,7 +14,11 @@ decoding on a thread pool meanwhile; same rows, same tuples.  Speed: README "KIT
 
 ``ground_dir`` writes every image's ground maps (``DepthInferencer.ground_maps`` -> ``show_ground``: attention, slope and ground-depth
 pictures, or one ``.npz`` under ``format_only``).  The maps exist on the engine's route only, so the frames go through the engine: alone
-(no result list), or in the same pass as ``device_eval``; with the host loop's ``pre_eval`` it raises.  Speed: not measured."""
+(no result list), or in the same pass as ``device_eval``; with the host loop's ``pre_eval`` it raises.  Speed: not measured.
+
+``scene_dir`` (KITTI protocol) writes every image's scene cloud — the prediction, the ground prior, the LiDAR ground truth and the
+slope-adjusted ground plane in one binary ``.ply`` (``DepthInferencer.scene_points`` -> ``write_scene_ply``) — through the engine, alone: it
+returns no results and combines with no other output.  The loop: speed not measured; the kernel: README "Scene clouds"."""
 import os.path as osp
 
 import torch
@@ -120,6 +124,23 @@ def _ground_only(model, data_loader, ground_dir, format_only):
     return []
 
 
+def _scene_only(model, data_loader, scene_dir):
+    """``scene_dir``: every frame through ``DepthInferencer.scene_points`` with its ground truth, written as
+    ``scene_dir/<ori_filename with .ply>``; no results."""
+    from ..utils.point_cloud import write_scene_ply
+    from .inference import SCENE_LAYERS, _config_of
+    depther = getattr(model, 'module', model)
+    if getattr(depther, 'cfg', None) is not None and _config_of(depther)[0]['protocol'] != 'kitti':
+        raise NotImplementedError('scene_dir: the scene clouds are built for the KITTI protocol (a frame-sized ground prior and a uint16 '
+                                  'ground truth in the KB-crop window)')
+    depther, eng, indices, frames = _engine_frames(model, data_loader, 'scene_dir', evaluates=False)
+    dataset = data_loader.dataset
+    for i, frame in zip(indices, frames):
+        out_file = osp.join(scene_dir, osp.splitext(dataset.img_infos[i]['filename'])[0] + '.ply')
+        write_scene_ply(out_file, eng.scene_points(gt=dataset.gt_raw(i), **frame), SCENE_LAYERS)
+    return []
+
+
 def _device_eval_batches(dataset, eng, indices, frames, sums, size, graph):
     """``_device_eval``'s frames in batches of ``size``: the pool decodes the next batch's image and ground-truth PNGs while the batched
     engine and ``pre_eval_device_batch`` work on the current one; batch k fills rows ``k * size ..`` of ``sums``."""
@@ -169,15 +190,21 @@ def _device_eval(model, data_loader, pre_eval, format_only, show, out_dir, ply_d
 
 
 def single_gpu_test(model, data_loader, pre_eval=False, format_only=False, format_args=None, device=None, *, show=False,
-                    out_dir=None, device_eval=False, ply_dir=None, ground_dir=None, eval_batch=1, engine_graph=True):
+                    out_dir=None, device_eval=False, ply_dir=None, ground_dir=None, eval_batch=1, engine_graph=True, scene_dir=None):
     """Returns a list with one entry per image: the metric tuple (``pre_eval``) or the ``(1, H, W)`` depth map.  ``show`` / ``out_dir``:
     ``show_result`` of every image's map, written to ``out_dir/replace_str(ori_filename)`` (``format_only``: the raw map as
     ``out_dir/<ori_filename without extension>.npy``).  ``ply_dir``: every image's point cloud as ``ply_dir/<ori_filename with .ply>``
     (``save_point_cloud`` with the image's ``cam_intrinsic`` meta and its KB-crop offsets).  ``device_eval`` (with ``pre_eval``; KITTI or
     DDAD protocol): the module docstring.  ``ground_dir``: every image's ground maps (module docstring); without ``device_eval`` the
     result is an empty list.  ``eval_batch=F`` (2 .. 8; with ``device_eval``, KITTI protocol, no ``ground_dir``): F frames per forward
-    (``_device_eval``).  ``engine_graph=False``: the engine of ``device_eval`` runs eagerly and captures no hipGraph."""
+    (``_device_eval``).  ``engine_graph=False``: the engine of ``device_eval`` runs eagerly and captures no hipGraph.  ``scene_dir`` (KITTI
+    protocol; alone): every image's scene cloud as ``scene_dir/<ori_filename with .ply>`` (module docstring); the result is an empty list."""
     model.eval()
+    if scene_dir:
+        if pre_eval or format_only or show or out_dir or ply_dir or ground_dir or device_eval:
+            raise NotImplementedError('scene_dir with pre_eval / format_only / show / out_dir / ply_dir / ground_dir / device_eval: the scene '
+                                      'clouds come from an engine loop of their own that returns no results; run them apart')
+        return _scene_only(model, data_loader, scene_dir)
     if eval_batch != 1 and not device_eval:
         raise NotImplementedError('eval_batch > 1 batches the device evaluation loop: it needs device_eval=True')
     if device_eval:
@@ -213,12 +240,13 @@ def single_gpu_test(model, data_loader, pre_eval=False, format_only=False, forma
 
 
 def multi_gpu_test(model, data_loader, pre_eval=False, format_only=False, format_args=None, device=None, *, show=False, out_dir=None,
-                   device_eval=False, ply_dir=None, ground_dir=None, eval_batch=1, engine_graph=True):
+                   device_eval=False, ply_dir=None, ground_dir=None, eval_batch=1, engine_graph=True, scene_dir=None):
     """Each rank evaluates its shard of a non-shuffled DistributedSampler; rank 0 receives the results in dataset order.  ``show`` /
-    ``out_dir`` / ``ply_dir`` / ``ground_dir`` / ``device_eval`` / ``eval_batch`` / ``engine_graph`` as in ``single_gpu_test``: every rank writes the
-    files of its own shard."""
+    ``out_dir`` / ``ply_dir`` / ``ground_dir`` / ``scene_dir`` / ``device_eval`` / ``eval_batch`` / ``engine_graph`` as in
+    ``single_gpu_test``: every rank writes the files of its own shard."""
     part = single_gpu_test(model, data_loader, pre_eval, format_only, format_args, device, show=show, out_dir=out_dir,
-                           device_eval=device_eval, ply_dir=ply_dir, ground_dir=ground_dir, eval_batch=eval_batch, engine_graph=engine_graph)
+                           device_eval=device_eval, ply_dir=ply_dir, ground_dir=ground_dir, eval_batch=eval_batch, engine_graph=engine_graph,
+                           scene_dir=scene_dir)
     rank, world = get_dist_info()
     if world == 1:
         return part

@@ -1,5 +1,6 @@
 from .color_depth import colorize
-from .point_cloud import POINT_DTYPE, depth_to_points, kitti_intrinsics, write_ply
+from .point_cloud import POINT_DTYPE, depth_to_points, kitti_intrinsics, scene_records_to_points, write_ply, write_scene_ply
 from .position_encoding import SinePositionalEncoding
 
-__all__ = ['SinePositionalEncoding', 'colorize', 'POINT_DTYPE', 'depth_to_points', 'write_ply', 'kitti_intrinsics']
+__all__ = ['SinePositionalEncoding', 'colorize', 'POINT_DTYPE', 'depth_to_points', 'write_ply', 'kitti_intrinsics', 'write_scene_ply',
+           'scene_records_to_points']

@@ -1,6 +1,9 @@
 """Point clouds from depth maps (tools/misc/visualize_point-cloud_kitti.py of the reference): ``depth_to_points`` back-projects the pixels
 whose depth is in range through the camera intrinsics and colours them from the frame; ``write_ply`` stores them as a binary
-little-endian PLY file; ``kitti_intrinsics`` finds a KITTI frame's intrinsics.
+little-endian PLY file; ``kitti_intrinsics`` finds a KITTI frame's intrinsics.  ``write_scene_ply`` stores a scene cloud — several layers
+in one record buffer (``kernels.scene_points``, gedepth_amd/csrc/scene.hip; ``DepthInferencer.scene_points``: the prediction, the ground
+prior, the LiDAR ground truth and the slope-adjusted ground plane, role of the reference's visualize_point-cloud_kitti_gt_pe_pred.py) — as
+the same file with one ``comment layer <name> <count>`` line per layer; ``scene_records_to_points`` brings its tensors to the host.
 
 The per-pixel work is two gfx950 launches (``ge_depth_points``, gedepth_amd/csrc/cloud.hip): an ordered stream compaction that leaves the
 kept points in row-major order as 16-byte records — the file's payload byte for byte.  Where the reference formats about 428 000 points
@@ -17,7 +20,7 @@ import torch
 
 from ... import kernels
 
-__all__ = ['POINT_DTYPE', 'depth_to_points', 'write_ply', 'kitti_intrinsics']
+__all__ = ['POINT_DTYPE', 'depth_to_points', 'write_ply', 'kitti_intrinsics', 'write_scene_ply', 'scene_records_to_points']
 
 POINT_DTYPE = np.dtype([('x', '<f4'), ('y', '<f4'), ('z', '<f4'), ('red', 'u1'), ('green', 'u1'), ('blue', 'u1'), ('alpha', 'u1')])
 
@@ -87,6 +90,45 @@ def write_ply(path, points):
     os.makedirs(osp.dirname(osp.abspath(path)), exist_ok=True)
     with open(path, 'wb') as fh:
         fh.write(_PLY_HEADER.format(n=points.size).encode('ascii'))
+        fh.write(points.tobytes())
+
+
+def scene_records_to_points(records, counts, names=None):
+    """``(records, counts)`` device tensors of ``kernels.scene_points`` -> ``(a POINT_DTYPE array of the counts[L] records, an ordered
+    {layer name: count})`` (``counts`` and the records are copied to the host once each; synchronises).  ``names``: one per layer, default
+    ``layer0``, ``layer1``, ..."""
+    host = [int(v) for v in counts.cpu().tolist()]
+    L = len(host) - 1
+    names = [f'layer{k}' for k in range(L)] if names is None else list(names)
+    if len(names) != L or len(set(names)) != L:
+        raise ValueError(f'{len(names)} layer names {names} for the {L} layers of counts (one name each, no name twice)')
+    if sum(host[:L]) != host[L] or min(host) < 0:
+        raise ValueError(f'counts {host}: the last entry must be the sum of the others')
+    return records[:host[L]].cpu().numpy().reshape(-1).view(POINT_DTYPE), dict(zip(names, host[:L]))
+
+
+def write_scene_ply(path, points, counts):
+    """Write a scene cloud as ``write_ply`` writes a cloud — the same binary little-endian PLY file, readable by the same tools — with one
+    ``comment layer <name> <count>`` line per layer between the ``format`` line and ``element vertex``: the layers' records follow one another
+    in that order.  ``points``: a ``POINT_DTYPE`` array with ``counts`` an ordered ``{layer name: count}`` that sums to its size, or the
+    ``(records, counts)`` tensors of ``kernels.scene_points`` (copied to the host once) with ``counts`` the layers' names (None:
+    ``scene_records_to_points``' default names).  Parent directories are created.  Host only."""
+    if isinstance(points, (tuple, list)) and len(points) == 2 and torch.is_tensor(points[0]):
+        points, counts = scene_records_to_points(*points, counts)
+    points = np.asarray(points)
+    if points.dtype != POINT_DTYPE:
+        raise TypeError(f'write_scene_ply takes a POINT_DTYPE array or (records, counts) tensors, got dtype {points.dtype}')
+    points = np.ascontiguousarray(points.reshape(-1))
+    layers = [(str(k), int(v)) for k, v in dict(counts).items()]
+    if any(not k or len(k.split()) != 1 for k, _ in layers):
+        raise ValueError(f'layer names must be single words, got {[k for k, _ in layers]}')
+    if any(v < 0 for _, v in layers) or sum(v for _, v in layers) != points.size:
+        raise ValueError(f'the layer counts {dict(layers)} do not sum to the {points.size} points')
+    head, tail = _PLY_HEADER.format(n=points.size).split('element vertex', 1)
+    header = head + ''.join(f'comment layer {k} {v}\n' for k, v in layers) + 'element vertex' + tail
+    os.makedirs(osp.dirname(osp.abspath(path)), exist_ok=True)
+    with open(path, 'wb') as fh:
+        fh.write(header.encode('ascii'))
         fh.write(points.tobytes())
 
 

@@ -1,6 +1,6 @@
 """ctypes binding of libgedepth_hip.so (C ABI: include/gedepth_hip.h, include/gedepth_eval.h for the KITTI evaluation entry points,
 include/gedepth_ddad.h for the DDAD test protocol, include/gedepth_cloud.h for the point clouds and include/gedepth_ground.h for the ground
-embedding's maps, include/gedepth_batch.h for the batched KITTI inference and evaluation).
+embedding's maps, include/gedepth_batch.h for the batched KITTI inference and evaluation, include/gedepth_scene.h for the scene clouds).
 
 The header is the only statement of the ABI: ``SIGNATURES`` (name -> (restype, argtypes)) is parsed from it at import, so a new entry
 point is declared there and nowhere else.  ``call(name, *args)`` launches an entry point that returns an error code and raises on a
@@ -8,8 +8,9 @@ non-zero one; size queries and predicates that return a value are called on ``li
 for include/gedepth_eval.h, ``DDAD_SIGNATURES`` for include/gedepth_ddad.h, ``CLOUD_SIGNATURES`` for include/gedepth_cloud.h and
 ``GROUND_SIGNATURES`` for include/gedepth_ground.h, whose entry points stay outside the versioned ABI of gedepth_hip.h; ``HEADERS`` names the
 five.  ``EXTRA_HEADERS`` is a second table of headers, parsed by the same loop: ``BATCH_SIGNATURES`` for include/gedepth_batch.h (the batched
-KITTI front end, merge and metric sums; its ``GeBatchFrame`` struct is mirrored in gedepth_amd/batch_kernels.py).  ``lib()`` binds the
-entry points of both tables.
+KITTI front end, merge and metric sums; its ``GeBatchFrame`` struct is mirrored in gedepth_amd/batch_kernels.py).  ``SCENE_HEADERS`` is a
+third: ``SCENE_SIGNATURES`` for include/gedepth_scene.h (the scene clouds; its ``GeSceneLayer`` struct is mirrored in
+gedepth_amd/scene_kernels.py).  ``lib()`` binds the entry points of all three tables.
 
 There is deliberately NO fallback: if the shared library is missing, or a tensor is not a
 contiguous CUDA(HIP) tensor of the expected dtype, the call raises.  Build the library with
@@ -26,6 +27,7 @@ LIB_PATH = os.environ.get('GE_LIB') or os.path.join(_HERE, 'csrc', 'libgedepth_h
 HEADERS = {'SIGNATURES': 'gedepth_hip.h', 'EVAL_SIGNATURES': 'gedepth_eval.h', 'DDAD_SIGNATURES': 'gedepth_ddad.h',
            'CLOUD_SIGNATURES': 'gedepth_cloud.h', 'GROUND_SIGNATURES': 'gedepth_ground.h'}      # table name -> its header under include/, in binding order
 EXTRA_HEADERS = {'BATCH_SIGNATURES': 'gedepth_batch.h'}      # headers added after the five: same parsing, same binding
+SCENE_HEADERS = {'SCENE_SIGNATURES': 'gedepth_scene.h'}      # and after those
 GE_F32, GE_BF16 = 0, 1
 GE_COLORIZE_VMIN_DATA, GE_COLORIZE_VMAX_DATA, GE_COLORIZE_EQUAL = 1, 2, 4      # ge_depth_colorize flags
 
@@ -57,7 +59,7 @@ def parse_header(text):
     return sigs
 
 
-for _table, _header in {**HEADERS, **EXTRA_HEADERS}.items():            # SIGNATURES, EVAL_SIGNATURES, ...: name -> (restype, argtypes)
+for _table, _header in {**HEADERS, **EXTRA_HEADERS, **SCENE_HEADERS}.items():            # SIGNATURES, EVAL_SIGNATURES, ...: name -> (restype, argtypes)
     with open(os.path.join(os.path.dirname(_HERE), 'include', _header)) as _fh:
         globals()[_table] = parse_header(_fh.read())
 
@@ -77,7 +79,7 @@ def lib():
                 f'{LIB_PATH} is missing: the gfx950 HIP kernels are not built. '
                 f'Run gedepth_amd/csrc/build.sh (hipcc --offload-arch=gfx950). There is no CPU/eager fallback.')
         handle = ctypes.CDLL(LIB_PATH)
-        for table in (*HEADERS, *EXTRA_HEADERS):
+        for table in (*HEADERS, *EXTRA_HEADERS, *SCENE_HEADERS):
             for name, (res, args) in globals()[table].items():
                 fn = getattr(handle, name)   # AttributeError here == ABI mismatch: fail loudly
                 fn.restype, fn.argtypes = res, args

@@ -2117,3 +2117,6 @@ from .ground_kernels import ground_maps  # noqa: E402,F401
 # --------------------------------------------------------------------- batched KITTI inference / evaluation (csrc/infer_batch.hip,
 # include/gedepth_batch.h)
 from .batch_kernels import depth_metric_sums_batch, infer_front_batch, tta_merge_batch  # noqa: E402,F401
+
+# --------------------------------------------------------------------- scene clouds (csrc/scene.hip, include/gedepth_scene.h)
+from .scene_kernels import SceneLayer, scene_points  # noqa: E402,F401

@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """Evaluate / run a depther — CLI of the reference's tools/test.py:21-68 (config, checkpoint, --eval, --options, --out,
---format-only, --show, --show-dir, --eval-options, --launcher), plus --ply-dir and --ground-dir.
+--format-only, --show, --show-dir, --eval-options, --launcher), plus --ply-dir, --ground-dir and --scene-dir.
 
 With a KITTI tree at ``cfg.data.test.data_root`` this is the Eigen-split protocol of the reference: test pipeline with
 flip test-time augmentation, ``forward_test`` (``return_loss=False``), KB crop + Garg crop, per-image metrics, nan-mean
@@ -19,6 +19,11 @@ ground, over [0, 1]), ``<name>_slope.png`` (the predicted slope over [-5, 5] deg
 slope-adjusted ground depth), or with ``--format-only`` one ``<name>.npz`` of the raw arrays (``BaseDepther.show_ground``).  The frames go
 through the graphed engine (``DepthInferencer.ground_maps``): alone, or with ``--eval ... --device-eval`` in the same pass; with a host-loop
 ``--eval`` it raises.
+
+``--scene-dir DIR`` (KITTI protocol) writes one scene cloud per test image, ``DIR/<ori_filename with .ply>``: the prediction's points coloured
+from the image, the ground prior's in red, the LiDAR ground truth's in green and the slope-adjusted ground plane's in blue, in one binary
+PLY whose header names the layers (``DepthInferencer.scene_points``, ``depth.utils.write_scene_ply``).  The frames go through the graphed
+engine; it runs alone, without ``--eval`` or any other output.
 
 ``--device-eval`` (with ``--eval`` and ``--synthetic 0``; KITTI or DDAD protocol) evaluates on the device: frames go through the graphed
 engine (flip-TTA for KITTI, the single view for DDAD) and each map is reduced to its metric sums by a HIP kernel, so no map is copied to the
@@ -64,6 +69,8 @@ def parse_args(argv=None):
     p.add_argument('--ply-dir', help='directory where one coloured point cloud per test image is saved as a binary .ply')
     p.add_argument('--ground-dir', help='directory where the ground attention / slope / ground-depth pictures of every test image (or, with '
                                         '--format-only, one .npz of the raw maps) are saved; runs the graphed engine')
+    p.add_argument('--scene-dir', help='directory where one scene cloud per test image (prediction, ground prior, ground truth and adjusted '
+                                       'ground plane in one binary .ply) is saved; KITTI protocol, runs the graphed engine, alone')
     p.add_argument('--eval-options', nargs='+', default=None, help='k=v options for evaluate / format_results')
     p.add_argument('--launcher', choices=['none', 'pytorch'], default='none', help='job launcher (pytorch: torch.distributed.run)')
     p.add_argument('--local_rank', '--local-rank', type=int, default=0)
@@ -73,6 +80,13 @@ def parse_args(argv=None):
     args = p.parse_args(argv)
     if 'LOCAL_RANK' not in os.environ:
         os.environ['LOCAL_RANK'] = str(args.local_rank)
+    if args.scene_dir:
+        clash = [flag for flag, on in (('--eval', args.eval), ('--out', args.out), ('--format-only', args.format_only), ('--show', args.show),
+                                       ('--show-dir', args.show_dir), ('--ply-dir', args.ply_dir), ('--ground-dir', args.ground_dir),
+                                       ('--device-eval', args.device_eval)) if on]
+        if clash:
+            raise ValueError(f'--scene-dir cannot be combined with {" / ".join(clash)}: the scene clouds come from an engine loop of their '
+                             'own that returns no results')
     if args.eval and args.format_only:
         raise ValueError('--eval and --format-only cannot be both specified')
     if args.device_eval and (not args.eval or args.synthetic != 0 or args.show or args.show_dir or args.ply_dir):
@@ -117,7 +131,7 @@ def run_dataset(args, cfg):
     with torch.autocast('cuda', dtype=torch.bfloat16, enabled=args.bf16):
         results = test(model, loader, pre_eval=args.eval is not None, format_only=args.format_only, format_args=eval_kwargs,
                        show=args.show, out_dir=args.show_dir, device_eval=args.device_eval, ply_dir=args.ply_dir,
-                       ground_dir=args.ground_dir, eval_batch=args.eval_batch)
+                       ground_dir=args.ground_dir, eval_batch=args.eval_batch, scene_dir=args.scene_dir)
     rank, _ = get_dist_info()
     if rank == 0:
         if args.out:
@@ -138,7 +152,8 @@ def main():
         cfg.merge_from_dict(DictAction.parse(args.options))
     cfg.model.pretrained = None
     cfg.model.train_cfg = None
-    if args.out or args.format_only or args.show or args.show_dir or args.ply_dir or args.ground_dir or args.launcher == 'pytorch':
+    if args.out or args.format_only or args.show or args.show_dir or args.ply_dir or args.ground_dir or args.scene_dir or \
+            args.launcher == 'pytorch':
         return run_dataset(args, cfg)
     model = build_depther(cfg.model, test_cfg=cfg.get('test_cfg'))
     if args.checkpoint:
