@@ -30,6 +30,7 @@ import test_inference_gpu as TI
 import test_kernels_gpu as TK
 import test_msda_hist_batched_gpu as HB
 import test_visualize_gpu as TV
+import test_window_attn_gpu as TW
 from test_visualize_cpu import CASES as COLORIZE_CASES
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -72,6 +73,10 @@ CASES = [
                                                          ((3, 5), (10, 9), (11, 35)), (0, 3))),
     Case('window_attn v3 fp8', WIN, _each(lambda c, gs: TK.test_window_attention_fp8_forward(c.dev, *gs),
                                           (((2, 11, 35, 3), 0), ((2, 11, 35, 3), 3), ((2, 10, 9, 6), 0)))),
+    # routed inputs, bit for bit, where the last window row and column hold one real row / column (variants 1, 2, 3); 243 windows over 64 persistent
+    # workgroups per head (test_window_attn_gpu.py)
+    Case('window_attn routed (8,15) nH6 shift 3', WIN, lambda c: TW.test_routing_bit_for_bit(c.dev, (1, 8, 15, 6), 3)),
+    Case('window_attn many windows per workgroup', WIN, lambda c: TW.test_many_windows_per_workgroup(c.dev)),
     # ---- deformable attention: streaming and query-grid kernels, every kernel-selection mode, binned / atomic backward
     Case('msda streaming fp32 small+tiny', MSDA, _each(lambda c, b, sh: TK.test_msda_fp32_fwd_bwd(c.dev, b, sh, c.monkeypatch), (True, False), (SMALL, TINY))),
     Case('msda window kernels ragged f32', MSDA, lambda c: TK.test_msda_window_kernels(c.dev, 'ragged', 'f32')),        # modes 7 3 0 8 13 61 125 29
@@ -224,7 +229,7 @@ def test_guarded(dev, monkeypatch, golden, case, poison):
     # cached per-stream workspaces / accumulators made by earlier (unguarded) tests would bypass the frames
     for cache in ('_LN_ACC', '_COLSUM_WS', '_POS_ROWS', '_TILE_ORDER_CACHE', '_MM_VALUE_CHOICE'):
         monkeypatch.setattr(kernels, cache, {})
-    guard.install(monkeypatch, [kernels, optim, TK, TI, HB, CB, TX], binding=hip, frame_copies_on=dev)
+    guard.install(monkeypatch, [kernels, optim, TK, TI, HB, CB, TX, TW], binding=hip, frame_copies_on=dev)
     failure = None
     try:
         case.run(Ctx(dev, monkeypatch, golden))           # 2. the value test's own comparisons, NaN-strict
