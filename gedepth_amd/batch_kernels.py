@@ -1,4 +1,4 @@
-"""Wrappers of the batched KITTI entry points (csrc/infer_batch.hip, include/gedepth_batch.h): ``infer_front_batch``, ``tta_merge_batch`` and
+"""Wrappers of the batched KITTI entry points (csrc/infer.hip, csrc/eval.hip; include/gedepth_batch.h): ``infer_front_batch``, ``tta_merge_batch`` and
 ``depth_metric_sums_batch`` — one launch (the metric sums: two) for up to ``BATCH_MAX`` frames, each frame with the bits of
 ``kernels.infer_front`` / ``kernels.tta_merge`` / ``kernels.depth_metric_sums``.  ``kernels`` re-exports them; they launch through
 ``kernels._launch`` and live in a module of their own for the reason eval_kernels.py gives.

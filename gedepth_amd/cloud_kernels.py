@@ -1,4 +1,4 @@
-"""Wrapper of the point-cloud entry point (csrc/cloud.hip, include/gedepth_cloud.h).  ``kernels.depth_points`` is this function: it launches
+"""Wrapper of the point-cloud entry point (csrc/scene.hip, include/gedepth_cloud.h).  ``kernels.depth_points`` is this function: it launches
 through ``kernels._launch`` like every other wrapper, and lives in a module of its own for the reason eval_kernels.py gives (kernels.py holds
 the entry points of include/gedepth_hip.h)."""
 import torch

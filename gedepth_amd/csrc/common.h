@@ -240,53 +240,3 @@ static inline unsigned ge_blocks(long n, int per_block, long cap = 1 << 20) {
   if (b > cap) b = cap;
   return (unsigned)b;
 }
-
-// ---- KITTI inference front end and flip-TTA merge: the per-group bodies shared by the single-frame kernels (infer.hip) and the batched
-// ones (infer_batch.hip), so that a frame gets the same bits from either.
-struct InferNorm { double mean[3], stdinv[3]; float pe_max, depth_scale; int to_rgb; };
-
-// Group i (four consecutive pixels of row i / G of the crop window) of one frame -> view 0 and, reversed, the mirrored position of view 1.
-// dst (views, 5, Hc, Wc) planar f32 of THIS frame; G = Wc / 4, n = Hc * Wc.
-__device__ __forceinline__ void ge_infer_front_group(const uint8_t* __restrict__ bgr, const float* __restrict__ pe, float* __restrict__ dst, int W,
-                                                     int top, int left, int Wc, int views, const InferNorm& p, long i, int G, long n) {
-#pragma clang fp contract(off)
-  const int y = (int)(i / G), g = (int)(i - (long)y * G);
-  const long s = (long)(y + top) * W + (left + 4 * g);
-  const uint8_t* px = bgr + s * 3;
-  float o[5][4];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      // ge_aug_load: (float)u8; ge_aug_color_normalize: truncf (a no-op on a uint8 value), BGR -> RGB, f64 (x - mean) * (1 / std)
-      const float t = truncf((float)px[3 * k + c]);
-      const int oc = p.to_rgb ? 2 - c : c;
-      o[oc][k] = (float)(((double)t - p.mean[oc]) * p.stdinv[oc]);
-    }
-    const float raw = pe[s + k];
-    float f = raw;                                        // LoadImageFromFile: > pe_max or < 0 zeroed; Normalize: / depth_scale where > 0
-    if (f > p.pe_max) f = 0.f;
-    if (f < 0.f) f = 0.f;
-    if (f > 0.f) f = f / p.depth_scale;
-    o[3][k] = f;
-    o[4][k] = raw;
-  }
-  const long r = (long)y * Wc;
-#pragma unroll
-  for (int c = 0; c < 5; ++c) *(float4*)(dst + c * n + r + 4 * g) = make_float4(o[c][0], o[c][1], o[c][2], o[c][3]);
-  if (views == 2) {
-    float* d1 = dst + 5 * n + r + (Wc - 4 - 4 * g);      // ge_aug_window(flip): x -> Wc - 1 - x
-#pragma unroll
-    for (int c = 0; c < 5; ++c) *(float4*)(d1 + c * n) = make_float4(o[c][3], o[c][2], o[c][1], o[c][0]);
-  }
-}
-
-// Group i of the merge of one frame's two flip views: (out0 + flip(out1)) / 2.  src (2, H, W), dst (H, W) of THIS frame; G = W / 4, n = H * W.
-__device__ __forceinline__ void ge_tta_merge_group(const float* __restrict__ src, float* __restrict__ dst, int W, long i, int G, long n) {
-#pragma clang fp contract(off)
-  const int y = (int)(i / G), g = (int)(i - (long)y * G);
-  const long r = (long)y * W;
-  const float4 a = *(const float4*)(src + r + 4 * g);
-  const float4 b = *(const float4*)(src + n + r + (W - 4 - 4 * g));
-  *(float4*)(dst + r + 4 * g) = make_float4((a.x + b.w) / 2.f, (a.y + b.z) / 2.f, (a.z + b.y) / 2.f, (a.w + b.x) / 2.f);
-}

@@ -9,21 +9,118 @@
 //
 // Reduction without atomics (the library is built with -munsafe-fp-atomics, and an atomic sum would depend on arrival order): a lane sums
 // its groups of four pixels, a wave folds its lanes with shuffles, a workgroup folds its four waves through LDS and stores ten doubles to
-// partials[block]; metrics_fold_k, one workgroup on the same stream, adds the partials in index order.  Same bits on every run.
+// partials[block]; metrics_fold_k, one workgroup per image on the same stream, adds the partials in index order.  Same bits on every run.
+// The KITTI kernels take up to GE_BATCH_MAX images per launch (ge_depth_metrics_batch, include/gedepth_batch.h), the image on blockIdx.y
+// of the first pass and blockIdx.x of the fold; ge_depth_metrics is their launch of one image.
 #pragma clang fp contract(off)
-#include "eval_sums.h"
+#include "batch_table.h"
 #include "../../include/gedepth_eval.h"
 #include "../../include/gedepth_ddad.h"
 
+#define GE_EVAL_THREADS 256
+#define GE_EVAL_GROUPS 2           // groups of four pixels per lane before the grid-stride loop goes round again
+#define GE_EVAL_MAX_BLOCKS 1024
+#define GE_EVAL_SUMS 10
+
+struct EvalArgs { int Hc, Wc, r0, r1, c0, c1; float scale, lo, hi; };     // the crop, the protocol's rectangle in it, gt = raw / scale, lo < gt < hi
+
+// One pixel: `gt` in metres (f32), `inside` = it lies in the protocol's rectangle; it counts when also lo < gt < hi.
+__device__ __forceinline__ void metric_pixel(float p, float gt, bool inside, float lo, float hi, double acc[GE_EVAL_SUMS]) {
+  if (!(inside && gt > lo && gt < hi)) return;
+  const float q0 = gt / p, q1 = p / gt;
+  const float ratio = (q0 > q1 || q0 != q0) ? q0 : q1;               // numpy.maximum: NaN wins
+  acc[0] += 1.0;
+  acc[1] += ratio < 1.25f ? 1.0 : 0.0;
+  acc[2] += ratio < 1.5625f ? 1.0 : 0.0;
+  acc[3] += ratio < 1.953125f ? 1.0 : 0.0;
+  const double g = (double)gt, q = (double)p;
+  const double d = g - q, d2 = d * d;
+  const double l = log(q) - log(g);
+  acc[4] += fabs(d) / g;
+  acc[5] += d2 / g;
+  acc[6] += d2;
+  acc[7] += l;
+  acc[8] += l * l;
+  acc[9] += fabs(log10(g) - log10(q));
+}
+
+// lane sums -> wave (shuffles) -> workgroup (LDS across the four waves) -> partials[block]
+// `row`: the ten doubles of this workgroup in the partials
+__device__ __forceinline__ void metrics_block_fold(double acc[GE_EVAL_SUMS], double (*red)[GE_EVAL_SUMS], double* __restrict__ row) {
+#pragma unroll
+  for (int k = 0; k < GE_EVAL_SUMS; ++k)
+    for (int s = GE_WAVE / 2; s > 0; s >>= 1) acc[k] += __shfl_down(acc[k], s, GE_WAVE);
+  const int wave = threadIdx.x / GE_WAVE, lane = threadIdx.x % GE_WAVE;
+  if (lane == 0) {
+#pragma unroll
+    for (int k = 0; k < GE_EVAL_SUMS; ++k) red[wave][k] = acc[k];
+  }
+  __syncthreads();
+  if (threadIdx.x < GE_EVAL_SUMS) {
+    double s = red[0][threadIdx.x];
+    for (int w = 1; w < GE_EVAL_THREADS / GE_WAVE; ++w) s += red[w][threadIdx.x];
+    row[threadIdx.x] = s;
+  }
+}
+
+// One lane's sums over the crop of one image, as workgroup blockIdx.x of gridDim.x.  `gt_raw` (row stride W) starts at the crop's corner.
+// PV: pred is 16-byte aligned and Wc % 4 == 0 (one float4 per group).  GV (only with PV): every group's four ground-truth values are
+// 8-byte aligned (W % 4 == 0, left % 4 == 0, base 8-byte aligned).  Otherwise element loads, each one bounds-checked against Wc.
 template <bool PV, bool GV>
-__global__ void __launch_bounds__(GE_EVAL_THREADS) metrics_partial_k(const float* __restrict__ pred, const uint16_t* __restrict__ gt_raw,
-                                                                     EvalArgs a, double* __restrict__ partials) {
+__device__ __forceinline__ void metrics_window_sums(const float* __restrict__ pred, const uint16_t* __restrict__ gt_raw, int W, const EvalArgs& a,
+                                                    double acc[GE_EVAL_SUMS]) {
+  const int G = (a.Wc + 3) >> 2;                                      // groups per row
+  const long items = (long)a.Hc * G;
+  for (long it = (long)blockIdx.x * GE_EVAL_THREADS + threadIdx.x; it < items; it += (long)gridDim.x * GE_EVAL_THREADS) {
+    const int r = (int)(it / G), c = 4 * (int)(it - (long)r * G);
+    if (r < a.r0 || r >= a.r1 || c + 4 <= a.c0 || c >= a.c1) continue;        // nothing of this group is in the rectangle: no loads
+    const float* ps = pred + (long)r * a.Wc + c;
+    const uint16_t* gs = gt_raw + (long)r * W + c;
+    float p[4];
+    uint16_t raw[4];
+    if (PV) {
+      const float4 t = *(const float4*)ps;
+      p[0] = t.x; p[1] = t.y; p[2] = t.z; p[3] = t.w;
+    } else {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) p[k] = c + k < a.Wc ? ps[k] : 1.f;
+    }
+    if (PV && GV) {
+      const uint2 t = *(const uint2*)gs;
+      raw[0] = (uint16_t)t.x; raw[1] = (uint16_t)(t.x >> 16); raw[2] = (uint16_t)t.y; raw[3] = (uint16_t)(t.y >> 16);
+    } else {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) raw[k] = c + k < a.Wc ? gs[k] : (uint16_t)0;
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k)                                                   // gt = (float)raw / depth_scale; c1 <= Wc covers the row's tail
+      metric_pixel(p[k], (float)raw[k] / a.scale, c + k >= a.c0 && c + k < a.c1, a.lo, a.hi, acc);
+  }
+}
+
+// the block partition of one image: it depends on (Hc, Wc) only
+static unsigned metrics_blocks(int Hc, int Wc) {
+  return ge_blocks((long)Hc * ((Wc + 3) >> 2), GE_EVAL_THREADS * GE_EVAL_GROUPS, GE_EVAL_MAX_BLOCKS);
+}
+
+// Image f = blockIdx.y of the table (batch_table.h; `image` the (H, W) uint16 ground truth): pred (n, Hc, Wc), partials (n, gridDim.x, 10).
+// The ground truth's 8-byte loads (GV) are a per-image choice, uniform over the workgroup.  The images share the block partition, so an
+// image's bits do not depend on how many images the launch has: ge_depth_metrics is the launch of one.
+template <bool PV>
+__global__ void __launch_bounds__(GE_EVAL_THREADS) metrics_partial_k(const float* __restrict__ pred, BatchTable t, EvalArgs a,
+                                                                     double* __restrict__ partials) {
   __shared__ double red[GE_EVAL_THREADS / GE_WAVE][GE_EVAL_SUMS];
+  const GeBatchFrame fr = t.f[blockIdx.y];
   double acc[GE_EVAL_SUMS];
 #pragma unroll
   for (int k = 0; k < GE_EVAL_SUMS; ++k) acc[k] = 0.0;
-  metrics_window_sums<PV, GV>(pred, gt_raw, a, acc);                  // eval_sums.h
-  metrics_block_fold(acc, red, partials + (long)blockIdx.x * GE_EVAL_SUMS);
+  const float* p = pred + (long)blockIdx.y * a.Hc * a.Wc;
+  const uint16_t* gt = (const uint16_t*)fr.image + ((long)fr.top * fr.W + fr.left);
+  if (PV && ((uintptr_t)fr.image & 7) == 0 && (fr.W & 3) == 0 && (fr.left & 3) == 0)
+    metrics_window_sums<PV, true>(p, gt, fr.W, a, acc);
+  else
+    metrics_window_sums<PV, false>(p, gt, fr.W, a, acc);
+  metrics_block_fold(acc, red, partials + ((long)blockIdx.y * gridDim.x + blockIdx.x) * GE_EVAL_SUMS);
 }
 
 // DDAD protocol (depth/datasets/ddad.py pre_eval): the (h, w) prediction is resized bilinearly, align_corners = True, to the (H, W) ground
@@ -76,42 +173,63 @@ __global__ void __launch_bounds__(GE_EVAL_THREADS) metrics_resized_partial_k(con
   metrics_block_fold(acc, red, partials + (long)blockIdx.x * GE_EVAL_SUMS);
 }
 
+// image f = blockIdx.x: its partials in index order
 __global__ void __launch_bounds__(GE_WAVE) metrics_fold_k(const double* __restrict__ partials, int blocks, double* __restrict__ sums) {
   if (threadIdx.x >= GE_EVAL_SUMS) return;
+  const double* p = partials + (long)blockIdx.x * blocks * GE_EVAL_SUMS;
   double s = 0.0;
-  for (int b = 0; b < blocks; ++b) s += partials[(long)b * GE_EVAL_SUMS + threadIdx.x];
-  sums[threadIdx.x] = s;
+  for (int b = 0; b < blocks; ++b) s += p[(long)b * GE_EVAL_SUMS + threadIdx.x];
+  sums[(long)blockIdx.x * GE_EVAL_SUMS + threadIdx.x] = s;
 }
 
-extern "C" size_t ge_depth_metrics_workspace(int Hc, int Wc) {
-  if (Hc <= 0 || Wc <= 0) return 0;
-  return (size_t)metrics_blocks(Hc, Wc) * GE_EVAL_SUMS * sizeof(double);
+extern "C" size_t ge_depth_metrics_batch_workspace(int n, int Hc, int Wc) {
+  if (n < 1 || n > GE_BATCH_MAX || Hc <= 0 || Wc <= 0) return 0;
+  return (size_t)n * metrics_blocks(Hc, Wc) * GE_EVAL_SUMS * sizeof(double);
+}
+extern "C" size_t ge_depth_metrics_workspace(int Hc, int Wc) { return ge_depth_metrics_batch_workspace(1, Hc, Wc); }
+
+// what both KITTI entry points refuse, but for their own rule on the prediction's alignment
+static int metrics_check(const float* pred, const GeBatchFrame* frames, int n, const EvalArgs& a, const double* partials, const double* sums) {
+  if (!pred || !partials || !sums) return GE_ERR_BAD_ARG;
+  if (int e = batch_frames_check(frames, n, a.Hc, a.Wc, false)) return e;                           // every window lies in its frame
+  if (a.r0 < 0 || a.r0 > a.Hc || a.r1 < 0 || a.r1 > a.Hc || a.c0 < 0 || a.c0 > a.Wc || a.c1 < 0 || a.c1 > a.Wc) return GE_ERR_BAD_ARG;
+  if (((uintptr_t)partials & 7) || ((uintptr_t)sums & 7)) return GE_ERR_UNSUPPORTED;
+  for (int f = 0; f < n; ++f)
+    if ((uintptr_t)frames[f].image & 1) return GE_ERR_UNSUPPORTED;
+  return GE_OK;
+}
+// the two launches over n checked images; pv: the prediction takes float4 loads
+static int metrics_launch(const float* pred, const GeBatchFrame* frames, int n, bool pv, const EvalArgs& a, double* partials, double* sums,
+                          void* stream) {
+  hipStream_t s = ge_stream(stream);
+  const unsigned blocks = metrics_blocks(a.Hc, a.Wc);
+  const dim3 grid(blocks, (unsigned)n);
+  if (pv)
+    metrics_partial_k<true><<<grid, GE_EVAL_THREADS, 0, s>>>(pred, batch_table(frames, n), a, partials);
+  else
+    metrics_partial_k<false><<<grid, GE_EVAL_THREADS, 0, s>>>(pred, batch_table(frames, n), a, partials);
+  GE_LAUNCH_CHECK();
+  metrics_fold_k<<<(unsigned)n, GE_WAVE, 0, s>>>(partials, (int)blocks, sums);
+  GE_LAUNCH_CHECK();
+  return GE_OK;
 }
 
 extern "C" int ge_depth_metrics(const float* pred, const uint16_t* gt_raw, int H, int W, int top, int left, int Hc, int Wc,
                                 int r0, int r1, int c0, int c1, float depth_scale, float min_depth, float max_depth,
                                 double* partials, double* sums, void* stream) {
-  if (!pred || !gt_raw || !partials || !sums || H <= 0 || W <= 0 || Hc <= 0 || Wc <= 0) return GE_ERR_BAD_ARG;
-  if (top < 0 || left < 0 || Hc > H - top || Wc > W - left) return GE_ERR_BAD_ARG;                  // the window lies in the frame
-  if (r0 < 0 || r0 > Hc || r1 < 0 || r1 > Hc || c0 < 0 || c0 > Wc || c1 < 0 || c1 > Wc) return GE_ERR_BAD_ARG;
-  if (((uintptr_t)pred & 3) || ((uintptr_t)gt_raw & 1) || ((uintptr_t)partials & 7) || ((uintptr_t)sums & 7)) return GE_ERR_UNSUPPORTED;
-  hipStream_t s = ge_stream(stream);
-  EvalArgs a;
-  a.W = W; a.top = top; a.left = left; a.Hc = Hc; a.Wc = Wc; a.r0 = r0; a.r1 = r1; a.c0 = c0; a.c1 = c1;
-  a.scale = depth_scale; a.lo = min_depth; a.hi = max_depth;
-  const unsigned blocks = metrics_blocks(Hc, Wc);
-  const bool pv = ((uintptr_t)pred & 15) == 0 && (Wc & 3) == 0;
-  const bool gv = pv && ((uintptr_t)gt_raw & 7) == 0 && (W & 3) == 0 && (left & 3) == 0;
-  if (gv)
-    metrics_partial_k<true, true><<<blocks, GE_EVAL_THREADS, 0, s>>>(pred, gt_raw, a, partials);
-  else if (pv)
-    metrics_partial_k<true, false><<<blocks, GE_EVAL_THREADS, 0, s>>>(pred, gt_raw, a, partials);
-  else
-    metrics_partial_k<false, false><<<blocks, GE_EVAL_THREADS, 0, s>>>(pred, gt_raw, a, partials);
-  GE_LAUNCH_CHECK();
-  metrics_fold_k<<<1, GE_WAVE, 0, s>>>(partials, (int)blocks, sums);
-  GE_LAUNCH_CHECK();
-  return GE_OK;
+  const GeBatchFrame fr = {gt_raw, nullptr, H, W, top, left};
+  const EvalArgs a = {Hc, Wc, r0, r1, c0, c1, depth_scale, min_depth, max_depth};
+  if (int e = metrics_check(pred, &fr, 1, a, partials, sums)) return e;
+  if ((uintptr_t)pred & 3) return GE_ERR_UNSUPPORTED;
+  return metrics_launch(pred, &fr, 1, ((uintptr_t)pred & 15) == 0 && (Wc & 3) == 0, a, partials, sums, stream);
+}
+
+extern "C" int ge_depth_metrics_batch(const float* pred, const GeBatchFrame* frames, int n, int Hc, int Wc, int r0, int r1, int c0, int c1,
+                                      float depth_scale, float min_depth, float max_depth, double* partials, double* sums, void* stream) {
+  const EvalArgs a = {Hc, Wc, r0, r1, c0, c1, depth_scale, min_depth, max_depth};
+  if (int e = metrics_check(pred, frames, n, a, partials, sums)) return e;
+  if ((Wc & 3) || ((uintptr_t)pred & 15)) return GE_ERR_UNSUPPORTED;
+  return metrics_launch(pred, frames, n, true, a, partials, sums, stream);
 }
 
 extern "C" size_t ge_depth_metrics_resized_workspace(int H, int W) { return ge_depth_metrics_workspace(H, W); }

@@ -1,24 +1,75 @@
-// Single-frame inference (depth/apis/inference.py of the reference; gedepth_amd/depth/apis/inference.py here): the KITTI test
-// pipeline's per-frame front end and the flip-TTA merge of encoder_decoder.py aug_test, each as one streaming launch around the
-// batch-2 forward of the two flip views.
+// KITTI / DDAD inference (depth/apis/inference.py of the reference; gedepth_amd/depth/apis/inference.py and batch_inference.py here): the
+// test pipeline's per-frame front end and the flip-TTA merge of encoder_decoder.py aug_test, each as one streaming launch around the
+// forward of the flip views.  The KITTI kernels take up to GE_BATCH_MAX frames per launch, the frame index on blockIdx.y
+// (include/gedepth_batch.h); the single-frame entry points of gedepth_hip.h are their launch of one frame.
 //
-// ge_infer_front restates, op for op, LoadImageFromFile(USEPE) -> KBCrop -> MultiScaleFlipAug(RandomFlip, Normalize) of
+// The KITTI front end restates, op for op, LoadImageFromFile(USEPE) -> KBCrop -> MultiScaleFlipAug(RandomFlip, Normalize) of
 // configs/_base_/datasets/kitti_gedepth.py, i.e. the composition ge_aug_load -> ge_aug_color_normalize(color_on = 0) ->
 // ge_aug_window(flip) of aug.hip, so that both produce the same bits.  Each thread reads four consecutive pixels of the crop window
 // once and writes them to view 0 and, reversed, to the mirrored position of view 1: one read of the window, 16-byte stores to both
 // views, no LDS.  Pure streaming work (~3.3 MB read, 17.1 MB written per frame): launch-latency-sized, no MFMA.
 #pragma clang fp contract(off)
-#include "common.h"
+#include "batch_table.h"
 #include "../../include/gedepth_ddad.h"
 
-// dst (views, 5, Hc, Wc) planar f32; view 1 = view 0 mirrored horizontally.  Wc % 4 == 0, dst 16-byte aligned (checked by the caller).
-// The group's body is ge_infer_front_group of common.h, which ge_infer_front_batch (infer_batch.hip) runs per frame too.
-__global__ void __launch_bounds__(256) infer_front_k(const uint8_t* __restrict__ bgr, const float* __restrict__ pe, float* __restrict__ dst,
-                                                     int W, int top, int left, int Hc, int Wc, int views, InferNorm p) {
+struct InferNorm { double mean[3], stdinv[3]; float pe_max, depth_scale; int to_rgb; };
+static InferNorm infer_norm(float pe_max, const double* mean3, const double* std3, float depth_scale, int to_rgb) {
+  InferNorm p;
+  for (int c = 0; c < 3; ++c) { p.mean[c] = mean3[c]; p.stdinv[c] = 1.0 / std3[c]; }
+  p.pe_max = pe_max; p.depth_scale = depth_scale; p.to_rgb = to_rgb;
+  return p;
+}
+
+extern "C" size_t ge_batch_frame_size(void) { return sizeof(GeBatchFrame); }
+
+// Frame f = blockIdx.y of the table (batch_table.h) -> images views * f .. views * f + views - 1 of dst (views * n, 5, Hc, Wc) planar f32;
+// view 1 = view 0 mirrored horizontally.  Wc % 4 == 0, dst 16-byte aligned (checked by the caller).  The frames share grid.x, so a frame's
+// bits do not depend on how many frames the launch has: ge_infer_front is the launch of one.
+__global__ void __launch_bounds__(256) infer_front_k(BatchTable t, float* __restrict__ dst, int Hc, int Wc, int views, InferNorm p) {
+  const GeBatchFrame fr = t.f[blockIdx.y];
+  const uint8_t* __restrict__ bgr = (const uint8_t*)fr.image;
+  const float* __restrict__ pe = (const float*)fr.aux;
   const int G = Wc >> 2;                                   // float4 groups per output row
   const long n = (long)Hc * Wc, groups = (long)Hc * G;
-  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < groups; i += (long)gridDim.x * 256)
-    ge_infer_front_group(bgr, pe, dst, W, top, left, Wc, views, p, i, G, n);
+  dst += (long)blockIdx.y * views * 5 * n;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < groups; i += (long)gridDim.x * 256) {
+    const int y = (int)(i / G), g = (int)(i - (long)y * G);
+    const long s = (long)(y + fr.top) * fr.W + (fr.left + 4 * g);
+    const uint8_t* px = bgr + s * 3;
+    float o[5][4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        // ge_aug_load: (float)u8; ge_aug_color_normalize: truncf (a no-op on a uint8 value), BGR -> RGB, f64 (x - mean) * (1 / std)
+        const float v = truncf((float)px[3 * k + c]);
+        const int oc = p.to_rgb ? 2 - c : c;
+        o[oc][k] = (float)(((double)v - p.mean[oc]) * p.stdinv[oc]);
+      }
+      const float raw = pe[s + k];
+      float f = raw;                                        // LoadImageFromFile: > pe_max or < 0 zeroed; Normalize: / depth_scale where > 0
+      if (f > p.pe_max) f = 0.f;
+      if (f < 0.f) f = 0.f;
+      if (f > 0.f) f = f / p.depth_scale;
+      o[3][k] = f;
+      o[4][k] = raw;
+    }
+    const long r = (long)y * Wc;
+#pragma unroll
+    for (int c = 0; c < 5; ++c) *(float4*)(dst + c * n + r + 4 * g) = make_float4(o[c][0], o[c][1], o[c][2], o[c][3]);
+    if (views == 2) {
+      float* d1 = dst + 5 * n + r + (Wc - 4 - 4 * g);      // ge_aug_window(flip): x -> Wc - 1 - x
+#pragma unroll
+      for (int c = 0; c < 5; ++c) *(float4*)(d1 + c * n) = make_float4(o[c][3], o[c][2], o[c][1], o[c][0]);
+    }
+  }
+}
+// the launch of n checked frames
+static int infer_front_launch(const GeBatchFrame* frames, int n, float* dst, int Hc, int Wc, int views, const InferNorm& p, void* stream) {
+  const dim3 grid(ge_blocks((long)Hc * (Wc / 4), 256, 65536), (unsigned)n);
+  infer_front_k<<<grid, 256, 0, ge_stream(stream)>>>(batch_table(frames, n), dst, Hc, Wc, views, p);
+  GE_LAUNCH_CHECK();
+  return GE_OK;
 }
 extern "C" int ge_infer_front(const uint8_t* bgr_hwc, const float* pe, float* dst, int H, int W, int top, int left, int Hc, int Wc,
                               int views, float pe_max, const double* mean3, const double* std3, float depth_scale, int to_rgb,
@@ -26,14 +77,18 @@ extern "C" int ge_infer_front(const uint8_t* bgr_hwc, const float* pe, float* ds
   if (!bgr_hwc || !pe || !dst || !mean3 || !std3 || H <= 0 || W <= 0 || Hc <= 0 || Wc <= 0 || top < 0 || left < 0 || top + Hc > H ||
       left + Wc > W || (views != 1 && views != 2))
     return GE_ERR_BAD_ARG;
+  if ((Wc & 3) || ((uintptr_t)dst & 15)) return GE_ERR_UNSUPPORTED;          // (the ground depth's alignment: ge_infer_front_batch only)
+  const GeBatchFrame fr = {bgr_hwc, pe, H, W, top, left};
+  return infer_front_launch(&fr, 1, dst, Hc, Wc, views, infer_norm(pe_max, mean3, std3, depth_scale, to_rgb), stream);
+}
+extern "C" int ge_infer_front_batch(const GeBatchFrame* frames, int n, float* dst, int Hc, int Wc, int views, float pe_max,
+                                    const double* mean3, const double* std3, float depth_scale, int to_rgb, void* stream) {
+  if (!dst || !mean3 || !std3 || (views != 1 && views != 2)) return GE_ERR_BAD_ARG;
+  if (int e = batch_frames_check(frames, n, Hc, Wc, true)) return e;
   if ((Wc & 3) || ((uintptr_t)dst & 15)) return GE_ERR_UNSUPPORTED;
-  InferNorm p;
-  for (int c = 0; c < 3; ++c) { p.mean[c] = mean3[c]; p.stdinv[c] = 1.0 / std3[c]; }
-  p.pe_max = pe_max; p.depth_scale = depth_scale; p.to_rgb = to_rgb;
-  const long groups = (long)Hc * (Wc / 4);
-  infer_front_k<<<ge_blocks(groups, 256, 65536), 256, 0, ge_stream(stream)>>>(bgr_hwc, pe, dst, W, top, left, Hc, Wc, views, p);
-  GE_LAUNCH_CHECK();
-  return GE_OK;
+  for (int f = 0; f < n; ++f)
+    if ((uintptr_t)frames[f].aux & 3) return GE_ERR_UNSUPPORTED;
+  return infer_front_launch(frames, n, dst, Hc, Wc, views, infer_norm(pe_max, mean3, std3, depth_scale, to_rgb), stream);
 }
 
 // ge_infer_front_ddad restates LoadDDADImageFromFile(USEPE, USE_DYNAMIC_PE) -> DDADResize(shape, depth = False) -> Normalize of
@@ -83,26 +138,34 @@ extern "C" int ge_infer_front_ddad(const uint8_t* bgr_hwc, const float* pe, floa
   if (!bgr_hwc || !pe || !dst || !mean3 || !std3 || H <= 0 || W <= 0 || Hd <= 0 || Wd <= 0) return GE_ERR_BAD_ARG;
   if (Hd > H || Wd > W) return GE_ERR_UNSUPPORTED;          // the area filter is the shrinking branch, as in ge_aug_area_u8
   if ((Wd & 3) || ((uintptr_t)dst & 15) || ((uintptr_t)pe & 3)) return GE_ERR_UNSUPPORTED;
-  InferNorm p;
-  for (int c = 0; c < 3; ++c) { p.mean[c] = mean3[c]; p.stdinv[c] = 1.0 / std3[c]; }
-  p.pe_max = pe_max; p.depth_scale = depth_scale; p.to_rgb = to_rgb;
   const long groups = (long)Hd * (Wd / 4);
-  infer_front_ddad_k<<<ge_blocks(groups, 256, 65536), 256, 0, ge_stream(stream)>>>(bgr_hwc, pe, dst, H, W, Hd, Wd, p);
+  infer_front_ddad_k<<<ge_blocks(groups, 256, 65536), 256, 0, ge_stream(stream)>>>(bgr_hwc, pe, dst, H, W, Hd, Wd,
+                                                                                    infer_norm(pe_max, mean3, std3, depth_scale, to_rgb));
   GE_LAUNCH_CHECK();
   return GE_OK;
 }
 
 // encoder_decoder.py aug_test over the two flip views: (out0 + flip(out1)) / 2, in that order (sum, then divide by the view count;
-// the division by 2 is exact).  src (2, H, W) f32, dst (H, W) f32; W % 4 == 0, both 16-byte aligned.
+// the division by 2 is exact).  Frame f = blockIdx.y: src (2 n, H, W) f32, frame-major, dst (n, H, W) f32; W % 4 == 0, both 16-byte aligned.
 __global__ void __launch_bounds__(256) tta_merge_k(const float* __restrict__ src, float* __restrict__ dst, int H, int W) {
   const int G = W >> 2;
   const long n = (long)H * W, groups = (long)H * G;
-  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < groups; i += (long)gridDim.x * 256) ge_tta_merge_group(src, dst, W, i, G, n);
+  src += (long)blockIdx.y * 2 * n;
+  dst += (long)blockIdx.y * n;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < groups; i += (long)gridDim.x * 256) {
+    const int y = (int)(i / G), g = (int)(i - (long)y * G);
+    const long r = (long)y * W;
+    const float4 a = *(const float4*)(src + r + 4 * g);
+    const float4 b = *(const float4*)(src + n + r + (W - 4 - 4 * g));
+    *(float4*)(dst + r + 4 * g) = make_float4((a.x + b.w) / 2.f, (a.y + b.z) / 2.f, (a.z + b.y) / 2.f, (a.w + b.x) / 2.f);
+  }
 }
-extern "C" int ge_tta_merge(const float* src, float* dst, int H, int W, void* stream) {
-  if (!src || !dst || H <= 0 || W <= 0) return GE_ERR_BAD_ARG;
+extern "C" int ge_tta_merge_batch(const float* src, float* dst, int n, int H, int W, void* stream) {
+  if (!src || !dst || n < 1 || n > GE_BATCH_MAX || H <= 0 || W <= 0) return GE_ERR_BAD_ARG;
   if ((W & 3) || ((uintptr_t)src & 15) || ((uintptr_t)dst & 15)) return GE_ERR_UNSUPPORTED;
-  tta_merge_k<<<ge_blocks((long)H * (W / 4), 256, 65536), 256, 0, ge_stream(stream)>>>(src, dst, H, W);
+  const dim3 grid(ge_blocks((long)H * (W / 4), 256, 65536), (unsigned)n);
+  tta_merge_k<<<grid, 256, 0, ge_stream(stream)>>>(src, dst, H, W);
   GE_LAUNCH_CHECK();
   return GE_OK;
 }
+extern "C" int ge_tta_merge(const float* src, float* dst, int H, int W, void* stream) { return ge_tta_merge_batch(src, dst, 1, H, W, stream); }

@@ -1,22 +1,75 @@
-// Scene clouds (tools/misc/visualize_point-cloud_kitti_gt_pe_pred.py of the reference; include/gedepth_scene.h): the kept points of up to
-// four depth layers over one candidate grid — the prediction coloured from the frame, the ground-plane prior, the LiDAR ground truth
-// (uint16, divided here) and the slope-adjusted ground plane in constant colours — as ONE hole-free buffer of 16-byte PLY records, layer
-// after layer, each layer in row-major candidate order.
+// Point clouds from depth maps (tools/misc/visualize_point-cloud_kitti.py and visualize_point-cloud_kitti_gt_pe_pred.py of the reference;
+// include/gedepth_cloud.h, include/gedepth_scene.h; gedepth_amd/depth/utils/point_cloud.py here): back-project the pixels whose depth is in
+// range through the intrinsics and leave them as 16-byte records (x y z f32, R G B alpha u8) with no holes: the device buffer is the
+// payload of a binary PLY file byte for byte.  A scene is the kept points of up to four depth layers over one candidate grid — the
+// prediction coloured from the frame, the ground-plane prior, the LiDAR ground truth (uint16, divided here) and the slope-adjusted ground
+// plane in constant colours — layer after layer, each layer in row-major candidate order.  ge_depth_points is the scene of one f32 layer
+// coloured from the frame.
 //
-// cloud.hip's ordered two-launch compaction with the layer on blockIdx.y.  The layers' pointers, windows, ranges and colours travel BY VALUE
-// in the kernel-argument block (SceneLayers, 4 x 48 = 192 bytes; a workgroup reads its layer's entry at a uniform offset), as BatchTable
-// does in infer_batch.hip: no device-side table, nothing to keep alive after the call.
-//   pass 1  block (l, b): the kept candidates of span b of layer l -> ws[l * blocks + b];
+// Ordered stream compaction in two launches with the layer on blockIdx.y.  A block owns a contiguous span of 256 * ipt candidates of its
+// layer, taken 256 at a time (thread t of round j: candidate span start + 256 j + t, so a wave reads 64 neighbours).  The layers' pointers,
+// windows, ranges and colours travel BY VALUE in the kernel-argument block (SceneLayers, 4 x 48 = 192 bytes; a workgroup reads its layer's
+// entry at a uniform offset), as BatchTable does in batch_table.h: no device-side table, nothing to keep alive after the call.
+//   pass 1  block (l, b): predicate -> 64-bit ballot -> popcount per wave, the four wave counts through LDS, the kept candidates of span b
+//           of layer l -> ws[l * blocks + b];
 //   pass 2  block (l, b) folds the entries before l * blocks + b, in two sums (the layers before its own, its own layer's earlier spans),
 //           forms the predicate again and places a kept lane at  fold + kept in earlier rounds + kept in earlier waves of the round +
 //           kept in lower lanes (mbcnt of the ballot), one 16-byte store per kept point; the last block of a layer stores the layer's
-//           count, the last block of the last layer the total as well.
-// No atomics, no block waiting on another block, no grid-striding (the span grows as in cloud_geometry), so a point's place is a pure
-// function of (layer, candidate index).  The candidate grid, the keep rule and the record are cloud_points.h's: a point has the bits
-// ge_depth_points gives it.  Streaming work (at 352 x 1216 with four layers: 6 MB read, up to 27 MB written): launch-latency-sized.
+//           count, the last block of the last layer the total as well, where the caller has room for one.
+// No atomics, no block waiting on another block; the grid is capped by growing ipt, never by grid-striding, so a point's place is a pure
+// function of (layer, candidate index).  The arithmetic is numpy's float32 arithmetic: true IEEE division, no contraction.  Streaming work
+// (at 352 x 1216 with four layers: 6 MB read, up to 27 MB written): launch-latency-sized.
 #pragma clang fp contract(off)
-#include "cloud_points.h"
+#include "common.h"
+#include "../../include/gedepth_cloud.h"
 #include "../../include/gedepth_scene.h"
+
+#define GE_CLOUD_MIN_IPT 4          // candidates per thread: at least 4 (a span of 1024), more once the grid would pass GE_CLOUD_MAX_BLOCKS
+#define GE_CLOUD_MAX_BLOCKS 1024
+
+// candidate i (< the number of candidates) of the grid r = row0, row0 + step, ..., c = 0, step, ... with nc candidates per row -> its pixel
+__device__ __forceinline__ void cloud_pixel(int i, int nc, int row0, int step, int& r, int& c) {
+  const int ri = i / nc;
+  r = row0 + ri * step;
+  c = (i - ri * nc) * step;
+}
+
+// the keep rule: f32 comparisons, so NaN fails and +-inf fail finite bounds
+__device__ __forceinline__ bool cloud_in_range(float z, float dmin, float dmax) { return dmin <= z && z <= dmax; }
+
+// R | G << 8 | B << 16 of the BGR frame's pixel (top + r, left + c); white without a frame
+__device__ __forceinline__ uint32_t cloud_frame_rgb(const uint8_t* __restrict__ bgr, int Ws, int top, int left, int r, int c) {
+  if (!bgr) return 0x00ffffffu;
+  const uint8_t* p = bgr + ((long)(top + r) * Ws + (left + c)) * 3;
+  return (uint32_t)p[2] | ((uint32_t)p[1] << 8) | ((uint32_t)p[0] << 16);
+}
+
+// the 16-byte record of pixel (r, c) at depth z: x y z f32, then R G B alpha
+__device__ __forceinline__ ge_u32x4 cloud_record(int r, int c, float z, float fx, float fy, float cx, float cy, uint32_t rgb, uint32_t alpha) {
+  const float x = ((float)c - cx) / fx * z;
+  const float y = ((float)r - cy) / fy * z;
+  const ge_u32x4 rec = {__float_as_uint(x), __float_as_uint(y), __float_as_uint(z), rgb | (alpha << 24)};
+  return rec;
+}
+
+// the number of set bits of a wave's ballot below this lane
+__device__ __forceinline__ int cloud_lower_lanes(unsigned long long m) {
+  return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+}
+
+// nc, n, ipt and the blocks per map of a geometry; false for one the entry points refuse.  The grid is capped by growing ipt, never by
+// grid-striding, so a point's place is a pure function of its candidate index.
+static bool cloud_geometry(int H, int W, int row0, int step, int& nc, int& n, int& ipt, unsigned& blocks) {
+  if (H <= 0 || W <= 0 || row0 < 0 || row0 >= H || step < 1 || (long)H * W > 0x7fffffffL) return false;
+  const long nr = ((long)(H - row0) + step - 1) / step;
+  nc = (int)(((long)W + step - 1) / step);
+  n = (int)(nr * nc);                                 // <= H * W
+  const long per = 256L * GE_CLOUD_MAX_BLOCKS;
+  ipt = (int)((n + per - 1) / per);
+  if (ipt < GE_CLOUD_MIN_IPT) ipt = GE_CLOUD_MIN_IPT;
+  blocks = (unsigned)((n + 256L * ipt - 1) / (256L * ipt));
+  return true;
+}
 
 struct SceneLayers { GeSceneLayer l[GE_SCENE_MAX_LAYERS]; };
 static_assert(sizeof(GeSceneLayer) == 48 && sizeof(SceneLayers) == 192, "the by-value layer table is 4 x 48 bytes");
@@ -55,9 +108,9 @@ __global__ void __launch_bounds__(256) scene_count_k(SceneLayers t, SceneArgs a,
   if (threadIdx.x == 0) ws[blockIdx.y * gridDim.x + blockIdx.x] = wc[0] + wc[1] + wc[2] + wc[3];
 }
 
-// pass 2: the records; counts[l] from the block that owns layer l's last candidate, counts[L] from the last layer's
+// pass 2: the records; counts[l] from the block that owns layer l's last candidate, *total (unless null) from the last layer's
 __global__ void __launch_bounds__(256) scene_write_k(SceneLayers t, const uint8_t* __restrict__ bgr, SceneArgs a, const int* __restrict__ ws,
-                                                     ge_u32x4* __restrict__ records, int* __restrict__ counts) {
+                                                     ge_u32x4* __restrict__ records, int* __restrict__ counts, int* __restrict__ total) {
   __shared__ int red[2][256];                         // [0]: the layers before this one, [1]: this layer's earlier spans
   __shared__ int wc[2][4];                            // the wave counts of a round; two sets, so one barrier per round is enough
   const int t_ = threadIdx.x, lane = t_ & 63, w = t_ >> 6;
@@ -97,7 +150,7 @@ __global__ void __launch_bounds__(256) scene_write_k(SceneLayers t, const uint8_
   }
   if (blockIdx.x == gridDim.x - 1 && t_ == 0) {
     counts[blockIdx.y] = run - before;
-    if (blockIdx.y == gridDim.y - 1) counts[gridDim.y] = run;
+    if (blockIdx.y == gridDim.y - 1 && total) *total = run;
   }
 }
 
@@ -114,9 +167,9 @@ extern "C" size_t ge_scene_points_workspace(int H, int W, int row0, int step, in
   return (size_t)L * blocks * sizeof(int);
 }
 
-extern "C" int ge_scene_points(const GeSceneLayer* layers, int L, int H, int W, const uint8_t* bgr, int Hs, int Ws, int top, int left, float fx,
-                               float fy, float cx, float cy, int row0, int step, int alpha, void* records, int* counts, void* workspace,
-                               void* stream) {
+// ge_scene_points but for the total: counts[L] with `with_total`, nowhere without (ge_depth_points: `counts` is one int)
+static int scene_points(const GeSceneLayer* layers, int L, int H, int W, const uint8_t* bgr, int Hs, int Ws, int top, int left, float fx, float fy,
+                        float cx, float cy, int row0, int step, int alpha, void* records, int* counts, bool with_total, void* workspace, void* stream) {
   if (!layers || !records || !counts || !workspace || L < 1 || L > GE_SCENE_MAX_LAYERS || H <= 0 || W <= 0 || row0 < 0 || row0 >= H ||
       step < 1 || alpha < 0 || alpha > 255 || fx == 0.f || fy == 0.f)
     return GE_ERR_BAD_ARG;
@@ -142,7 +195,24 @@ extern "C" int ge_scene_points(const GeSceneLayer* layers, int L, int H, int W, 
   const dim3 grid(blocks, (unsigned)L);
   scene_count_k<<<grid, 256, 0, s>>>(t, a, (int*)workspace);
   GE_LAUNCH_CHECK();
-  scene_write_k<<<grid, 256, 0, s>>>(t, bgr, a, (const int*)workspace, (ge_u32x4*)records, counts);
+  scene_write_k<<<grid, 256, 0, s>>>(t, bgr, a, (const int*)workspace, (ge_u32x4*)records, counts, with_total ? counts + L : nullptr);
   GE_LAUNCH_CHECK();
   return GE_OK;
+}
+
+extern "C" int ge_scene_points(const GeSceneLayer* layers, int L, int H, int W, const uint8_t* bgr, int Hs, int Ws, int top, int left, float fx,
+                               float fy, float cx, float cy, int row0, int step, int alpha, void* records, int* counts, void* workspace,
+                               void* stream) {
+  return scene_points(layers, L, H, W, bgr, Hs, Ws, top, left, fx, fy, cx, cy, row0, step, alpha, records, counts, true, workspace, stream);
+}
+
+// the scene of one f32 layer: the whole map, coloured from the frame
+extern "C" size_t ge_depth_points_workspace(int H, int W, int row0, int step) { return ge_scene_points_workspace(H, W, row0, step, 1); }
+
+extern "C" int ge_depth_points(const float* depth, int H, int W, const uint8_t* bgr, int Hs, int Ws, int top, int left, float fx, float fy,
+                               float cx, float cy, float dmin, float dmax, int row0, int step, int alpha, void* records, int* count,
+                               void* workspace, void* stream) {
+  GeSceneLayer ly = {};
+  ly.data = depth; ly.kind = GE_SCENE_F32; ly.H = H; ly.W = W; ly.scale = 1.f; ly.dmin = dmin; ly.dmax = dmax; ly.from_frame = 1;
+  return scene_points(&ly, 1, H, W, bgr, Hs, Ws, top, left, fx, fy, cx, cy, row0, step, alpha, records, count, false, workspace, stream);
 }

@@ -3,7 +3,7 @@
 Per batch of n <= F frames, on the engine's stream:
 
   1. n uploads, each slot through its own pinned buffer (``PinnedUpload``), non-blocking;
-  2. ONE ``ge_infer_front_batch`` (csrc/infer_batch.hip) writes the flip views of the n frames, frame-major, into the first ``views * n``
+  2. ONE ``ge_infer_front_batch`` (csrc/infer.hip) writes the flip views of the n frames, frame-major, into the first ``views * n``
      images of the static ``(views * F, 5, 352, 1216)`` input; the frames may differ in size (the KITTI days do), each has its own crop
      offsets and ground depth.  Outside the graph: only its arguments change from batch to batch;
   3. ``model.encode_decode`` runs all ``views * F`` images as one forward and ONE ``ge_tta_merge_batch`` merges the F pairs into the
@@ -17,7 +17,6 @@ slot f holds does not reach another slot's map.
 
 ``decode_ahead`` is the host side: a pool of at most ``DECODE_WORKERS`` threads decodes the next batch's PNGs (PIL releases the GIL while
 inflating) while the device computes the current one.  DDAD, ``points`` and ``ground_maps`` stay single-frame (``DepthInferencer``)."""
-import gc
 from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
@@ -74,7 +73,7 @@ def frame_size(img):
 
 class BatchDepthInferencer(DepthInferencer):
     """The flip-TTA engine with ``frames`` = F slots (module docstring); KITTI protocol.  ``batch(imgs)`` runs n <= F frames.  Captures are
-    keyed as ``DepthInferencer``'s plus ``('batch', F)``; the capture's gc-off block and the contract that parameters are updated IN PLACE
+    keyed as ``DepthInferencer``'s plus ``('batch', F)``; the capture itself (``_run``) and the contract that parameters are updated IN PLACE
     (a replay then sees the new values: ``FusedAdamW`` updates its arena in place) are the base class's."""
 
     def __init__(self, model, frames, bf16=False, config=None):
@@ -131,27 +130,7 @@ class BatchDepthInferencer(DepthInferencer):
             devs = [up(b, self.device) for up, b in zip(self._stagings, bgrs)]
             K.infer_front_batch(devs, raws, self.static_in, tops, lefts, s['mean'], s['std'], s['views'], s['to_rgb'], s['pe_max'],
                                 s['depth_scale'])
-            key = self._key()
-            g = self.graphs.get(key) if graph else None
-            if graph and g is None and self.calls.get(key, 0) >= self.WARMUP:
-                g = torch.cuda.CUDAGraph()
-                collecting = gc.isenabled()                  # no cycle collection inside a capture: DepthInferencer._frame says why
-                gc.disable()
-                try:
-                    with torch.cuda.graph(g, stream=self.stream):
-                        self._body(metas)
-                finally:
-                    if collecting:
-                        gc.enable()
-                self.graphs[key] = g
-                self.captures += 1
-            if g is not None:
-                g.replay()
-                self.replays += 1
-            else:
-                self._body(metas)
-                if graph:
-                    self.calls[key] = self.calls.get(key, 0) + 1
+            self._run(self._key(), graph, lambda: self._body(metas))
             self.last_n = n
             if to_host:
                 host = self.static_out[:n].cpu().numpy()                           # synchronises the engine's stream
@@ -163,7 +142,7 @@ class BatchDepthInferencer(DepthInferencer):
 
     def reset(self):
         super().reset()
-        self.replays, self.last_n = 0, 0             # graph replays so far; the frame count of the last batch
+        self.last_n = 0                              # the frame count of the last batch
 
     def run(self, imgs, pes=None, calib=None, cam_height=1.65, graph=True):
         """Any number of frames, in batches of F with the next batch decoding ahead -> one host map per frame, in order."""

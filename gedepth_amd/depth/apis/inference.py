@@ -249,7 +249,8 @@ def _config_of(model):
 
 
 class DepthInferencer:
-    """The flip-TTA engine of one model and precision (module docstring).  ``captures`` counts hipGraph captures; ``reset()`` drops them.
+    """The flip-TTA engine of one model and precision (module docstring).  ``captures`` counts hipGraph captures and ``replays`` their replays; ``reset()`` drops
+    the graphs and zeroes both.
 
     A capture is keyed by the precision and the ``kernel_variant`` of every module that has one.  It bakes in the addresses of the
     parameters, buffers and static tensors: parameters must be updated IN PLACE (``load_state_dict``, ``param.data.copy_``) for a replay to
@@ -282,7 +283,7 @@ class DepthInferencer:
 
     def reset(self):
         """Drop every captured graph (and its memory pool) and the warm-up counts."""
-        self.graphs, self.calls, self.captures = {}, {}, 0
+        self.graphs, self.calls, self.captures, self.replays = {}, {}, 0, 0
         self.frame_size = None                   # DDAD: the (H, W) of the frames this engine has taken
 
     # ---- ground depth
@@ -356,6 +357,34 @@ class DepthInferencer:
             K.ground_maps(*lr, self.static_in, self.static_height, model.depth_scale, 200.0, flip=self.spec['views'] == 2,
                           out=self.static_ground, valid=self.static_ground_valid)
 
+    def _run(self, key, graph, body):
+        """``body()`` on the current (the engine's) stream: eagerly for the first ``WARMUP`` calls under ``key`` (and whenever ``graph``
+        is false), then captured once in a hipGraph and replayed from then on."""
+        g = self.graphs.get(key) if graph else None
+        if graph and g is None and self.calls.get(key, 0) >= self.WARMUP:
+            g = torch.cuda.CUDAGraph()
+            # The cycle collector must not run inside the capture (torch.cuda.graph does not collect before it by default): a dead
+            # cycle it frees there (a model and the engine it kept, with pinned buffer, events and device tensors) makes runtime
+            # calls that a capturing thread may not make, and an error raised inside a destructor ends the process.  It runs again
+            # right after the capture.
+            collecting = gc.isenabled()
+            gc.disable()
+            try:
+                with torch.cuda.graph(g, stream=self.stream):
+                    body()
+            finally:
+                if collecting:
+                    gc.enable()
+            self.graphs[key] = g
+            self.captures += 1
+        if g is not None:
+            g.replay()
+            self.replays += 1
+        else:
+            body()
+            if graph:
+                self.calls[key] = self.calls.get(key, 0) + 1
+
     def upload(self, bgr):
         """Host uint8 frame -> device, through a reused pinned buffer and a non-blocking copy on the current stream (``PinnedUpload``)."""
         return self._staging(bgr, self.device)
@@ -393,30 +422,7 @@ class DepthInferencer:
                 s = self.spec
                 self.static_ground = torch.empty(4, s['height'], s['width'], device=self.device, dtype=torch.float32)
                 self.static_ground_valid = torch.empty(s['height'], s['width'], device=self.device, dtype=torch.uint8)
-            key = self._key(ground)
-            g = self.graphs.get(key) if graph else None
-            if graph and g is None and self.calls.get(key, 0) >= self.WARMUP:
-                g = torch.cuda.CUDAGraph()
-                # The cycle collector must not run inside the capture (torch.cuda.graph does not collect before it by default): a dead
-                # cycle it frees there (a model and the engine it kept, with pinned buffer, events and device tensors) makes runtime
-                # calls that a capturing thread may not make, and an error raised inside a destructor ends the process.  It runs again
-                # right after the capture.
-                collecting = gc.isenabled()
-                gc.disable()
-                try:
-                    with torch.cuda.graph(g, stream=self.stream):
-                        self._body(metas, ground)
-                finally:
-                    if collecting:
-                        gc.enable()
-                self.graphs[key] = g
-                self.captures += 1
-            if g is not None:
-                g.replay()
-            else:
-                self._body(metas, ground)
-                if graph:
-                    self.calls[key] = self.calls.get(key, 0) + 1
+            self._run(self._key(ground), graph, lambda: self._body(metas, ground))
             # to_host: synchronises the engine's stream; a fresh host array per frame
             if ground:
                 out = dict(zip(PLANES, self.static_ground), depth=self.static_out, valid=self.static_ground_valid)

@@ -5,7 +5,7 @@ in one record buffer (``kernels.scene_points``, gedepth_amd/csrc/scene.hip; ``De
 prior, the LiDAR ground truth and the slope-adjusted ground plane, role of the reference's visualize_point-cloud_kitti_gt_pe_pred.py) — as
 the same file with one ``comment layer <name> <count>`` line per layer; ``scene_records_to_points`` brings its tensors to the host.
 
-The per-pixel work is two gfx950 launches (``ge_depth_points``, gedepth_amd/csrc/cloud.hip): an ordered stream compaction that leaves the
+The per-pixel work is two gfx950 launches (``ge_depth_points``, gedepth_amd/csrc/scene.hip): an ordered stream compaction that leaves the
 kept points in row-major order as 16-byte records — the file's payload byte for byte.  Where the reference formats about 428 000 points
 one by one with ``"%.4f"`` into an ASCII file under an indented (malformed) header, the file here is the standard binary form with the
 same properties: ``x y z`` (float), ``red green blue alpha`` (uchar).

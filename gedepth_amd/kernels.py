@@ -2108,14 +2108,14 @@ def depth_colorize(value, vmin, vmax, lut):
 # and the DDAD test protocol (include/gedepth_ddad.h)
 from .eval_kernels import depth_metric_sums, depth_metric_sums_resized, infer_front_ddad  # noqa: E402,F401
 
-# --------------------------------------------------------------------- point clouds (csrc/cloud.hip, include/gedepth_cloud.h)
+# --------------------------------------------------------------------- point clouds (csrc/scene.hip, include/gedepth_cloud.h)
 from .cloud_kernels import depth_points  # noqa: E402,F401
 
 # --------------------------------------------------------------------- the ground embedding's maps (csrc/ground.hip, include/gedepth_ground.h)
 from .ground_kernels import ground_maps  # noqa: E402,F401
 
-# --------------------------------------------------------------------- batched KITTI inference / evaluation (csrc/infer_batch.hip,
-# include/gedepth_batch.h)
+# --------------------------------------------------------------------- batched KITTI inference / evaluation (csrc/infer.hip,
+# csrc/eval.hip, include/gedepth_batch.h)
 from .batch_kernels import depth_metric_sums_batch, infer_front_batch, tta_merge_batch  # noqa: E402,F401
 
 # --------------------------------------------------------------------- scene clouds (csrc/scene.hip, include/gedepth_scene.h)

@@ -1,5 +1,6 @@
 /*
- * gedepth_batch.h — C ABI of the batched KITTI inference / evaluation entry points of libgedepth_hip.so (csrc/infer_batch.hip).
+ * gedepth_batch.h — C ABI of the batched KITTI inference / evaluation entry points of libgedepth_hip.so (csrc/infer.hip: front end and
+ * merge; csrc/eval.hip: metric sums).
  *
  * Same conventions as gedepth_hip.h (extern "C", 0 on success, GE_ERR_* of that header for argument errors, device pointers owned by
  * the caller, `stream` a hipStream_t, nothing allocates or synchronises).  Declared here and not in gedepth_hip.h: that header is the
@@ -7,8 +8,10 @@
  *
  * Each entry point is ONE launch (the metric sums: two) for n <= GE_BATCH_MAX frames, the frame index on blockIdx.y.  The frames' pointers
  * and geometry are read from the HOST array `frames` during the call and travel by value in the kernel-argument struct (8 x 32 = 256
- * bytes): there is no device-side table, no extra copy, and the array may be reused as soon as the call returns.  Per frame every entry
- * point computes the bits of its single-frame counterpart (ge_infer_front, ge_tta_merge, ge_depth_metrics).
+ * bytes): there is no device-side table, no extra copy, and the array may be reused as soon as the call returns.  The single-frame entry
+ * points (ge_infer_front, ge_tta_merge, ge_depth_metrics) launch these very kernels with n = 1 and the same grid.x, so a frame has the same
+ * bits from either; what pins the bits is independent of both: the training pipeline's chain ge_aug_load -> ge_aug_color_normalize ->
+ * ge_aug_window for the front end, the expression (a + mirror(b)) / 2 for the merge, float64 sums for the metrics (tests/).
  */
 #ifndef GEDEPTH_BATCH_H
 #define GEDEPTH_BATCH_H
@@ -54,8 +57,8 @@ int ge_tta_merge_batch(const float* src, float* dst, int n, int H, int W, void* 
 /*
  * ge_depth_metrics_batch: ge_depth_metrics (gedepth_eval.h) for n images.  pred (n, Hc, Wc) f32; frames[f].image the (H, W) uint16 ground
  * truth of image f, read in the window at (top, left); the rectangle and the three depth parameters are shared.  sums (n, 10) f64, row f
- * the ten sums of image f with the bits ge_depth_metrics gives for it: the first pass runs ge_depth_metrics' block partition (it depends on
- * (Hc, Wc) only) once per image on grid.y, the second folds each image's partials in index order on grid.x = n; no atomics.  Whether an
+ * the ten sums of image f with the bits ge_depth_metrics gives for it (the same kernels): the first pass runs one block partition (it depends
+ * on (Hc, Wc) only) once per image on grid.y, the second folds each image's partials in index order on grid.x = n; no atomics.  Whether an
  * image's ground truth is read with 8-byte loads (W % 4 == 0, left % 4 == 0, base 8-byte aligned) is decided per image.
  *   partials  ge_depth_metrics_batch_workspace(n, Hc, Wc) bytes, 8-byte aligned.
  * GE_ERR_BAD_ARG: a null pointer (pred, frames, an image, partials, sums), n outside 1 .. GE_BATCH_MAX, a non-positive size, a window

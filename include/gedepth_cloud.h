@@ -1,5 +1,6 @@
 /*
- * gedepth_cloud.h — C ABI of the point-cloud entry points of libgedepth_hip.so (csrc/cloud.hip).
+ * gedepth_cloud.h — C ABI of the point-cloud entry points of libgedepth_hip.so (csrc/scene.hip, where
+ * ge_depth_points is the scene cloud of gedepth_scene.h with one f32 layer coloured from the frame).
  *
  * Same conventions as gedepth_hip.h (extern "C", 0 on success, GE_ERR_* of that header for argument errors, device pointers owned by
  * the caller, `stream` a hipStream_t, nothing allocates or synchronises).  Like gedepth_eval.h and gedepth_ddad.h, this header stands

@@ -5,7 +5,7 @@
  *
  * Same conventions as gedepth_hip.h (extern "C", 0 on success, GE_ERR_* of that header for argument errors, device pointers owned by
  * the caller, `stream` a hipStream_t, nothing allocates or synchronises).  Like gedepth_cloud.h, whose record and keep rule this header
- * shares (csrc/cloud_points.h), it stands beside the versioned training / inference ABI of gedepth_hip.h, which does not change with it.
+ * shares (one kernel pair runs both), it stands beside the versioned training / inference ABI of gedepth_hip.h, which does not change with it.
  */
 #ifndef GEDEPTH_SCENE_H
 #define GEDEPTH_SCENE_H

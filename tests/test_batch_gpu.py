@@ -1,9 +1,13 @@
-"""Batched KITTI inference and evaluation on the MI355X (csrc/infer_batch.hip, gedepth_amd/batch_kernels.py, depth/apis/batch_inference.py):
-the three batched entry points bit for bit against their single-frame counterparts under red zones and poison (tests/memguard.py), the
+"""Batched KITTI inference and evaluation on the MI355X (csrc/infer.hip, csrc/eval.hip, gedepth_amd/batch_kernels.py,
+depth/apis/batch_inference.py): the three batched entry points bit for bit against their single-frame counterparts under red zones and
+poison (tests/memguard.py) — the same kernels at grid.y = n and at grid.y = 1, which checks the per-frame offsets — and against references
+that share no code with them (the training pipeline's chain of aug.hip for the front end, the torch expression for the merge, float64
+sums within the bounds of tests/test_eval_device_gpu.py for the metrics), the
 batched engine against ``aug_test`` and against its own graph replay on a tree with two frame sizes, the batched device evaluation loop
 against the host loop, and validation on the device while training.
 
-Bounds.  Kernels: ``torch.equal`` (the metric rows as int64 views, so NaN rows compare).  Engine against the host route: the project's
+Bounds.  Kernels: ``torch.equal`` (the metric rows as int64 views, so NaN rows compare); the metric rows against float64:
+``test_eval_device_gpu._assert_sums``.  Engine against the host route: the project's
 bound for the engine, max <= 2e-4 and mean <= 1e-5 relative per pixel (``ENGINE_EPS`` of tests/test_eval_device_gpu.py).  Graph replay
 against the eager run: 1e-6 of the map's largest value (``test_inference_gpu.py::test_graph_replay``).  The loops: the assertions of
 ``test_eval_device_gpu.py::test_device_eval_loop_vs_host_loop`` — a count moves by at most the pixels whose ratio lies within 2 * ENGINE_EPS
@@ -79,6 +83,11 @@ def test_front_batch_equals_the_single_frame_kernel(monkeypatch, case, views, po
     assert bool(memguard.poisoned(out[views * n:], poison).all()), 'the slot after the last frame must stay untouched'
     if views == 2:
         assert torch.equal(out[1], out[0].flip(-1))
+    if case == 'small-3':                                             # the independent reference: the training pipeline's chain (aug.hip)
+        for f, (bgr, pe, top, left) in enumerate(frames):
+            chain = TI._chain(torch.from_numpy(bgr).cuda(), torch.from_numpy(pe).cuda(), top, left, Hc, Wc)      # pe_max, depth_scale: 200, as above
+            for v in range(views):
+                assert torch.equal(out[views * f + v], chain[v]), (case, views, f, v)
 
 
 @pytest.mark.parametrize('poison', memguard.POISONS, ids=lambda p: f'{p:02x}')
@@ -114,6 +123,16 @@ def _metric_frames(case):
             (odd,) + TE._inputs(odd, 34)]
 
 
+def _metric_rect(case, Hc, Wc):
+    return (1, Hc - 1, 3, Wc - 2) if case == 'multi-block' else (0, Hc, 0, Wc)
+
+
+@functools.lru_cache(maxsize=None)
+def _metric_refs(case):
+    """Per image of ``_metric_frames(case)`` the ten float64 sums over the pixels that count: the reference of test_eval_device_gpu.py."""
+    return [TE.R.sums_f64(*TE._host((geom, raw, pred, _metric_rect(case, *geom[4:])))) for geom, raw, pred in _metric_frames(case)]
+
+
 @pytest.mark.parametrize('poison', memguard.POISONS, ids=lambda p: f'{p:02x}')
 @pytest.mark.parametrize('case', ['one-block', 'multi-block'])
 def test_metrics_batch_rows_carry_the_bits_of_the_single_image_kernel(monkeypatch, case, poison):
@@ -123,7 +142,7 @@ def test_metrics_batch_rows_carry_the_bits_of_the_single_image_kernel(monkeypatc
     n = len(frames)
     Hc, Wc = frames[0][0][4:]
     assert all(f[0][4:] == (Hc, Wc) for f in frames) and Wc % 4 == 0
-    rect = (1, Hc - 1, 3, Wc - 2) if case == 'multi-block' else (0, Hc, 0, Wc)
+    rect = _metric_rect(case, Hc, Wc)
     pred = torch.from_numpy(np.stack([f[2] for f in frames])).cuda()
     ref = torch.zeros(n, 10, device='cuda', dtype=torch.float64)
     for f, (geom, raw, _) in enumerate(frames):
@@ -144,6 +163,8 @@ def test_metrics_batch_rows_carry_the_bits_of_the_single_image_kernel(monkeypatc
     assert torch.equal(got[:n].view(torch.int64), ref.cpu().view(torch.int64)), (got[:n], ref)
     assert bool((got[n] == -7.0).all()), 'the row after the last image must keep its value'
     assert torch.equal(got[n + 1].view(torch.int64), ref[0].cpu().view(torch.int64))
+    for f, f64 in enumerate(_metric_refs(case)):                      # the independent reference: float64 sums, non-finite rows included
+        TE._assert_sums(got[f].numpy(), f64, f'{case} image {f}')
     counts = got[:n, 0].tolist()
     assert counts[0] > 0 and counts[1] > 0 and counts[2] == 0 and not got[2].any()           # the all-zero ground truth counts nothing
     if case == 'one-block':

@@ -1,4 +1,5 @@
-"""Point clouds on the MI355X: ``ge_depth_points`` (csrc/cloud.hip) bit for bit against the numpy float32 restatement (tests/cloud_ref.py)
+"""Point clouds on the MI355X: ``ge_depth_points`` (csrc/scene.hip: the scene cloud of one frame-coloured f32 layer, with no
+total stored behind its one-int count) bit for bit against the numpy float32 restatement (tests/cloud_ref.py)
 under red zones and both poison bytes (tests/memguard.py), ``DepthInferencer.points`` / ``inference_point_cloud`` on the toy KITTI tree,
 and tools/test.py's ``--ply-dir`` end to end.
 

@@ -104,30 +104,40 @@ def test_front_end_matches_reference_fixture(toy):
         assert np.allclose(img.astype(np.float64).sum((1, 2)), g[f'{tag}_sum'], rtol=1e-12, atol=1e-9), tag
 
 
-def test_front_end_equals_training_pipeline_chain():
-    """ge_infer_front == ge_aug_load -> ge_aug_color_normalize(color_on=0) -> ge_aug_window(flip), bit for bit, on every KITTI size."""
+def _chain(bgr, pe, top, left, Hc, Wc, pe_max=200.0, depth_scale=200.0):
+    """The training pipeline's chain for the (Hc, Wc) window at (top, left) of one frame (device tensors ``bgr`` uint8 HWC, ``pe`` f32):
+    ge_aug_load -> ge_aug_color_normalize(color_on=0) -> ge_aug_window(flip) -> [view 0, view 1], each (5, Hc, Wc).  ``pe_max`` /
+    ``depth_scale``: those of the front-end call under test."""
     from gedepth_amd import hip
     lib = hip.lib()
     mean = (ctypes.c_double * 3)(*[float(np.float32(v)) for v in MEAN])
     std = (ctypes.c_double * 3)(*[float(np.float32(v)) for v in STD])
     ones = (ctypes.c_double * 3)(1.0, 1.0, 1.0)
     vp = lambda a: ctypes.cast(a, ctypes.c_void_p)
+    H, W = bgr.shape[:2]
+    raw = torch.empty(5, Hc, Wc, device='cuda')
+    norm = torch.empty_like(raw)
+    hip.check(lib.ge_aug_load(hip.ptr(bgr), hip.ptr(pe), hip.ptr(raw), H, W, top, left, Hc, Wc, pe_max, hip.stream()), 'load')
+    hip.check(lib.ge_aug_color_normalize(hip.ptr(raw), hip.ptr(norm), Hc, Wc, 0, 1.0, 1.0, vp(ones), vp(mean), vp(std), depth_scale, 1,
+                                         hip.stream()), 'normalize')
+    views = []
+    for flip in (0, 1):
+        ref = torch.empty_like(raw)
+        hip.check(lib.ge_aug_window(hip.ptr(norm), hip.ptr(ref), 5, Hc, Wc, Hc, Wc, 0, 0, flip, 0.0, hip.stream()), 'window')
+        views.append(ref)
+    return views
+
+
+def test_front_end_equals_training_pipeline_chain():
+    """ge_infer_front == ge_aug_load -> ge_aug_color_normalize(color_on=0) -> ge_aug_window(flip), bit for bit, on every KITTI size."""
     for i, (H, W) in enumerate(KITTI_SIZES):
         rng = np.random.default_rng(10 + i)
         bgr = torch.from_numpy(_frame(20 + i, H, W)).cuda()
         pe_np = _plane(H, W) * rng.uniform(0.5, 2.0, (H, W)).astype(np.float32)
         pe_np[rng.random((H, W)) < 0.01] = 250.0                      # above the 200 m filter
         pe = torch.from_numpy(pe_np).cuda()
-        top, left = H - 352, int((W - 1216) / 2)
         got = _front(bgr.cpu().numpy(), pe_np)
-        raw = torch.empty(5, 352, 1216, device='cuda')
-        norm = torch.empty_like(raw)
-        hip.check(lib.ge_aug_load(hip.ptr(bgr), hip.ptr(pe), hip.ptr(raw), H, W, top, left, 352, 1216, 200.0, hip.stream()), 'load')
-        hip.check(lib.ge_aug_color_normalize(hip.ptr(raw), hip.ptr(norm), 352, 1216, 0, 1.0, 1.0, vp(ones), vp(mean), vp(std), 200.0, 1,
-                                             hip.stream()), 'normalize')
-        for flip in (0, 1):
-            ref = torch.empty_like(raw)
-            hip.check(lib.ge_aug_window(hip.ptr(norm), hip.ptr(ref), 5, 352, 1216, 352, 1216, 0, 0, flip, 0.0, hip.stream()), 'window')
+        for flip, ref in enumerate(_chain(bgr, pe, H - 352, int((W - 1216) / 2), 352, 1216)):
             assert torch.equal(got[flip], ref), ((H, W), flip)
         assert torch.equal(got[1], got[0].flip(-1))
 

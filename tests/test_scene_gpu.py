@@ -104,7 +104,8 @@ def test_subsets_of_the_layers(monkeypatch, names):
 
 @pytest.mark.parametrize('colour', ['bgr', 'white'])
 def test_a_lone_frame_coloured_layer_is_depth_points(monkeypatch, colour):
-    """A single f32 layer with the frame's colour and a zero window: the bytes and the count of ``kernels.depth_points`` on the same inputs."""
+    """A single f32 layer with the frame's colour and a zero window: the bytes and the count of ``kernels.depth_points`` on the same inputs
+    (the same kernels, entered through ``ge_depth_points``, which stores no total; the numpy restatement is the independent reference)."""
     from gedepth_amd import kernels
     depth = np.ascontiguousarray(S.small_layers(('prediction',))[0].window(S.H, S.W))
     bgr = S.FRAME if colour == 'bgr' else None
