@@ -285,7 +285,6 @@ int ge_window_attn_fwd_mfma(const void* qkv, const float* qkv_bias, const float*
                             float scale, bool fp8, hipStream_t s);
 int ge_window_attn_bwd_mfma(const void* qkv, const float* qkv_bias, const float* bias_table, const void* d_out, void* d_qkv,
                             float* workspace, const WinGeom& g, float scale, int wg_per_head, hipStream_t s);
-extern const int ge_window_attn_mfma_available;
 
 extern "C" size_t ge_window_attn_bwd_workspace(int B, int H, int W, int nH) {
   WinGeom g;
@@ -301,10 +300,10 @@ extern "C" int ge_window_attn_fwd(const void* qkv, const float* qkv_bias, const 
   if (e) return e;
   const long items = (long)B * g.nWh * g.nWw * nH;
   if (items == 0) return GE_OK;
-  if (variant == 0) variant = (dtype == GE_BF16 && (ge_window_attn_mfma_available & 1)) ? 2 : 1;
+  if (variant == 0) variant = dtype == GE_BF16 ? 2 : 1;
   hipStream_t s = ge_stream(stream);
   if (variant == 2 || variant == 3) {                          // 3: fp8 (e4m3) MFMA contractions, BASELINE.json configs[4]
-    if (dtype != GE_BF16 || !(ge_window_attn_mfma_available & 1)) return GE_ERR_UNSUPPORTED;
+    if (dtype != GE_BF16) return GE_ERR_UNSUPPORTED;
     return ge_window_attn_fwd_mfma(qkv, qkv_bias, bias_table, out, g, scale, variant == 3, s);
   }
   if (variant != 1) return GE_ERR_BAD_ARG;
@@ -332,9 +331,9 @@ extern "C" int ge_window_attn_bwd(const void* qkv, const float* qkv_bias, const 
     return (int)he;
   }
   const int wph = bwd_wg_per_head(g);
-  if (variant == 0) variant = (dtype == GE_BF16 && (ge_window_attn_mfma_available & 2)) ? 2 : 1;
+  if (variant == 0) variant = dtype == GE_BF16 ? 2 : 1;
   if (variant == 2 || variant == 3) {                          // the fp8 forward differentiates through the bf16 MFMA backward
-    if (dtype != GE_BF16 || !(ge_window_attn_mfma_available & 2)) return GE_ERR_UNSUPPORTED;
+    if (dtype != GE_BF16) return GE_ERR_UNSUPPORTED;
     e = ge_window_attn_bwd_mfma(qkv, qkv_bias, bias_table, d_out, d_qkv, (float*)workspace, g, scale, wph, s);
     if (e) return e;
   } else if (variant == 1) {

@@ -1,6 +1,6 @@
 // Swin shifted-window attention core for gfx950 — bf16 MFMA tile variant (the performance path).
 //
-// One wave64 per (batch, window, head).  The 49 x 32 q / k / v rows of the 7x7 window are staged in LDS
+// One wave64 per (batch, window, head) forward, two (one per 32-query tile) backward.  The 49 x 32 q / k / v rows of the 7x7 window are staged in LDS
 // (16-byte pieces; pad tokens take the qkv bias; rows 49..63 are zero) and every contraction runs on
 // v_mfma_f32_32x32x16_bf16 with fp32 accumulation:
 //
@@ -18,7 +18,6 @@
 //
 // HBM traffic is the algorithmic minimum: q,k,v (+dO) read once, out (dqkv) written once; the op is HBM-bound
 // (24.5 FLOP/B at bf16, ridge 312 FLOP/B) and MFMA only has to keep the arithmetic off the critical path.
-#include <stdlib.h>
 #include "common.h"
 #include "window_attn.h"
 
@@ -97,33 +96,8 @@ __device__ __forceinline__ ge_bf16x8 row8(const bf16_t* tile, int row, int col0)
   return __builtin_bit_cast(ge_bf16x8, *(const uint4*)(tile + row * RLD + col0));
 }
 
-// Stage a 49 x 32 bf16 operand row-major into LDS (rows >= 49 zero).  pad rows take `padval` (fp32 -> bf16).
-__device__ __forceinline__ void stage_rm(const bf16_t* __restrict__ base, long row_stride, int col0, const int* tok,
-                                         const float* __restrict__ padval, bf16_t* dst, int lane) {
-  uint4 v[4];
-#pragma unroll
-  for (int it = 0; it < 4; ++it) {
-    const int piece = lane + it * 64;           // 64 rows x 4 pieces of 8 bf16
-    const int t = piece >> 2, part = (piece & 3) * 8;
-    v[it] = make_uint4(0, 0, 0, 0);
-    if (t < WT) {
-      const int src = tok[t];
-      if (src >= 0) {
-        v[it] = *(const uint4*)(base + (long)src * row_stride + col0 + part);
-      } else if (padval) {
-        const float* pv = padval + col0 + part;
-        v[it] = make_uint4(ge_pack_bf16x2(pv[0], pv[1]), ge_pack_bf16x2(pv[2], pv[3]), ge_pack_bf16x2(pv[4], pv[5]), ge_pack_bf16x2(pv[6], pv[7]));
-      }
-    }
-  }
-#pragma unroll
-  for (int it = 0; it < 4; ++it) {
-    const int piece = lane + it * 64;
-    const int t = piece >> 2, part = (piece & 3) * 8;
-    *(uint4*)(dst + t * RLD + part) = v[it];
-  }
-}
-// The two halves of stage_rm, for kernels that fetch the NEXT window's operands into registers while the current one is computed.
+// Gather a 49 x 32 bf16 operand into registers: 64 rows x 4 pieces of 8 bf16, four pieces per lane (rows >= 49 zero).  Pad rows take
+// `padval` (fp32 -> bf16), or zero when it is null.
 __device__ __forceinline__ void load_rm(const bf16_t* __restrict__ base, long row_stride, int col0, const int* tok,
                                         const float* __restrict__ padval, int lane, uint4 v[4]) {
 #pragma unroll
@@ -142,6 +116,7 @@ __device__ __forceinline__ void load_rm(const bf16_t* __restrict__ base, long ro
     }
   }
 }
+// ... and park it row-major in LDS: dst[row][RLD]
 __device__ __forceinline__ void store_rm(bf16_t* dst, int lane, const uint4 v[4]) {
 #pragma unroll
   for (int it = 0; it < 4; ++it) {
@@ -150,25 +125,18 @@ __device__ __forceinline__ void store_rm(bf16_t* dst, int lane, const uint4 v[4]
     *(uint4*)(dst + t * RLD + part) = v[it];
   }
 }
+__device__ __forceinline__ void stage_rm(const bf16_t* __restrict__ base, long row_stride, int col0, const int* tok,
+                                         const float* __restrict__ padval, bf16_t* dst, int lane) {
+  uint4 v[4];
+  load_rm(base, row_stride, col0, tok, padval, lane, v);
+  store_rm(dst, lane, v);
+}
 // Stage V transposed: vt[d][key], keys >= 49 zero.
 __device__ __forceinline__ void stage_vt(const bf16_t* __restrict__ base, long row_stride, int col0, const int* tok,
                                          const float* __restrict__ padval, bf16_t* vt, int lane) {
   uint4 v[4];
-#pragma unroll
-  for (int it = 0; it < 4; ++it) {
-    const int piece = lane + it * 64;
-    const int t = piece >> 2, part = (piece & 3) * 8;
-    v[it] = make_uint4(0, 0, 0, 0);
-    if (t < WT) {
-      const int src = tok[t];
-      if (src >= 0) {
-        v[it] = *(const uint4*)(base + (long)src * row_stride + col0 + part);
-      } else {
-        const float* pv = padval + col0 + part;
-        v[it] = make_uint4(ge_pack_bf16x2(pv[0], pv[1]), ge_pack_bf16x2(pv[2], pv[3]), ge_pack_bf16x2(pv[4], pv[5]), ge_pack_bf16x2(pv[6], pv[7]));
-      }
-    }
-  }
+  __builtin_assume(padval != nullptr);          // V always has a pad value (the qkv bias)
+  load_rm(base, row_stride, col0, tok, padval, lane, v);
 #pragma unroll
   for (int it = 0; it < 4; ++it) {
     const int piece = lane + it * 64;
@@ -370,181 +338,12 @@ __global__ void __launch_bounds__(64) window_attn_fwd_mfma_k(const bf16_t* __res
 }
 
 // =========================================================================================== backward
-struct WinSmemMfmaBwd {
-  bf16_t k[64 * RLD];
-  bf16_t q[64 * RLD];
-  bf16_t v[64 * RLD];       // re-used as the [key][32 queries] transpose buffer after dP is formed
-  bf16_t go[64 * RLD];
-  float bias[NBIAS + 7];
-  float dbias[NBIAS + 7];
-  float dpad[2 * HD];
-  WinMeta m;
-};
-#define WS_PER_WG_MFMA (NBIAS + 2 * HD)
+#define WS_PER_WG_MFMA (NBIAS + 2 * HD)   // workspace row of a workgroup: [169 dbias][64 dpad], as WS_PER_WG in window_attn.hip
 
-__global__ void __launch_bounds__(64) window_attn_bwd_mfma_k(const bf16_t* __restrict__ qkv, const float* __restrict__ qkv_bias,
-                                                             const float* __restrict__ bias_table, const bf16_t* __restrict__ gout,
-                                                             bf16_t* __restrict__ dqkv, float* __restrict__ workspace,
-                                                             WinGeom g, float scale, int wg_per_head) {
-  __shared__ __attribute__((aligned(16))) WinSmemMfmaBwd sm;
-  const int lane = threadIdx.x, c = lane & 31, hi = lane >> 5;
-  const int head = blockIdx.x % g.nH;
-  const int slot = blockIdx.x / g.nH;
-  const int nW = g.nWh * g.nWw;
-  const int n_bw = g.B * nW;
-  const long L = (long)g.H * g.W;
-  for (int i = lane; i < NBIAS; i += GE_WAVE) { sm.bias[i] = bias_table[i * g.nH + head]; sm.dbias[i] = 0.f; }
-  sm.dpad[lane] = 0.f;
-  __syncthreads();
-  // bias-table gradient: dS[q][key] lands on table entry (i_q - i_k + 6) * 13 + (j_q - j_k + 6), which depends on the
-  // (query, key) position inside the window only — the same for every window this persistent workgroup visits.  So the lane
-  // that owns accumulator element (kt, qt, r) sums its dS over all windows in REGISTERS and scatters once at the end
-  // (64 LDS float atomics per workgroup instead of per window: ds_add_f32 costs ~170 cycles per wave-instruction, which made
-  // this kernel 5x slower than the forward one).
-  ge_f32x16 dB[2][2];
-#pragma unroll
-  for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-    for (int qt = 0; qt < 2; ++qt)
-#pragma unroll
-      for (int i = 0; i < 16; ++i) dB[kt][qt][i] = 0.f;
-
-  for (int bw = slot; bw < n_bw; bw += wg_per_head) {
-    const int b = bw / nW, win = bw - b * nW;
-    const int wy = win / g.nWw, wx = win - wy * g.nWw;
-    fill_meta(g, wy, wx, lane, sm.m);
-    __syncthreads();
-    const bf16_t* base = qkv + (long)b * L * 3 * g.C;
-    stage_rm(base, 3 * g.C, head * HD, sm.m.tok, qkv_bias, sm.q, lane);
-    stage_rm(base, 3 * g.C, g.C + head * HD, sm.m.tok, qkv_bias, sm.k, lane);
-    stage_rm(base, 3 * g.C, 2 * g.C + head * HD, sm.m.tok, qkv_bias, sm.v, lane);
-    stage_rm(gout + (long)b * L * g.C, g.C, head * HD, sm.m.tok, nullptr, sm.go, lane);
-    __syncthreads();
-
-    ge_f32x16 P[2][2], dS[2][2];
-    st_tiles(sm.k, sm.q, c, hi, P);
-    const bool use_mask = g.shift > 0 && (wy == g.nWh - 1 || wx == g.nWw - 1);
-    softmax_cols(P, sm.bias, sm.m.meta, c, hi, scale, use_mask);
-    st_tiles(sm.v, sm.go, c, hi, dS);                       // dP^T = V dO^T
-    __syncthreads();                                        // all lanes done reading sm.v -> transpose buffer
-
-    // dS = P (dP - delta), delta = sum_key P dP per query;  bias-table gradient
-#pragma unroll
-    for (int qt = 0; qt < 2; ++qt) {
-      float delta = 0.f;
-#pragma unroll
-      for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) delta += P[kt][qt][r] * dS[kt][qt][r];
-      delta += __shfl_xor(delta, 32, 64);
-#pragma unroll
-      for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const float ds = P[kt][qt][r] * (dS[kt][qt][r] - delta);     // exactly 0 for rows / columns >= 49 (P == 0 there)
-          dS[kt][qt][r] = ds;
-          dB[kt][qt][r] += ds;
-        }
-    }
-
-    // dQ^T[d][query] = scale * sum_key K^T[d][key] dS^T[key][query]
-    {
-      ge_f32x16 dq[2];
-#pragma unroll
-      for (int qt = 0; qt < 2; ++qt)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) dq[qt][i] = 0.f;
-#pragma unroll
-      for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-        for (int s = 0; s < 2; ++s) {
-          const ge_bf16x8 a = col8(sm.k, kt * 32 + 16 * s + 4 * hi, c);
-          dq[0] = mfma_bf16(a, pack8(dS[kt][0], 8 * s), dq[0]);
-          dq[1] = mfma_bf16(a, pack8(dS[kt][1], 8 * s), dq[1]);
-        }
-#pragma unroll
-      for (int qt = 0; qt < 2; ++qt) {
-        const int q = qt * 32 + c;
-        if (q < WT) {
-          const int dst = sm.m.tok[q];
-          if (dst >= 0) store_cols(dq[qt], scale, dqkv + ((long)b * L + dst) * 3 * g.C + head * HD, hi);
-        }
-      }
-    }
-
-    // dV^T[d][key] = sum_q dO^T[d][q] P[q][key];  dK^T[d][key] = scale * sum_q Q^T[d][q] dS[q][key]
-    ge_f32x16 dv[2], dk[2];
-#pragma unroll
-    for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-      for (int i = 0; i < 16; ++i) { dv[kt][i] = 0.f; dk[kt][i] = 0.f; }
-    bf16_t* tb = sm.v;                                       // [64 keys][RLD], columns 0..31 = queries of tile qt
-#pragma unroll
-    for (int qt = 0; qt < 2; ++qt) {
-#pragma unroll
-      for (int pass = 0; pass < 2; ++pass) {                 // pass 0: P -> dV ; pass 1: dS -> dK
-#pragma unroll
-        for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-          for (int r = 0; r < 16; ++r)
-            tb[(kt * 32 + crow(r, hi)) * RLD + c] = f2bf_hw(pass == 0 ? P[kt][qt][r] : dS[kt][qt][r]);
-        __syncthreads();
-        const bf16_t* lhs = pass == 0 ? sm.go : sm.q;
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-          const ge_bf16x8 a = col8_lin(lhs, qt * 32 + ks * 16 + hi * 8, c);    // X^T[d = c][8 consecutive queries]
-          const ge_bf16x8 b0 = row8(tb, c, ks * 16 + hi * 8), b1 = row8(tb, 32 + c, ks * 16 + hi * 8);
-          if (pass == 0) { dv[0] = mfma_bf16(a, b0, dv[0]); dv[1] = mfma_bf16(a, b1, dv[1]); }
-          else { dk[0] = mfma_bf16(a, b0, dk[0]); dk[1] = mfma_bf16(a, b1, dk[1]); }
-        }
-        __syncthreads();
-      }
-    }
-#pragma unroll
-    for (int kt = 0; kt < 2; ++kt) {
-      const int key = kt * 32 + c;
-      if (key < WT) {
-        const int dst = sm.m.tok[key];
-        if (dst >= 0) {
-          bf16_t* rp = dqkv + ((long)b * L + dst) * 3 * g.C + head * HD;
-          store_cols(dk[kt], scale, rp + g.C, hi);
-          store_cols(dv[kt], 1.f, rp + 2 * g.C, hi);
-        } else {
-#pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            atomicAdd(&sm.dpad[crow(r, hi)], dk[kt][r] * scale);
-            atomicAdd(&sm.dpad[HD + crow(r, hi)], dv[kt][r]);
-          }
-        }
-      }
-    }
-    __syncthreads();
-  }
-#pragma unroll
-  for (int qt = 0; qt < 2; ++qt) {
-    const int q = qt * 32 + c;
-    const int qb = (q / WS) * 13 + (q % WS) + 6 * 13 + 6;
-#pragma unroll
-    for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int key = kt * 32 + crow(r, hi);
-        if (q < WT && key < WT) atomicAdd(&sm.dbias[qb - ((key / WS) * 13 + key % WS)], dB[kt][qt][r]);
-      }
-  }
-  __syncthreads();
-  float* wsp = workspace + (long)blockIdx.x * WS_PER_WG_MFMA;
-  for (int i = lane; i < NBIAS; i += GE_WAVE) wsp[i] = sm.dbias[i];
-  wsp[NBIAS + lane] = sm.dpad[lane];
-}
-
-// ------------------------------------------------------------------------------------------- backward, two waves per (window, head)
-// The single-wave kernel above holds P, dS, dB, dQ, dK, dV for both 32-query tiles at once: 256 VGPR + 93 AGPR = one wave per SIMD, four
-// (window, head) items in flight per CU, each with 25 - 30 us of exposed latency (staging by one wave, eight barriers, four LDS transposes).
-// Here wave w of a 128-thread workgroup owns QUERY TILE w: scores, soft-max, dP, dS, the bias-table gradient and dQ of its 32 queries are
-// wave-local (half the registers: two waves per SIMD), the four operand tiles are staged by both waves, and only the key-side sums
-// dK / dV = sum over ALL queries meet: each wave sends its partial for the other wave's key tile through LDS (8 KB each way, in the space
-// of the dead operand tiles) and finishes its own key tile.
+// Two waves per (window, head): wave w of a 128-thread workgroup owns QUERY TILE w.  Scores, soft-max, dP, dS, the bias-table gradient and dQ of
+// its 32 queries are wave-local, so P, dS, dB, dQ, dK, dV of one tile fit three waves per SIMD; the four operand tiles are staged by both waves
+// (wave 0: q, k; wave 1: v, dO), and the key-side sums dK / dV over ALL queries are finished per KEY TILE w from the P / dS tiles that both waves
+// park, transposed, in the dead operand tiles.
 __device__ __forceinline__ void st_tiles_q(const bf16_t* A_rows, const bf16_t* B_rows, int qt, int c, int hi, ge_f32x16 acc[2]) {
 #pragma unroll
   for (int kt = 0; kt < 2; ++kt)
@@ -599,24 +398,25 @@ __device__ __forceinline__ void softmax_q(ge_f32x16 acc[2], const float* bias, c
 }
 
 struct WinSmemMfmaBwd2 {
-  bf16_t k[64 * RLD];       // k | q | v | go are contiguous: 20 KB, re-used for the transposes and the dK / dV exchange
+  bf16_t k[64 * RLD];       // k | q | v | go: 20 KB; v (wave 0) and k (wave 1) are re-used for the transposes of P and dS
   bf16_t q[64 * RLD];
   bf16_t v[64 * RLD];
   bf16_t go[64 * RLD];
   float bias[NBIAS + 7];
   float dbias[NBIAS + 7];
   float dpad[2][2 * HD];    // per wave
-  WinMeta m[2];             // token tables of the current and of the next window (double buffer)
+  // Token tables, double-buffered: window i of this workgroup uses m[i & 1].  Wave 0 alone writes them: m[0] before the barrier in front of the
+  // loop, and inside iteration i the table of window i + 1 into m[(i + 1) & 1] between the FIRST and the SECOND barrier of that iteration.  Both
+  // waves read m[i & 1] from the top of iteration i (the operand gather) to its very end, AFTER its last barrier (the dK / dV rows).  So every
+  // reader of the buffer's previous contents (iteration i - 1, through its end) has arrived at the first barrier of iteration i before the writer
+  // passes it, and the next readers (the top of iteration i + 1) come after the later barriers of iteration i: no barrier is spent on the tables.
+  WinMeta m[2];
 };
 #ifndef WA_BWD_WAVES
-#define WA_BWD_WAVES 3                      // waves per SIMD the register allocation targets: 3 = 168 VGPRs (13 spilled registers), six workgroups per CU.
-                                            // Measured (tools/ubench/winattn_time.py, same session, us per launch at the four Swin stages): 2 waves + pipeline 151 / 117 / 92 / 57,
-                                            // 3 waves without it 151 / 110 / 70 / 57, and with the persistent grid cut to the six resident workgroups per CU
+#define WA_BWD_WAVES 3                      // waves per SIMD the register allocation targets: 3 = 168 VGPRs (8 spilled registers), six workgroups per CU.
+                                            // Measured (tools/ubench/winattn_time.py, same session, us per launch at the four Swin stages): 2 waves with a register prefetch of the
+                                            // next window's operands (since removed: at 3 waves it spilled 276 registers) 151 / 117 / 92 / 57, 3 waves without it 151 / 110 / 70 / 57, and with the persistent grid cut to the six resident workgroups per CU
                                             // (window_attn.hip: bwd_wg_per_head) 130 / 98 / 80 / 60 on a slower box where the 8-per-CU grid gave 153 / 120 / 79 / 61
-#endif
-#ifndef WA_BWD_PREFETCH
-#define WA_BWD_PREFETCH 0                   // 1: the next window's operands are fetched into 32 registers under this window's arithmetic (with 3 waves per
-                                            // SIMD that spills 276 registers; with 2 it gains 7 % on stage 0 — the third wave gains 25 % on stage 2)
 #endif
 __global__ void __launch_bounds__(128, WA_BWD_WAVES) window_attn_bwd_mfma2_k(const bf16_t* __restrict__ qkv, const float* __restrict__ qkv_bias,
                                                                   const float* __restrict__ bias_table, const bf16_t* __restrict__ gout,
@@ -632,28 +432,15 @@ __global__ void __launch_bounds__(128, WA_BWD_WAVES) window_attn_bwd_mfma2_k(con
   for (int i = tid; i < NBIAS; i += 128) { sm.bias[i] = bias_table[i * g.nH + head]; sm.dbias[i] = 0.f; }
   if (tid < 2 * HD) { sm.dpad[0][tid] = 0.f; sm.dpad[1][tid] = 0.f; }
   __syncthreads();
-  ge_f32x16 dB[2];                                              // bias-table gradient of this wave's query tile, summed over the windows
+  // bias-table gradient of this wave's query tile: dS[q][key] lands on table entry (i_q - i_k + 6) * 13 + (j_q - j_k + 6), which depends on the
+  // (query, key) position inside the window only, so the lane that owns an accumulator element sums its dS over all windows of this persistent
+  // workgroup in REGISTERS and scatters once at the end (ds_add_f32 costs ~170 cycles per wave-instruction)
+  ge_f32x16 dB[2];
 #pragma unroll
   for (int kt = 0; kt < 2; ++kt)
 #pragma unroll
     for (int i = 0; i < 16; ++i) dB[kt][i] = 0.f;
 
-  // Software pipeline over the windows of this persistent workgroup (round 6): the operands of window i + 1 are fetched into registers
-  // (2 operands x 4 pieces per lane = 32 VGPRs; wave 0: q, k; wave 1: v, dO) right after window i's tiles have been parked in LDS, and stay
-  // in flight under all of window i's arithmetic — an item used to start with 2 - 3 us of exposed load latency, 7.6 us per item in total
-  // at four resident workgroups per CU.  The token tables are double-buffered in LDS (one barrier less per window).
-  uint4 pa[4], pb[4];
-  auto fetch = [&](int bw_, const WinMeta& mm) {
-    const int b_ = bw_ / nW;
-    const bf16_t* base_ = qkv + (long)b_ * L * 3 * g.C;
-    if (qt == 0) {
-      load_rm(base_, 3 * g.C, head * HD, mm.tok, qkv_bias, lane, pa);
-      load_rm(base_, 3 * g.C, g.C + head * HD, mm.tok, qkv_bias, lane, pb);
-    } else {
-      load_rm(base_, 3 * g.C, 2 * g.C + head * HD, mm.tok, qkv_bias, lane, pa);
-      load_rm(gout + (long)b_ * L * g.C, g.C, head * HD, mm.tok, nullptr, lane, pb);
-    }
-  };
   auto meta_of = [&](int bw_, WinMeta& mm) {
     const int b_ = bw_ / nW, win_ = bw_ - b_ * nW;
     const int wy_ = win_ / g.nWw, wx_ = win_ - wy_ * g.nWw;
@@ -662,20 +449,28 @@ __global__ void __launch_bounds__(128, WA_BWD_WAVES) window_attn_bwd_mfma2_k(con
   if (slot < n_bw) {
     if (qt == 0) meta_of(slot, sm.m[0]);
     __syncthreads();
-    if (WA_BWD_PREFETCH) fetch(slot, sm.m[0]);
   }
   int cur = 0;
   for (int bw = slot; bw < n_bw; bw += wg_per_head, cur ^= 1) {
     const int b = bw / nW, win = bw - b * nW;
     const int wy = win / g.nWw, wx = win - wy * g.nWw;
     const WinMeta& M = sm.m[cur];
-    if (!WA_BWD_PREFETCH) fetch(bw, M);                     // (A/B) no pipeline: load now, as round 5 did
-    if (qt == 0) { store_rm(sm.q, lane, pa); store_rm(sm.k, lane, pb); }
-    else { store_rm(sm.v, lane, pa); store_rm(sm.go, lane, pb); }
-    const int bw_next = bw + wg_per_head;
-    if (bw_next < n_bw && qt == 0) meta_of(bw_next, sm.m[cur ^ 1]);
+    {
+      const bf16_t* base = qkv + (long)b * L * 3 * g.C;
+      uint4 pa[4], pb[4];                                    // both operands' loads are issued before either LDS store
+      if (qt == 0) {
+        load_rm(base, 3 * g.C, head * HD, M.tok, qkv_bias, lane, pa);
+        load_rm(base, 3 * g.C, g.C + head * HD, M.tok, qkv_bias, lane, pb);
+        store_rm(sm.q, lane, pa); store_rm(sm.k, lane, pb);
+      } else {
+        load_rm(base, 3 * g.C, 2 * g.C + head * HD, M.tok, qkv_bias, lane, pa);
+        load_rm(gout + (long)b * L * g.C, g.C, head * HD, M.tok, nullptr, lane, pb);
+        store_rm(sm.v, lane, pa); store_rm(sm.go, lane, pb);
+      }
+    }
     __syncthreads();
-    if (WA_BWD_PREFETCH && bw_next < n_bw) fetch(bw_next, sm.m[cur ^ 1]);
+    const int bw_next = bw + wg_per_head;
+    if (bw_next < n_bw && qt == 0) meta_of(bw_next, sm.m[cur ^ 1]);   // only here: see WinSmemMfmaBwd2::m
 
     ge_f32x16 P[2], dS[2];
     st_tiles_q(sm.k, sm.q, qt, c, hi, P);
@@ -761,7 +556,8 @@ __global__ void __launch_bounds__(128, WA_BWD_WAVES) window_attn_bwd_mfma2_k(con
         }
       }
     }
-    // (the loop-top stores of the next window's tiles must not overtake this window's last fragment reads: the second barrier of pass 1 orders them)
+    // no barrier here: the loop-top stores of the next window's tiles come after this window's last fragment reads (the second barrier of pass 1),
+    // M is not rewritten before the next iteration's first barrier, and sm.dpad[qt] is this wave's own
   }
   for (int w = 0; w < 2; ++w) {                                // wave after wave: a fixed summation order, bit-reproducible gradients
     if (qt == w) {
@@ -782,8 +578,6 @@ __global__ void __launch_bounds__(128, WA_BWD_WAVES) window_attn_bwd_mfma2_k(con
   if (tid < 2 * HD) wsp[NBIAS + tid] = sm.dpad[0][tid] + sm.dpad[1][tid];
 }
 
-extern const int ge_window_attn_mfma_available = 3;   // bit0: forward, bit1: backward
-
 int ge_window_attn_fwd_mfma(const void* qkv, const float* qkv_bias, const float* bias_table, void* out, const WinGeom& g,
                             float scale, bool fp8, hipStream_t s) {
   const long items = (long)g.B * g.nWh * g.nWw * g.nH;
@@ -796,15 +590,8 @@ int ge_window_attn_fwd_mfma(const void* qkv, const float* qkv_bias, const float*
 }
 int ge_window_attn_bwd_mfma(const void* qkv, const float* qkv_bias, const float* bias_table, const void* d_out, void* d_qkv,
                             float* workspace, const WinGeom& g, float scale, int wg_per_head, hipStream_t s) {
-  static const int two_wave = [] { const char* e = getenv("GE_WINATTN_BWD"); return !(e && e[0] == '1') ? 1 : 0; }();     // GE_WINATTN_BWD=1: single-wave kernel (A/B)
-  if (two_wave)
-    window_attn_bwd_mfma2_k<<<(unsigned)(wg_per_head * g.nH), 128, 0, s>>>((const bf16_t*)qkv, qkv_bias, bias_table,
-                                                                           (const bf16_t*)d_out, (bf16_t*)d_qkv, workspace, g,
-                                                                           scale, wg_per_head);
-  else
-    window_attn_bwd_mfma_k<<<(unsigned)(wg_per_head * g.nH), 64, 0, s>>>((const bf16_t*)qkv, qkv_bias, bias_table,
-                                                                         (const bf16_t*)d_out, (bf16_t*)d_qkv, workspace, g,
-                                                                         scale, wg_per_head);
+  window_attn_bwd_mfma2_k<<<(unsigned)(wg_per_head * g.nH), 128, 0, s>>>((const bf16_t*)qkv, qkv_bias, bias_table, (const bf16_t*)d_out,
+                                                                         (bf16_t*)d_qkv, workspace, g, scale, wg_per_head);
   GE_LAUNCH_CHECK();
   return GE_OK;
 }

@@ -6,7 +6,8 @@ a. routed inputs, bit for bit: every query attends to exactly one key, so out is
    LDS transposes and the pad rows.
 b. the mask is an additive -100: a score of 362 in another region still wins (bit for bit); one of 23 loses (against float64).
 c. stress inputs (peaked softmax, a common offset on k, an offset on v, a large bias table) against the float64 reference.
-d. many windows per persistent workgroup, unevenly divided: the register-held bias-table gradient summed over 3 and 4 windows.
+d. many windows per persistent workgroup, unevenly divided: the register-held bias-table gradient summed over 3 and 4 windows; routing there
+   bit for bit (the double-buffered token tables of the two-wave backward) and bit-identical gradients over repeated runs.
 e. fp8: all-zero q and v tiles.
 
 Tolerances of b - d are not constants.  The budget of a (case, tensor) pair is the error of ``winattn_ref.model`` — the same computation on the CPU
@@ -221,6 +222,48 @@ MANY_HEADS = (0, 23)
 # d_table 1.55, 1.68
 
 
+@functools.lru_cache(maxsize=None)
+def _many_inputs():
+    B, H, W, nH = MANY
+    C = nH * 32
+    g = gen(57)
+    qkv = torch.randn(B, H * W, 3 * C, generator=g).bfloat16()
+    qb = (0.3 * torch.randn(3 * C, generator=g)).bfloat16()
+    tab = 0.5 * torch.randn(169, nH, generator=g)
+    go = torch.randn(B, H * W, C, generator=g).bfloat16()
+    return qkv, qb, tab, go
+
+
+def test_many_windows_routing_and_repeatability(dev):
+    """Routed inputs at the MANY geometry, bit for bit, on variants 1 (bf16) and 2: a persistent workgroup walks 3 or 4 windows with the token
+    tables of two of them in LDS, and a dK / dV tile stored through another window's table lands in wrong rows, which fails the gathers exactly.
+
+    Then variant 2 three times on the same inputs, the routed ones and the random ones of test_many_windows_per_workgroup (on the routed ones
+    d_table and d_qkv_bias are zero): d_qkv is written by plain stores, d_table and d_qkv_bias are summed in a fixed order (per wave in LDS, then
+    the two-stage reduction over workgroups), so all three are bit-identical from run to run.  Measured on MI355X before asserting: identical on
+    both inputs, with this kernel and with its predecessor."""
+    B, H, W, nH = MANY
+    shift, C = 3, nH * 32
+    r, tab = _routed(MANY, shift, 8, False)
+    for variant, dt in ((1, torch.bfloat16), (2, torch.bfloat16)):
+        what = f'variant {variant} {dt} {MANY} shift {shift}'
+        o, dqkv, dqb, dtab = run_kernel(dev, r['qkv'], r['qkv_bias'], tab, r['go'], H, W, nH, shift, variant, dt)
+        for x in (o, dqkv, dqb, dtab):
+            assert bool(torch.isfinite(x).all()), what
+        assert torch.equal(o, r['out']), f'{what}: out is not the gather, {int((o != r["out"]).sum())} elements differ'
+        assert torch.equal(dqkv[:, :, 2 * C:], r['dv']), f'{what}: d_v is not the inverse gather, {int((dqkv[:, :, 2 * C:] != r["dv"]).sum())} elements differ'
+        assert not bool(dqkv[:, :, :C].any()), f'{what}: d_q'
+        assert not bool(dqkv[:, :, C:2 * C].any()), f'{what}: d_k'
+        assert not bool(dtab.any()), f'{what}: d_table'
+        assert not bool(dqb.any()), f'{what}: d_qkv_bias'
+    for label, args in (('routed', (r['qkv'], r['qkv_bias'], tab, r['go'])), ('random', _many_inputs())):
+        runs = [run_kernel(dev, *args, H, W, nH, shift, 2, torch.bfloat16) for _ in range(3)]
+        same = {name: all(torch.equal(runs[0][i], x[i]) for x in runs[1:]) for i, name in enumerate(NAMES)}
+        print(f'[winattn repeat {label} {MANY}] bit-identical over 3 runs: ' + ', '.join(f'{k} {v}' for k, v in same.items()))
+        assert same['d_qkv'], f'{label}: d_qkv differs between runs on the same inputs'
+        assert same['d_qkv_bias'] and same['d_table'], f'{label}: {same}'
+
+
 def test_many_windows_per_workgroup(dev):
     """bwd_wg_per_head takes its ``want`` branch (Swin stage 0 at batch >= 3) and the windows do not divide evenly.  Heads are independent, so the
     float64 reference (oracle semantics) runs on heads 0 and 23 only: a 2-head problem on their columns, which test_winattn_ref_cpu.py shows
@@ -232,11 +275,7 @@ def test_many_windows_per_workgroup(dev):
     wg_per_head = int(hip.lib().ge_window_attn_bwd_workspace(B, H, W, nH)) // (nH * (169 + 64) * 4)
     assert wg_per_head < -(-n_bw // 3), 'the workgroup count is capped by min_win, not by the resident-workgroup target'
     assert n_bw % wg_per_head != 0 and n_bw // wg_per_head >= 3, (n_bw, wg_per_head)
-    g = gen(57)
-    qkv = torch.randn(B, H * W, 3 * C, generator=g).bfloat16()
-    qb = (0.3 * torch.randn(3 * C, generator=g)).bfloat16()
-    tab = 0.5 * torch.randn(169, nH, generator=g)
-    go = torch.randn(B, H * W, C, generator=g).bfloat16()
+    qkv, qb, tab, go = _many_inputs()
     heads, cols = R.columns(nH, MANY_HEADS)
     sub = (qkv[:, :, cols].double(), qb[cols].double(), tab[:, heads].double(), go[:, :, cols[:len(cols) // 3]].double(), H, W, len(heads), shift)
     ref = reference(*sub)
