@@ -127,6 +127,7 @@ class BatchDepthInferencer(DepthInferencer):
             tops = [int(b.shape[0] - s['height']) for b in bgrs]                  # KBCrop
             lefts = [int((b.shape[1] - s['width']) / 2) for b in bgrs]
             raws = [self.ground_depth(b.shape[0], b.shape[1], p, pe, calib, cam_height) for b, p, pe in zip(bgrs, paths, pes)]
+            self.last_ground_depths = raws                    # kept for the stratified evaluation, as last_ground_depth is
             devs = [up(b, self.device) for up, b in zip(self._stagings, bgrs)]
             K.infer_front_batch(devs, raws, self.static_in, tops, lefts, s['mean'], s['std'], s['views'], s['to_rgb'], s['pe_max'],
                                 s['depth_scale'])
@@ -143,6 +144,7 @@ class BatchDepthInferencer(DepthInferencer):
     def reset(self):
         super().reset()
         self.last_n = 0                              # the frame count of the last batch
+        self.last_ground_depths = None               # the raw (H, W) f32 ground depths the last batch's front end was given
 
     def run(self, imgs, pes=None, calib=None, cam_height=1.65, graph=True):
         """Any number of frames, in batches of F with the next batch decoding ahead -> one host map per frame, in order."""

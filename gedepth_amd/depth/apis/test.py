@@ -12,6 +12,12 @@ close to 1.25^p.  ``show`` / ``out_dir`` and ``mask_pe`` are not covered.  ``eva
 batched engine (apis/batch_inference.py) and one ``ge_depth_metrics_batch`` call per batch, the next batch's image and ground-truth PNGs
 decoding on a thread pool meanwhile; same rows, same tuples.  Speed: README "KITTI speed" (KITTI); DDAD not measured.
 
+``strata=StrataSpec(...)`` (with ``device_eval``; KITTI protocol, any ``eval_batch``) adds one ``ge_depth_metrics_strata[_batch]`` call per
+frame or batch behind the unchanged ``ge_depth_metrics[_batch]`` call, on the same stream and the same upload of the ground truth: the
+ten sums per distance bin and on / off ground class (include/gedepth_strata.h), the ground plane being what the engine fed the front end
+(``last_ground_depth`` / ``last_ground_depths``).  Both buffers come back in the loop's one synchronisation and the loop returns
+``(results, rows)``, ``rows`` (N, S, 10) float64; ``dataset.evaluate_strata`` prints the table.  Speed: README "Where the error is".
+
 ``ground_dir`` writes every image's ground maps (``DepthInferencer.ground_maps`` -> ``show_ground``: attention, slope and ground-depth
 pictures, or one ``.npz`` under ``format_only``).  The maps exist on the engine's route only, so the frames go through the engine: alone
 (no result list), or in the same pass as ``device_eval``; with the host loop's ``pre_eval`` it raises.  Speed: not measured.
@@ -21,6 +27,7 @@ slope-adjusted ground plane in one binary ``.ply`` (``DepthInferencer.scene_poin
 returns no results and combines with no other output.  The loop: speed not measured; the kernel: README "Scene clouds"."""
 import os.path as osp
 
+import numpy as np
 import torch
 import torch.distributed as dist
 
@@ -141,9 +148,10 @@ def _scene_only(model, data_loader, scene_dir):
     return []
 
 
-def _device_eval_batches(dataset, eng, indices, frames, sums, size, graph):
+def _device_eval_batches(dataset, eng, indices, frames, sums, size, graph, strata=None, rows=None):
     """``_device_eval``'s frames in batches of ``size``: the pool decodes the next batch's image and ground-truth PNGs while the batched
-    engine and ``pre_eval_device_batch`` work on the current one; batch k fills rows ``k * size ..`` of ``sums``."""
+    engine and ``pre_eval_device_batch`` work on the current one; batch k fills rows ``k * size ..`` of ``sums`` (and, with ``strata``, of
+    ``rows``, from the same uploads and the ground depths the batch's front end was fed)."""
     from .batch_inference import decode_ahead
     from .inference import _decode
     jobs = [(lambda i=i, f=f: (_decode(f['img']), dataset.gt_raw(i))) for i, f in zip(indices, frames)]
@@ -152,14 +160,31 @@ def _device_eval_batches(dataset, eng, indices, frames, sums, size, graph):
         n = len(decoded)
         preds = eng.batch([d[0] for d in decoded], graph=graph, to_host=False, paths=[f['img'] for f in frames[row:row + n]])
         with torch.cuda.stream(eng.stream):
-            dataset.pre_eval_device_batch(preds, indices[row:row + n], sums[row:row + n], raws=[d[1] for d in decoded])
+            if strata is None:
+                dataset.pre_eval_device_batch(preds, indices[row:row + n], sums[row:row + n], raws=[d[1] for d in decoded])
+            else:
+                dataset.pre_eval_device_strata_batch(preds, indices[row:row + n], rows[row:row + n], strata, _strata_ground(eng, strata, True),
+                                                     raws=[d[1] for d in decoded], sums_rows=sums[row:row + n])
         row += n
 
 
-def _device_eval(model, data_loader, pre_eval, format_only, show, out_dir, ply_dir=None, ground_dir=None, eval_batch=1, engine_graph=True):
+def _strata_ground(eng, strata, batched=False):
+    """What the engine's front end was last fed as ground depth (a tensor, or the batch's list), None when ``strata`` has no ground class."""
+    if not strata.ground:
+        return None
+    ground = getattr(eng, 'last_ground_depths' if batched else 'last_ground_depth', None)
+    if ground is None:
+        raise NotImplementedError('strata with spec.ground: the model\'s front end was fed no ground depth; use StrataSpec(ground=False)')
+    return ground
+
+
+def _device_eval(model, data_loader, pre_eval, format_only, show, out_dir, ply_dir=None, ground_dir=None, eval_batch=1, engine_graph=True,
+                 strata=None):
     """The ``device_eval`` loop of ``single_gpu_test``: the list of metric tuples ``pre_eval`` yields, in the sampler's order.
     ``eval_batch=F > 1``: the sampler's indices in batches of F through the batched engine and ``pre_eval_device_batch``, image and
-    ground-truth PNGs of the next batch decoding ahead; same rows of the same buffer, same one copy at the end."""
+    ground-truth PNGs of the next batch decoding ahead; same rows of the same buffer, same one copy at the end.  ``strata`` (a
+    ``core.StrataSpec``): every image's sums per stratum as well, into an (N, S, 10) buffer that comes back in the same synchronisation;
+    the result is ``(the list, rows)``."""
     from ..core.evaluation import metrics_from_sums
     dataset = data_loader.dataset
     if not pre_eval or format_only:
@@ -170,8 +195,9 @@ def _device_eval(model, data_loader, pre_eval, format_only, show, out_dir, ply_d
         raise NotImplementedError('ground_dir with eval_batch > 1: the ground maps come from the single-frame engine; use eval_batch=1')
     depther, eng, indices, frames = _engine_frames(model, data_loader, 'device_eval', batch=eval_batch)
     sums = torch.empty(max(len(indices), 1), 10, device=eng.device, dtype=torch.float64)
+    rows = None if strata is None else torch.empty(max(len(indices), 1), strata.count, 10, device=eng.device, dtype=torch.float64)
     if eval_batch != 1:
-        _device_eval_batches(dataset, eng, indices, frames, sums, eval_batch, engine_graph)
+        _device_eval_batches(dataset, eng, indices, frames, sums, eval_batch, engine_graph, strata, rows)
     else:
         for row, (i, frame) in enumerate(zip(indices, frames)):
             if ground_dir:
@@ -180,17 +206,25 @@ def _device_eval(model, data_loader, pre_eval, format_only, show, out_dir, ply_d
             else:
                 pred = eng(to_host=False, graph=engine_graph, **frame)
             with torch.cuda.stream(eng.stream):
-                dataset.pre_eval_device(pred, i, sums[row])
+                if strata is None:
+                    dataset.pre_eval_device(pred, i, sums[row])
+                else:
+                    dataset.pre_eval_device_strata(pred, i, rows[row], strata, _strata_ground(eng, strata), sums_row=sums[row])
             if ground_dir:
                 depther.show_ground(maps, _ground_file(dataset, i, ground_dir))
     with torch.cuda.stream(eng.stream):
+        if strata is not None:
+            host_rows = torch.empty(len(indices), strata.count, 10, dtype=torch.float64, pin_memory=True)
+            host_rows.copy_(rows[:len(indices)], non_blocking=True)    # ordered before the copy below on the same stream
         host = sums[:len(indices)].cpu().numpy()                       # the one copy (and the one synchronisation) of the loop
     torch.cuda.current_stream(eng.device).wait_stream(eng.stream)
-    return [metrics_from_sums(r) for r in host]
+    results = [metrics_from_sums(r) for r in host]
+    return results if strata is None else (results, host_rows.numpy().copy())
 
 
 def single_gpu_test(model, data_loader, pre_eval=False, format_only=False, format_args=None, device=None, *, show=False,
-                    out_dir=None, device_eval=False, ply_dir=None, ground_dir=None, eval_batch=1, engine_graph=True, scene_dir=None):
+                    out_dir=None, device_eval=False, ply_dir=None, ground_dir=None, eval_batch=1, engine_graph=True, scene_dir=None,
+                    strata=None):
     """Returns a list with one entry per image: the metric tuple (``pre_eval``) or the ``(1, H, W)`` depth map.  ``show`` / ``out_dir``:
     ``show_result`` of every image's map, written to ``out_dir/replace_str(ori_filename)`` (``format_only``: the raw map as
     ``out_dir/<ori_filename without extension>.npy``).  ``ply_dir``: every image's point cloud as ``ply_dir/<ori_filename with .ply>``
@@ -198,8 +232,17 @@ def single_gpu_test(model, data_loader, pre_eval=False, format_only=False, forma
     DDAD protocol): the module docstring.  ``ground_dir``: every image's ground maps (module docstring); without ``device_eval`` the
     result is an empty list.  ``eval_batch=F`` (2 .. 8; with ``device_eval``, KITTI protocol, no ``ground_dir``): F frames per forward
     (``_device_eval``).  ``engine_graph=False``: the engine of ``device_eval`` runs eagerly and captures no hipGraph.  ``scene_dir`` (KITTI
-    protocol; alone): every image's scene cloud as ``scene_dir/<ori_filename with .ply>`` (module docstring); the result is an empty list."""
+    protocol; alone): every image's scene cloud as ``scene_dir/<ori_filename with .ply>`` (module docstring); the result is an empty list.
+    ``strata`` (a ``core.StrataSpec``; with ``device_eval``, KITTI protocol, any ``eval_batch``): the loop also reduces every map to its
+    metric sums per distance bin and on / off ground class (include/gedepth_strata.h) and returns ``(results, rows)``: ``results`` the list
+    it returns without ``strata``, ``rows`` an (N, S, 10) float64 array in the same order (``dataset.evaluate_strata`` prints its table)."""
     model.eval()
+    if strata is not None:
+        if not device_eval:
+            raise NotImplementedError('strata are reduced by the device evaluation loop: it needs device_eval=True (the host loop is not covered)')
+        if getattr(data_loader.dataset, 'device_protocol', None) != 'kitti':
+            raise NotImplementedError(f'strata: {type(data_loader.dataset).__name__} is not evaluated by the KITTI protocol (the DDAD protocol\'s '
+                                      'ge_depth_metrics_resized has no stratified form)')
     if scene_dir:
         if pre_eval or format_only or show or out_dir or ply_dir or ground_dir or device_eval:
             raise NotImplementedError('scene_dir with pre_eval / format_only / show / out_dir / ply_dir / ground_dir / device_eval: the scene '
@@ -208,7 +251,7 @@ def single_gpu_test(model, data_loader, pre_eval=False, format_only=False, forma
     if eval_batch != 1 and not device_eval:
         raise NotImplementedError('eval_batch > 1 batches the device evaluation loop: it needs device_eval=True')
     if device_eval:
-        return _device_eval(model, data_loader, pre_eval, format_only, show, out_dir, ply_dir, ground_dir, eval_batch, engine_graph)
+        return _device_eval(model, data_loader, pre_eval, format_only, show, out_dir, ply_dir, ground_dir, eval_batch, engine_graph, strata)
     if ground_dir:
         if pre_eval:
             raise NotImplementedError('ground_dir with the host loop\'s pre_eval: the ground maps exist on the engine\'s route only; '
@@ -240,13 +283,13 @@ def single_gpu_test(model, data_loader, pre_eval=False, format_only=False, forma
 
 
 def multi_gpu_test(model, data_loader, pre_eval=False, format_only=False, format_args=None, device=None, *, show=False, out_dir=None,
-                   device_eval=False, ply_dir=None, ground_dir=None, eval_batch=1, engine_graph=True, scene_dir=None):
+                   device_eval=False, ply_dir=None, ground_dir=None, eval_batch=1, engine_graph=True, scene_dir=None, strata=None):
     """Each rank evaluates its shard of a non-shuffled DistributedSampler; rank 0 receives the results in dataset order.  ``show`` /
-    ``out_dir`` / ``ply_dir`` / ``ground_dir`` / ``scene_dir`` / ``device_eval`` / ``eval_batch`` / ``engine_graph`` as in
-    ``single_gpu_test``: every rank writes the files of its own shard."""
+    ``out_dir`` / ``ply_dir`` / ``ground_dir`` / ``scene_dir`` / ``device_eval`` / ``eval_batch`` / ``engine_graph`` / ``strata`` as in
+    ``single_gpu_test``: every rank writes the files of its own shard; with ``strata`` rank 0 receives ``(results, rows)``."""
     part = single_gpu_test(model, data_loader, pre_eval, format_only, format_args, device, show=show, out_dir=out_dir,
                            device_eval=device_eval, ply_dir=ply_dir, ground_dir=ground_dir, eval_batch=eval_batch, engine_graph=engine_graph,
-                           scene_dir=scene_dir)
+                           scene_dir=scene_dir, strata=strata)
     rank, world = get_dist_info()
     if world == 1:
         return part
@@ -254,9 +297,21 @@ def multi_gpu_test(model, data_loader, pre_eval=False, format_only=False, format
     dist.all_gather_object(gathered, part)
     if rank != 0:
         return None
+    total = len(data_loader.dataset)
+    if strata is None:
+        return interleave_shards(gathered, total)
+    return interleave_shards([g[0] for g in gathered], total), interleave_shards([g[1] for g in gathered], total)
+
+
+def interleave_shards(shards, total):
+    """The shards of a non-shuffled DistributedSampler, which deals indices round-robin (shard k holds entries k, k + world, ...), back in
+    dataset order, cut to ``total`` entries (the sampler pads the last round).  Lists give a list; arrays give an array stacked along axis 0."""
     ordered = []
-    for i in range(max(len(g) for g in gathered)):
-        for g in gathered:                          # DistributedSampler deals indices round-robin
+    for i in range(max(len(g) for g in shards)):
+        for g in shards:
             if i < len(g):
                 ordered.append(g[i])
-    return ordered[:len(data_loader.dataset)]
+    ordered = ordered[:total]
+    if shards and isinstance(shards[0], np.ndarray):
+        return np.stack(ordered) if ordered else shards[0][:0]
+    return ordered

@@ -1,4 +1,4 @@
-from .evaluation import calculate, eval_metrics, metrics, metrics_from_sums, pre_eval_to_metrics
+from .evaluation import StrataSpec, calculate, eval_metrics, metrics, metrics_from_sums, pre_eval_to_metrics, strata_table
 from .utils import add_prefix
 
-__all__ = ['calculate', 'eval_metrics', 'metrics', 'metrics_from_sums', 'pre_eval_to_metrics', 'add_prefix']
+__all__ = ['StrataSpec', 'calculate', 'eval_metrics', 'metrics', 'metrics_from_sums', 'pre_eval_to_metrics', 'strata_table', 'add_prefix']

@@ -193,6 +193,71 @@ class KITTIDataset(Dataset):
         K.depth_metric_sums_batch(preds, devs, tops, lefts, self.eval_rect(352, 1216), self.depth_scale, self.min_depth, self.max_depth,
                                   sums_rows)
 
+    def pre_eval_device_strata(self, pred, index, rows, spec, ground, sums_row=None):
+        """``pre_eval_device`` per stratum of ``spec`` (``core.StrataSpec``): ``rows`` one (S, 10) block of a device (N, S, 10) float64 buffer,
+        ``ground`` the frame's raw (H, W) float32 ground depth on the device (what the front end was fed; ignored unless ``spec.ground``).
+        ``sums_row``: also run ``pre_eval_device``'s own call into this (10,) row, on the same upload of the ground truth.  Does not
+        synchronise."""
+        import torch
+        from ... import kernels as K
+        if not (torch.is_tensor(pred) and pred.is_cuda and tuple(pred.shape) == (1, 352, 1216) and pred.dtype == torch.float32):
+            raise TypeError('pre_eval_device_strata takes a CUDA (1, 352, 1216) float32 prediction, got '
+                            f'{tuple(pred.shape) if torch.is_tensor(pred) else type(pred)}')
+        if spec.ground and ground is None:
+            raise ValueError('pre_eval_device_strata: spec.ground needs the frame\'s ground depth')
+        raw = self.gt_raw(index)
+        h, w = raw.shape
+        dev = self.__dict__.setdefault('_gt_upload', PinnedUpload())(raw, pred.device)      # one upload for both calls
+        top, left = int(h - 352), int((w - 1216) / 2)                   # eval_kb_crop
+        limits = (self.depth_scale, self.min_depth, self.max_depth)
+        if sums_row is not None:
+            K.depth_metric_sums(pred, dev, top, left, self.eval_rect(352, 1216), *limits, sums_row)
+        K.depth_metric_sums_strata(pred, dev, top, left, self.eval_rect(352, 1216), *limits, rows, spec.edges,
+                                   ground if spec.ground else None, spec.ground_tol)
+
+    def pre_eval_device_strata_batch(self, preds, indices, rows, spec, grounds, raws=None, sums_rows=None):
+        """``pre_eval_device_strata`` for n = ``len(indices)`` <= 8 images in one ``ge_depth_metrics_strata_batch`` call: ``rows`` n
+        (S, 10) blocks, ``grounds`` the n frames' ground depths, ``raws`` as in ``pre_eval_device_batch``.  ``sums_rows``: also run
+        ``pre_eval_device_batch``'s own call into these (n, 10) rows, on the same uploads.  Does not synchronise."""
+        import torch
+        from ... import kernels as K
+        n = len(indices)
+        if not (torch.is_tensor(preds) and preds.is_cuda and preds.dim() == 4 and tuple(preds.shape[1:]) == (1, 352, 1216)
+                and preds.shape[0] >= n and preds.dtype == torch.float32):
+            raise TypeError(f'pre_eval_device_strata_batch takes a CUDA (F >= {n}, 1, 352, 1216) float32 tensor, got '
+                            f'{tuple(preds.shape) if torch.is_tensor(preds) else type(preds)}')
+        if not 1 <= n <= 8 or tuple(rows.shape) != (n, spec.count, 10):
+            raise ValueError(f'pre_eval_device_strata_batch takes 1 .. 8 images and one ({spec.count}, 10) block each, got {n} and '
+                             f'{tuple(rows.shape)}')
+        if spec.ground and (grounds is None or len(grounds) != n):
+            raise ValueError('pre_eval_device_strata_batch: spec.ground needs every frame\'s ground depth')
+        raws = [self.gt_raw(i) for i in indices] if raws is None else raws
+        uploads = self.__dict__.setdefault('_gt_uploads', [])          # pre_eval_device_batch's staging buffers
+        while len(uploads) < n:
+            uploads.append(PinnedUpload())
+        devs = [up(raw, preds.device) for up, raw in zip(uploads, raws)]
+        tops = [int(r.shape[0] - 352) for r in raws]                    # eval_kb_crop
+        lefts = [int((r.shape[1] - 1216) / 2) for r in raws]
+        limits = (self.depth_scale, self.min_depth, self.max_depth)
+        if sums_rows is not None:
+            K.depth_metric_sums_batch(preds, devs, tops, lefts, self.eval_rect(352, 1216), *limits, sums_rows)
+        K.depth_metric_sums_strata_batch(preds, devs, tops, lefts, self.eval_rect(352, 1216), *limits, rows, spec.edges,
+                                         list(grounds) if spec.ground else None, spec.ground_tol)
+
+    def evaluate_strata(self, rows, spec, logger=None):
+        """``rows`` (N, S, 10) float64 from the device loop -> ``{'<stratum>.<metric>': value}`` (the nine metrics, ``pixels`` and ``images``
+        of ``core.strata_table``); prints the table."""
+        from ..core.evaluation import strata_table
+        table = strata_table(rows, spec, self.min_depth, self.max_depth)
+        cols = METRIC_NAMES + ('pixels', 'images')
+        width = max(len(name) for name in table)
+        lines = ['Strata:', ' | '.join([' ' * width] + [f'{k:>8s}' for k in cols])]
+        for name, entry in table.items():
+            lines.append(' | '.join([f'{name:<{width}s}'] + [f'{entry[k]:8.4f}' for k in METRIC_NAMES]
+                                    + [f'{entry["pixels"]:8.4f}', f'{entry["images"]:8d}']))
+        (logger.info if logger is not None and hasattr(logger, 'info') else print)('\n'.join(lines))
+        return {f'{name}.{k}': v for name, entry in table.items() for k, v in entry.items()}
+
     def pre_eval(self, preds, indices):
         """Per-image metric tuples for predictions ``(1, 352, 1216)`` (kitti.py:502-552)."""
         if not isinstance(indices, list):

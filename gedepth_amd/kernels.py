@@ -2120,3 +2120,6 @@ from .batch_kernels import depth_metric_sums_batch, infer_front_batch, tta_merge
 
 # --------------------------------------------------------------------- scene clouds (csrc/scene.hip, include/gedepth_scene.h)
 from .scene_kernels import SceneLayer, scene_points  # noqa: E402,F401
+
+# --------------------------------------------------------------------- stratified metric sums (csrc/eval.hip, include/gedepth_strata.h)
+from .strata_kernels import depth_metric_sums_strata, depth_metric_sums_strata_batch  # noqa: E402,F401

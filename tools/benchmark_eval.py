@@ -6,7 +6,9 @@ Frames: a seeded synthetic KITTI tree, 16 image / ground-truth PNG pairs of two 
 analytic ground plane), listed ``--frames`` times in the split, so every pass decodes ``--frames`` image and ``--frames`` ground-truth PNGs
 from files.  Round 0 warms up (the engines capture their graphs there) and is not counted; the settings then alternate, pass by pass, for
 ``--rounds`` rounds.  A pass is timed from the call to the returned list of metric tuples (the loop ends with its one synchronising copy).
-The last line is one JSON object: per F the median and the minimum of the passes in ms per frame."""
+The last line is one JSON object: per F the median and the minimum of the passes in ms per frame.  ``--strata`` times every F twice, without
+and with ``strata=StrataSpec()`` (eight strata: four distance bins, on / off ground), alternated pass by pass; the keys of the second are
+``"<F>+strata"``."""
 import argparse
 import json
 import os
@@ -61,6 +63,7 @@ def main(argv=None):
     p.add_argument('--rounds', type=int, default=3)
     p.add_argument('--bf16', action='store_true')
     p.add_argument('--seed', type=int, default=0)
+    p.add_argument('--strata', action='store_true', help='time every setting without and with the stratified sums (StrataSpec())')
     args = p.parse_args(argv)
     assert torch.cuda.is_available(), 'tools/benchmark_eval.py measures the MI355X'
     cfg = Config.fromfile(args.config)
@@ -71,19 +74,23 @@ def main(argv=None):
         ds = build_dataset(cfg.data.test, dict(test_mode=True))
         loader = build_dataloader(ds, 1, 0, dist=False, shuffle=False)
         assert len(ds) == args.frames
-        spent = {F: [] for F in args.eval_batch}
+        from gedepth_amd.depth.core import StrataSpec
+        settings = [(F, spec) for F in args.eval_batch for spec in ((None, StrataSpec()) if args.strata else (None,))]
+        spent = {f'{F}+strata' if spec else F: [] for F, spec in settings}
         summary = {}
         for rnd in range(args.rounds + 1):
-            for F in args.eval_batch:
+            for F, spec in settings:
+                key = f'{F}+strata' if spec else F
                 torch.cuda.synchronize()
                 t0 = time.perf_counter()
                 with torch.autocast('cuda', dtype=torch.bfloat16, enabled=args.bf16):
-                    res = single_gpu_test(model, loader, pre_eval=True, device_eval=True, eval_batch=F)
+                    res = single_gpu_test(model, loader, pre_eval=True, device_eval=True, eval_batch=F, strata=spec)
                 elapsed = time.perf_counter() - t0
+                res = res[0] if spec else res
                 if rnd:
-                    spent[F].append(1e3 * elapsed / args.frames)
-                    print(f'[eval_batch={F}] round {rnd}: {spent[F][-1]:.2f} ms / frame')
-                summary[F] = float(np.nanmean([r[3] for r in res]))                  # abs_rel, to see that the settings evaluate the same
+                    spent[key].append(1e3 * elapsed / args.frames)
+                    print(f'[eval_batch={key}] round {rnd}: {spent[key][-1]:.2f} ms / frame')
+                summary[key] = float(np.nanmean([r[3] for r in res]))                # abs_rel, to see that the settings evaluate the same
         result = dict(config=osp.basename(args.config), frames=args.frames, rounds=args.rounds, bf16=args.bf16,
                       source='synthetic 375x1242 + 370x1224, image and ground-truth PNGs',
                       ms_per_frame_median={str(F): round(statistics.median(v), 3) for F, v in spent.items()},

@@ -29,6 +29,11 @@ engine; it runs alone, without ``--eval`` or any other output.
 engine (flip-TTA for KITTI, the single view for DDAD) and each map is reduced to its metric sums by a HIP kernel, so no map is copied to the
 host (``single_gpu_test(device_eval=True)``).  ``--eval-batch F`` (KITTI protocol, 2 .. 8) runs F frames per forward and one metric launch
 per batch, with the next batch's image and ground-truth PNGs decoding on a thread pool meanwhile.
+
+``--strata [EDGE ...]`` (with ``--eval --device-eval``; KITTI protocol) also reduces every map per distance bin of the ground truth (bare
+``--strata``: edges 20 40 60 metres) and per on / off ground class: a LiDAR return is on the ground when it lies within
+``--strata-ground-tol`` (default 0.1) times the ground depth of the plane the front end was fed; ``--strata-no-ground`` keeps the bins only.
+The table is printed after the usual summary; ``--strata-out FILE.npz`` stores ``rows`` (N, S, 10), ``names`` and ``edges``.
 """
 import argparse
 import os
@@ -61,6 +66,13 @@ def parse_args(argv=None):
                    help='with --eval and --synthetic 0: the graphed inference engine and the metric-sum kernel instead of the host loop')
     p.add_argument('--eval-batch', type=int, default=1,
                    help='with --device-eval (KITTI protocol): frames per forward, 1 .. 8; the next batch\'s PNGs decode on a thread pool')
+    p.add_argument('--strata', nargs='*', type=float, default=None, metavar='EDGE',
+                   help='with --eval --device-eval (KITTI protocol): metrics per distance bin (edges in metres; none given: 20 40 60) and '
+                        'on / off ground')
+    p.add_argument('--strata-ground-tol', type=float, default=0.1,
+                   help='a return is on the ground when |gt - g| <= T * g for the ground depth g of its pixel, T in [0, 1]')
+    p.add_argument('--strata-no-ground', action='store_true', help='distance bins only')
+    p.add_argument('--strata-out', help='.npz file that receives the per-image sums of every stratum (rows, names, edges)')
     p.add_argument('--out', help='output result file in pickle format (.pkl / .pickle), written by rank 0')
     p.add_argument('--format-only', action='store_true',
                    help='format the results (dataset.format_results) without evaluating; with --show-dir the raw maps are saved as .npy')
@@ -95,6 +107,15 @@ def parse_args(argv=None):
         raise ValueError('--eval-batch needs --device-eval: it batches the device evaluation loop')
     if not 1 <= args.eval_batch <= 8:
         raise ValueError(f'--eval-batch must be in 1 .. 8, got {args.eval_batch}')
+    if args.strata is None:
+        if args.strata_out or args.strata_no_ground:
+            raise ValueError('--strata-out / --strata-no-ground need --strata')
+    else:
+        if not (args.eval and args.device_eval):
+            raise ValueError('--strata needs --eval and --device-eval: the strata are reduced by the device evaluation loop')
+        if args.strata_out is not None and not args.strata_out.endswith('.npz'):
+            raise ValueError('--strata-out must be an .npz file')
+        args.strata = args.strata or [20.0, 40.0, 60.0]
     if args.eval_batch != 1 and args.ground_dir:
         raise ValueError('--eval-batch > 1 cannot be combined with --ground-dir: the ground maps come from the single-frame engine')
     if args.ground_dir and args.eval and not args.device_eval:
@@ -104,6 +125,23 @@ def parse_args(argv=None):
     if args.out is not None and not args.out.endswith(('.pkl', '.pickle')):
         raise ValueError('The output file must be a pkl file.')
     return args
+
+
+def strata_spec(args):
+    """The ``StrataSpec`` of ``--strata`` and its companions, or None."""
+    if args.strata is None:
+        return None
+    from gedepth_amd.depth.core import StrataSpec
+    return StrataSpec(args.strata, not args.strata_no_ground, args.strata_ground_tol)
+
+
+def report_strata(args, dataset, spec, rows):
+    """The table after the usual summary, and ``--strata-out``."""
+    dataset.evaluate_strata(rows, spec)
+    if args.strata_out:
+        os.makedirs(osp.dirname(osp.abspath(args.strata_out)), exist_ok=True)
+        np.savez(args.strata_out, rows=rows, names=np.array(spec.names(dataset.min_depth, dataset.max_depth)), edges=np.array(spec.edges))
+        print(f'writing strata sums to {args.strata_out}')
 
 
 def run_dataset(args, cfg):
@@ -128,11 +166,14 @@ def run_dataset(args, cfg):
     model = model.cuda().eval()
     model.cfg = cfg
     test = multi_gpu_test if distributed else single_gpu_test
+    spec, rows = strata_spec(args), None
     with torch.autocast('cuda', dtype=torch.bfloat16, enabled=args.bf16):
         results = test(model, loader, pre_eval=args.eval is not None, format_only=args.format_only, format_args=eval_kwargs,
                        show=args.show, out_dir=args.show_dir, device_eval=args.device_eval, ply_dir=args.ply_dir,
-                       ground_dir=args.ground_dir, eval_batch=args.eval_batch, scene_dir=args.scene_dir)
+                       ground_dir=args.ground_dir, eval_batch=args.eval_batch, scene_dir=args.scene_dir, strata=spec)
     rank, _ = get_dist_info()
+    if spec is not None and results is not None:
+        results, rows = results
     if rank == 0:
         if args.out:
             os.makedirs(osp.dirname(osp.abspath(args.out)), exist_ok=True)
@@ -141,6 +182,8 @@ def run_dataset(args, cfg):
                 pickle.dump(results, fh)
         if args.eval:
             dataset.evaluate(results, args.eval, **eval_kwargs)
+            if spec is not None:
+                report_strata(args, dataset, spec, rows)
     if torch.distributed.is_available() and torch.distributed.is_initialized():
         torch.distributed.destroy_process_group()
 
@@ -166,9 +209,14 @@ def main():
         dataset = build_dataset(cfg.data.test, dict(test_mode=True))
         loader = build_dataloader(dataset, 1, cfg.data.workers_per_gpu, dist=False, shuffle=False)
         model.cfg = cfg
+        spec = strata_spec(args)
         with torch.autocast('cuda', dtype=torch.bfloat16, enabled=args.bf16):
-            results = single_gpu_test(model, loader, pre_eval=True, device_eval=args.device_eval, eval_batch=args.eval_batch)
+            results = single_gpu_test(model, loader, pre_eval=True, device_eval=args.device_eval, eval_batch=args.eval_batch, strata=spec)
+        if spec is not None:
+            results, rows = results
         dataset.evaluate(results)
+        if spec is not None:
+            report_strata(args, dataset, spec, rows)
         return
     res = []
     for i in range(args.synthetic):
