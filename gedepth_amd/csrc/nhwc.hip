@@ -12,8 +12,11 @@
 //   ge_concat_rows_*     torch.cat([a, b], 1) of two channels-last maps / token matrices with the HAHI glue folded in:
 //                        dropout(tokens) + identity written into its slot (hahi.py:326-346)
 //   ge_add_rows          tokens + positional embedding (fp32 (N, C), broadcast over the batch; hahi.py:303-306)
+//   level tokens         (include/gedepth_neck.h) the neck's (B, sum HW, C) matrix of concatenated levels, written / read / summed level by
+//                        level in place: ge_bn_act_nhwc_*_rows, ge_add_rows_levels, ge_level_colsum, ge_token_grad_sum
 // All HBM-bound streaming work: 16-byte accesses along the channel dimension, fp32 arithmetic, no MFMA.
 #include "common.h"
+#include "../../include/gedepth_neck.h"
 
 #define NH_MAXLANES 256
 
@@ -85,7 +88,27 @@ static inline void nh_reduce_launch(void* workspace, int C, int K, unsigned nb, 
   nh_partials_reduce_k<double><<<(K * C + 31) / 32, 256, 0, s>>>(nh_partials(workspace, C, K), (double*)workspace, K * C, (int)nb, 0);
 }
 
+// ---------------------------------------------------------------------------------------------- rows of one level
+// The rows of one level of a (B, N, C) token matrix, N = sum of the levels' rows: dense row r of the level's (B * nl, C) matrix is row
+// (r / nl) * N + start + r % nl of the token matrix.  A thread walks r = r0, r0 + step, ...: (image, row in the image) come from one 32-bit
+// division per thread, and every step adds the grid's stride split into whole images and a remainder — no division in the row loop.
+struct NhWalk {
+  int img, n, nl, sb, sn;
+  __device__ __forceinline__ NhWalk(unsigned r0, unsigned step, int nl_) : nl(nl_) {
+    const unsigned d = (unsigned)nl_;
+    img = (int)(r0 / d); n = (int)(r0 - (unsigned)img * d);
+    sb = (int)(step / d); sn = (int)(step - (unsigned)sb * d);
+  }
+  __device__ __forceinline__ void next() {
+    n += sn; img += sb;
+    if (n >= nl) { n -= nl; ++img; }
+  }
+  __device__ __forceinline__ long row(long image_stride) const { return (long)img * image_stride + n; }
+};
+#define NH_WALK_MAX_ROWS (1 << 30)      // rows per image of a level: n + sn stays inside an int
+
 // ============================================================================ BatchNorm2d (training) + (Leaky)ReLU
+// ROWS: the operand named below has a free image stride (ge_bn_act_nhwc_*_rows): `npi` rows per image, `istr` rows from image to image
 template <typename T>
 __global__ void __launch_bounds__(256) bn_stats_nhwc_k(const T* __restrict__ x, float* __restrict__ ws, int C, long R, int lpr, int rpi) {
   constexpr int VN = V8<T>::N;
@@ -103,9 +126,9 @@ __global__ void __launch_bounds__(256) bn_stats_nhwc_k(const T* __restrict__ x, 
     }
   nh_col_commit<2, VN>(acc, ws, C, lpr, rpi, c0);
 }
-template <typename T>
+template <typename T, bool ROWS = false>      // ROWS: y
 __global__ void __launch_bounds__(256) bn_apply_nhwc_k(const T* __restrict__ x, const float* __restrict__ coef, T* __restrict__ y, int C,
-                                                       long R, int lpr, int rpi, float slope) {
+                                                       long R, int lpr, int rpi, float slope, int npi = 0, long istr = 0) {
   constexpr int VN = V8<T>::N;
   const int t = threadIdx.x, lane = t % lpr, rs = t / lpr;
   if (rs >= rpi) return;
@@ -113,21 +136,24 @@ __global__ void __launch_bounds__(256) bn_apply_nhwc_k(const T* __restrict__ x, 
   float a[VN], b[VN];
 #pragma unroll
   for (int k = 0; k < VN; ++k) { a[k] = coef[c0 + k]; b[k] = coef[C + c0 + k]; }
+  NhWalk w(blockIdx.x * rpi + rs, gridDim.x * rpi, ROWS ? npi : 1);
   for (long r = (long)blockIdx.x * rpi + rs; r < R; r += (long)gridDim.x * rpi) {
     float v[VN];
     V8<T>::ld(x + r * C + c0, v);
 #pragma unroll
     for (int k = 0; k < VN; ++k) { const float tv = __fmaf_rn(v[k], a[k], b[k]); v[k] = tv > 0.f ? tv : tv * slope; }
-    V8<T>::st(y + r * C + c0, v);
+    if (ROWS) { V8<T>::st(y + w.row(istr) * C + c0, v); w.next(); }
+    else V8<T>::st(y + r * C + c0, v);
   }
 }
 // RECOMP: the activation decision y > 0 is recomputed from x with the forward's coefficients (same fma, same operands) instead of
 // reading y: one tensor less per pass (2 of the 7 passes of the backward)
-template <typename T, bool RECOMP>
+template <typename T, bool RECOMP, bool ROWS = false>      // ROWS: dy
 __global__ void __launch_bounds__(256) bn_bwd_stats_nhwc_k(const T* __restrict__ dy, const T* __restrict__ y, const T* __restrict__ x,
                                                            const float* __restrict__ gamma, const float* __restrict__ beta,
                                                            const float* __restrict__ save_mean, const float* __restrict__ save_rstd,
-                                                           float* __restrict__ ws, int C, long R, int lpr, int rpi, float slope) {
+                                                           float* __restrict__ ws, int C, long R, int lpr, int rpi, float slope, int npi = 0,
+                                                           long istr = 0) {
   constexpr int VN = V8<T>::N;
   const int t = threadIdx.x, lane = t % lpr, rs = t / lpr;
   const int c0 = lane * VN;
@@ -137,10 +163,12 @@ __global__ void __launch_bounds__(256) bn_bwd_stats_nhwc_k(const T* __restrict__
     mu[v] = save_mean[c0 + v]; rsd[v] = save_rstd[c0 + v]; acc[0][v] = 0.f; acc[1][v] = 0.f;
     if (RECOMP) { fa[v] = gamma[c0 + v] * rsd[v]; fb[v] = __fmaf_rn(-mu[v], fa[v], beta[c0 + v]); }
   }
+  NhWalk w(blockIdx.x * rpi + rs, gridDim.x * rpi, ROWS ? npi : 1);
   if (rs < rpi)
     for (long r = (long)blockIdx.x * rpi + rs; r < R; r += (long)gridDim.x * rpi) {
       float g[VN], yv[VN], xv[VN];
-      V8<T>::ld(dy + r * C + c0, g);
+      if (ROWS) { V8<T>::ld(dy + w.row(istr) * C + c0, g); w.next(); }
+      else V8<T>::ld(dy + r * C + c0, g);
       V8<T>::ld(x + r * C + c0, xv);
       if (RECOMP) {
 #pragma unroll
@@ -157,11 +185,12 @@ __global__ void __launch_bounds__(256) bn_bwd_stats_nhwc_k(const T* __restrict__
     }
   nh_col_commit<2, VN>(acc, ws, C, lpr, rpi, c0);
 }
-template <typename T, bool RECOMP>
+template <typename T, bool RECOMP, bool ROWS = false>      // ROWS: dy
 __global__ void __launch_bounds__(256) bn_bwd_apply_nhwc_k(const T* __restrict__ dy, const T* __restrict__ y, const T* __restrict__ x,
                                                            const float* __restrict__ beta, const float* __restrict__ save_mean,
                                                            const float* __restrict__ save_rstd, const float* __restrict__ coef,
-                                                           T* __restrict__ dx, int C, long R, int lpr, int rpi, float slope) {
+                                                           T* __restrict__ dx, int C, long R, int lpr, int rpi, float slope, int npi = 0,
+                                                           long istr = 0) {
   constexpr int VN = V8<T>::N;
   const int t = threadIdx.x, lane = t % lpr, rs = t / lpr;
   if (rs >= rpi) return;
@@ -172,9 +201,11 @@ __global__ void __launch_bounds__(256) bn_bwd_apply_nhwc_k(const T* __restrict__
     a[k] = coef[c0 + k]; m1[k] = coef[C + c0 + k]; m2[k] = coef[2 * C + c0 + k]; mu[k] = save_mean[c0 + k]; rsd[k] = save_rstd[c0 + k];
     if (RECOMP) fb[k] = __fmaf_rn(-mu[k], a[k], beta[c0 + k]);          // coef[c] is gamma * rstd, the forward's scale
   }
+  NhWalk w(blockIdx.x * rpi + rs, gridDim.x * rpi, ROWS ? npi : 1);
   for (long r = (long)blockIdx.x * rpi + rs; r < R; r += (long)gridDim.x * rpi) {
     float g[VN], yv[VN], xv[VN];
-    V8<T>::ld(dy + r * C + c0, g);
+    if (ROWS) { V8<T>::ld(dy + w.row(istr) * C + c0, g); w.next(); }
+    else V8<T>::ld(dy + r * C + c0, g);
     V8<T>::ld(x + r * C + c0, xv);
     if (RECOMP) {
 #pragma unroll
@@ -242,7 +273,7 @@ static inline unsigned nh_grid_apply(long R, int rpi) { return ge_blocks(R, rpi 
 template <typename T>
 static int bn_nhwc_fwd_launch(const void* x, const float* gamma, const float* beta, void* y, float* save_mean, float* save_rstd,
                               float* running_mean, float* running_var, void* workspace, long R, int C, float eps, float momentum,
-                              float slope, hipStream_t s) {
+                              float slope, hipStream_t s, long npi = 0, long istr = 0) {      // npi > 0: y has a free image stride
   int lpr, rpi;
   if (!nh_geom<T>(C, lpr, rpi) || !nh_aligned(x, y)) return GE_ERR_UNSUPPORTED;
   double* ws = (double*)workspace;
@@ -254,28 +285,31 @@ static int bn_nhwc_fwd_launch(const void* x, const float* gamma, const float* be
   GE_LAUNCH_CHECK();
   bn_finalize_nhwc_k<<<(C + 255) / 256, 256, 0, s>>>(ws, gamma, beta, save_mean, save_rstd, running_mean, running_var, coef, C, (double)R, eps, momentum);
   GE_LAUNCH_CHECK();
-  bn_apply_nhwc_k<T><<<nh_grid_apply(R, rpi), 256, 0, s>>>((const T*)x, coef, (T*)y, C, R, lpr, rpi, slope);
+  if (npi) bn_apply_nhwc_k<T, true><<<nh_grid_apply(R, rpi), 256, 0, s>>>((const T*)x, coef, (T*)y, C, R, lpr, rpi, slope, (int)npi, istr);
+  else bn_apply_nhwc_k<T><<<nh_grid_apply(R, rpi), 256, 0, s>>>((const T*)x, coef, (T*)y, C, R, lpr, rpi, slope);
   GE_LAUNCH_CHECK();
   return GE_OK;
 }
 template <typename T>
 static int bn_nhwc_bwd_launch(const void* dy, const void* y, const void* x, const float* gamma, const float* beta, const float* save_mean,
                               const float* save_rstd, void* dx, float* dgamma, float* dbeta, void* workspace, long R, int C, float slope,
-                              hipStream_t s) {
+                              hipStream_t s, long npi = 0, long istr = 0) {      // npi > 0 (with beta): dy has a free image stride
   int lpr, rpi;
   if (!nh_geom<T>(C, lpr, rpi) || !nh_aligned(dy, y, x, dx)) return GE_ERR_UNSUPPORTED;
   double* ws = (double*)workspace;
   float* coef = (float*)(ws + 2 * C);
   const unsigned nb = nh_grid_rows(R, rpi);
   float* part = nh_partials(workspace, C, 2);
-  if (beta) bn_bwd_stats_nhwc_k<T, true><<<nb, 256, 0, s>>>((const T*)dy, nullptr, (const T*)x, gamma, beta, save_mean, save_rstd, part, C, R, lpr, rpi, slope);
+  if (npi) bn_bwd_stats_nhwc_k<T, true, true><<<nb, 256, 0, s>>>((const T*)dy, nullptr, (const T*)x, gamma, beta, save_mean, save_rstd, part, C, R, lpr, rpi, slope, (int)npi, istr);
+  else if (beta) bn_bwd_stats_nhwc_k<T, true><<<nb, 256, 0, s>>>((const T*)dy, nullptr, (const T*)x, gamma, beta, save_mean, save_rstd, part, C, R, lpr, rpi, slope);
   else bn_bwd_stats_nhwc_k<T, false><<<nb, 256, 0, s>>>((const T*)dy, (const T*)y, (const T*)x, gamma, beta, save_mean, save_rstd, part, C, R, lpr, rpi, slope);
   GE_LAUNCH_CHECK();
   nh_reduce_launch(workspace, C, 2, nb, s);
   GE_LAUNCH_CHECK();
   bn_bwd_finalize_nhwc_k<<<(C + 255) / 256, 256, 0, s>>>(ws, gamma, save_rstd, dgamma, dbeta, coef, C, (double)R);
   GE_LAUNCH_CHECK();
-  if (beta) bn_bwd_apply_nhwc_k<T, true><<<nh_grid_apply(R, rpi), 256, 0, s>>>((const T*)dy, nullptr, (const T*)x, beta, save_mean, save_rstd, coef, (T*)dx, C, R, lpr, rpi, slope);
+  if (npi) bn_bwd_apply_nhwc_k<T, true, true><<<nh_grid_apply(R, rpi), 256, 0, s>>>((const T*)dy, nullptr, (const T*)x, beta, save_mean, save_rstd, coef, (T*)dx, C, R, lpr, rpi, slope, (int)npi, istr);
+  else if (beta) bn_bwd_apply_nhwc_k<T, true><<<nh_grid_apply(R, rpi), 256, 0, s>>>((const T*)dy, nullptr, (const T*)x, beta, save_mean, save_rstd, coef, (T*)dx, C, R, lpr, rpi, slope);
   else bn_bwd_apply_nhwc_k<T, false><<<nh_grid_apply(R, rpi), 256, 0, s>>>((const T*)dy, (const T*)y, (const T*)x, beta, save_mean, save_rstd, coef, (T*)dx, C, R, lpr, rpi, slope);
   GE_LAUNCH_CHECK();
   return GE_OK;
@@ -295,6 +329,26 @@ extern "C" int ge_bn_act_nhwc_bwd(const void* dy, const void* y, const void* x, 
   if (!dy || (!y && !beta) || !x || !gamma || !save_mean || !save_rstd || !dx || !dgamma || !dbeta || !workspace || rows <= 0 || C <= 0) return GE_ERR_BAD_ARG;
   if (dtype == GE_F32) return bn_nhwc_bwd_launch<float>(dy, y, x, gamma, beta, save_mean, save_rstd, dx, dgamma, dbeta, workspace, rows, C, slope, ge_stream(stream));
   if (dtype == GE_BF16) return bn_nhwc_bwd_launch<bf16_t>(dy, y, x, gamma, beta, save_mean, save_rstd, dx, dgamma, dbeta, workspace, rows, C, slope, ge_stream(stream));
+  return GE_ERR_UNSUPPORTED;
+}
+// the same with y / dy as the rows of one level of a longer token matrix (include/gedepth_neck.h)
+static inline bool nh_rows_ok(long rows, long npi, long istr) { return npi > 0 && npi <= NH_WALK_MAX_ROWS && rows % npi == 0 && istr >= npi; }
+extern "C" int ge_bn_act_nhwc_fwd_rows(const void* x, const float* gamma, const float* beta, void* y, long rows_per_image, long image_stride,
+                                       float* save_mean, float* save_rstd, float* running_mean, float* running_var, void* workspace, long rows,
+                                       int C, float eps, float momentum, float slope, int dtype, void* stream) {
+  if (!x || !gamma || !beta || !y || !save_mean || !save_rstd || !workspace || rows <= 0 || C <= 0) return GE_ERR_BAD_ARG;
+  if (!nh_rows_ok(rows, rows_per_image, image_stride)) return GE_ERR_BAD_ARG;
+  if (dtype == GE_F32) return bn_nhwc_fwd_launch<float>(x, gamma, beta, y, save_mean, save_rstd, running_mean, running_var, workspace, rows, C, eps, momentum, slope, ge_stream(stream), rows_per_image, image_stride);
+  if (dtype == GE_BF16) return bn_nhwc_fwd_launch<bf16_t>(x, gamma, beta, y, save_mean, save_rstd, running_mean, running_var, workspace, rows, C, eps, momentum, slope, ge_stream(stream), rows_per_image, image_stride);
+  return GE_ERR_UNSUPPORTED;
+}
+extern "C" int ge_bn_act_nhwc_bwd_rows(const void* dy, long rows_per_image, long image_stride, const void* x, const float* gamma,
+                                       const float* beta, const float* save_mean, const float* save_rstd, void* dx, float* dgamma, float* dbeta,
+                                       void* workspace, long rows, int C, float slope, int dtype, void* stream) {
+  if (!dy || !beta || !x || !gamma || !save_mean || !save_rstd || !dx || !dgamma || !dbeta || !workspace || rows <= 0 || C <= 0) return GE_ERR_BAD_ARG;
+  if (!nh_rows_ok(rows, rows_per_image, image_stride)) return GE_ERR_BAD_ARG;
+  if (dtype == GE_F32) return bn_nhwc_bwd_launch<float>(dy, nullptr, x, gamma, beta, save_mean, save_rstd, dx, dgamma, dbeta, workspace, rows, C, slope, ge_stream(stream), rows_per_image, image_stride);
+  if (dtype == GE_BF16) return bn_nhwc_bwd_launch<bf16_t>(dy, nullptr, x, gamma, beta, save_mean, save_rstd, dx, dgamma, dbeta, workspace, rows, C, slope, ge_stream(stream), rows_per_image, image_stride);
   return GE_ERR_UNSUPPORTED;
 }
 
@@ -733,6 +787,179 @@ extern "C" int ge_colsum(const void* x, long R, int C, float* out, void* workspa
   if (dtype == GE_F32) return colsum_launch<float>(x, R, C, out, workspace, accumulate, ge_stream(stream));
   if (dtype == GE_BF16) return colsum_launch<bf16_t>(x, R, C, out, workspace, accumulate, ge_stream(stream));
   return GE_ERR_UNSUPPORTED;
+}
+
+// ============================================================================ level tokens of the HAHI neck (include/gedepth_neck.h)
+// (B, N, C) token matrices whose N rows are the concatenated levels.  blockIdx.y is the level, so everything that depends on it (first row,
+// row count, embedding row, part pointer) is uniform in a workgroup, and a thread walks its level's rows over all images with NhWalk.
+// The level table travels by value in the kernel arguments: no device table, nothing to upload or to wait for.
+struct NhLevels { int s[GE_NECK_MAX_LEVELS + 1]; };
+struct NhParts { const void* p[GE_NECK_MAX_LEVELS]; long pitch[GE_NECK_MAX_LEVELS]; long col[GE_NECK_MAX_LEVELS]; };
+// checks of a host level table -> NhLevels and the longest level; false: GE_ERR_BAD_ARG
+static bool nh_levels(const long* starts, int n, long N, NhLevels& lv, long& longest) {
+  if (!starts || n < 1 || n > GE_NECK_MAX_LEVELS || N <= 0 || N > NH_WALK_MAX_ROWS || starts[0] != 0 || starts[n] != N) return false;
+  longest = 0;
+  for (int l = 0; l <= GE_NECK_MAX_LEVELS; ++l) lv.s[l] = (int)N;
+  for (int l = 0; l < n; ++l) {
+    if (starts[l + 1] < starts[l]) return false;
+    lv.s[l] = (int)starts[l];
+    if (starts[l + 1] - starts[l] > longest) longest = starts[l + 1] - starts[l];
+  }
+  return true;
+}
+
+// out[b, n, :] = x[b, n, :] + (pos[n, :] + emb[level, :]): the level's embedding row sits in registers
+template <typename T>
+__global__ void __launch_bounds__(256) add_rows_levels_k(const T* __restrict__ x, const float* __restrict__ pos, const float* __restrict__ emb,
+                                                         T* __restrict__ out, int B, long N, int C, NhLevels lv, int lpr, int rpi) {
+  constexpr int VN = V8<T>::N;
+  const int t = threadIdx.x, lane = t % lpr, rs = t / lpr, level = blockIdx.y;
+  const int start = lv.s[level], nl = lv.s[level + 1] - start;
+  if (rs >= rpi || nl <= 0) return;
+  const int c0 = lane * VN;
+  float e[VN];
+#pragma unroll
+  for (int k = 0; k < VN; ++k) e[k] = emb[(long)level * C + c0 + k];
+  const long R = (long)B * nl;
+  NhWalk w(blockIdx.x * rpi + rs, gridDim.x * rpi, nl);
+  for (long r = (long)blockIdx.x * rpi + rs; r < R; r += (long)gridDim.x * rpi, w.next()) {
+    const long o = (w.row(N) + start) * C + c0;
+    const float* q = pos + (long)(start + w.n) * C + c0;
+    float v[VN];
+    V8<T>::ld(x + o, v);
+#pragma unroll
+    for (int k = 0; k < VN; k += 4) {
+      const float4 p4 = *(const float4*)(q + k);
+      v[k] += p4.x + e[k]; v[k + 1] += p4.y + e[k + 1]; v[k + 2] += p4.z + e[k + 2]; v[k + 3] += p4.w + e[k + 3];
+    }
+    V8<T>::st(out + o, v);
+  }
+}
+extern "C" int ge_add_rows_levels(const void* x, const float* pos, const float* emb, void* out, int B, long N, int C, const long* level_starts,
+                                  int n_levels, int dtype, void* stream) {
+  NhLevels lv;
+  long longest;
+  if (!x || !pos || !emb || !out || B <= 0 || C <= 0 || !nh_levels(level_starts, n_levels, N, lv, longest)) return GE_ERR_BAD_ARG;
+  int lpr, rpi;
+  if (dtype != GE_F32 && dtype != GE_BF16) return GE_ERR_UNSUPPORTED;
+  if (!(dtype == GE_F32 ? nh_geom<float>(C, lpr, rpi) : nh_geom<bf16_t>(C, lpr, rpi)) || !nh_aligned(x, pos, out)) return GE_ERR_UNSUPPORTED;
+  const dim3 grid(nh_grid_apply((long)B * longest, rpi), n_levels);
+  hipStream_t s = ge_stream(stream);
+  if (dtype == GE_F32) add_rows_levels_k<float><<<grid, 256, 0, s>>>((const float*)x, pos, emb, (float*)out, B, N, C, lv, lpr, rpi);
+  else add_rows_levels_k<bf16_t><<<grid, 256, 0, s>>>((const bf16_t*)x, pos, emb, (bf16_t*)out, B, N, C, lv, lpr, rpi);
+  GE_LAUNCH_CHECK();
+  return GE_OK;
+}
+
+// column sums per level: colsum_k on the level's rows; partial[(workgroup * L + level) * C + c], so one fold serves all levels
+template <typename T>
+__global__ void __launch_bounds__(256) level_colsum_k(const T* __restrict__ x, float* __restrict__ ws, int B, long N, int C, int L, NhLevels lv,
+                                                      int lpr, int rpi) {
+  constexpr int VN = V8<T>::N;
+  const int t = threadIdx.x, lane = t % lpr, rs = t / lpr, level = blockIdx.y;
+  const int start = lv.s[level], nl = lv.s[level + 1] - start;
+  const int c0 = lane * VN;
+  float acc[1][VN];
+#pragma unroll
+  for (int v = 0; v < VN; ++v) acc[0][v] = 0.f;
+  if (rs < rpi && nl > 0) {
+    const long R = (long)B * nl;
+    NhWalk w(blockIdx.x * rpi + rs, gridDim.x * rpi, nl);
+    for (long r = (long)blockIdx.x * rpi + rs; r < R; r += (long)gridDim.x * rpi, w.next()) {
+      float v[VN];
+      V8<T>::ld(x + (w.row(N) + start) * C + c0, v);
+#pragma unroll
+      for (int k = 0; k < VN; ++k) acc[0][k] += v[k];
+    }
+  }
+  nh_col_commit<1, VN>(acc, ws + (long)level * C, L * C, lpr, rpi, c0);      // row stride L * C: this level's slot of the workgroup's row
+}
+extern "C" int ge_level_colsum(const void* x, int B, long N, int C, const long* level_starts, int n_levels, float* out, void* workspace,
+                               int dtype, void* stream) {
+  NhLevels lv;
+  long longest;
+  if (!x || !out || !workspace || B <= 0 || C <= 0 || !nh_levels(level_starts, n_levels, N, lv, longest)) return GE_ERR_BAD_ARG;
+  int lpr, rpi;
+  if (dtype != GE_F32 && dtype != GE_BF16) return GE_ERR_UNSUPPORTED;
+  if (!(dtype == GE_F32 ? nh_geom<float>(C, lpr, rpi) : nh_geom<bf16_t>(C, lpr, rpi)) || !nh_aligned(x, out)) return GE_ERR_UNSUPPORTED;
+  const unsigned gx = nh_grid_rows((long)B * longest, rpi);
+  float* part = nh_partials(workspace, C, n_levels);
+  hipStream_t s = ge_stream(stream);
+  if (dtype == GE_F32) level_colsum_k<float><<<dim3(gx, n_levels), 256, 0, s>>>((const float*)x, part, B, N, C, n_levels, lv, lpr, rpi);
+  else level_colsum_k<bf16_t><<<dim3(gx, n_levels), 256, 0, s>>>((const bf16_t*)x, part, B, N, C, n_levels, lv, lpr, rpi);
+  GE_LAUNCH_CHECK();
+  nh_partials_reduce_k<float><<<(n_levels * C + 31) / 32, 256, 0, s>>>(part, out, n_levels * C, (int)gx, 0);
+  GE_LAUNCH_CHECK();
+  return GE_OK;
+}
+
+// out = a0 + a1 + a2 + part: every gradient that meets at one token matrix read once, summed in f32, rounded once.  A part is the level's
+// rows inside a wider matrix (the token columns of a channels-last concat gradient), read where it lies.
+template <typename T>
+__global__ void __launch_bounds__(256) token_grad_sum_k(const T* __restrict__ a0, const T* __restrict__ a1, const T* __restrict__ a2,
+                                                        NhParts pt, int has_parts, T* __restrict__ out, int B, long N, int C, NhLevels lv,
+                                                        int lpr, int rpi) {
+  constexpr int VN = V8<T>::N;
+  const int t = threadIdx.x, lane = t % lpr, rs = t / lpr, level = blockIdx.y;
+  const int start = lv.s[level], nl = lv.s[level + 1] - start;
+  if (rs >= rpi || nl <= 0) return;
+  const int c0 = lane * VN;
+  const T* part = has_parts ? (const T*)pt.p[level] + pt.col[level] + c0 : nullptr;
+  const long pitch = has_parts ? pt.pitch[level] : 0;
+  const long R = (long)B * nl;
+  NhWalk w(blockIdx.x * rpi + rs, gridDim.x * rpi, nl);
+  for (long r = (long)blockIdx.x * rpi + rs; r < R; r += (long)gridDim.x * rpi, w.next()) {
+    const long o = (w.row(N) + start) * C + c0;
+    float v[VN], q[VN];
+#pragma unroll
+    for (int k = 0; k < VN; ++k) v[k] = 0.f;
+    if (a0) {
+      V8<T>::ld(a0 + o, v);
+    }
+    if (a1) {
+      V8<T>::ld(a1 + o, q);
+#pragma unroll
+      for (int k = 0; k < VN; ++k) v[k] += q[k];
+    }
+    if (a2) {
+      V8<T>::ld(a2 + o, q);
+#pragma unroll
+      for (int k = 0; k < VN; ++k) v[k] += q[k];
+    }
+    if (part) {
+      V8<T>::ld(part + r * pitch, q);
+#pragma unroll
+      for (int k = 0; k < VN; ++k) v[k] += q[k];
+    }
+    V8<T>::st(out + o, v);
+  }
+}
+extern "C" int ge_token_grad_sum(const void* a0, const void* a1, const void* a2, const void* const* parts, const long* pitch, const long* col,
+                                 const long* level_starts, int n_parts, void* out, int B, long N, int C, int dtype, void* stream) {
+  if (!out || B <= 0 || N <= 0 || C <= 0 || n_parts < 0 || n_parts > GE_NECK_MAX_LEVELS || (!a0 && !a1 && !a2 && !n_parts)) return GE_ERR_BAD_ARG;
+  if (n_parts && (!parts || !pitch || !col)) return GE_ERR_BAD_ARG;
+  const long whole[2] = {0, N};
+  NhLevels lv;
+  NhParts pt = {};
+  long longest;
+  if (!nh_levels(n_parts ? level_starts : whole, n_parts ? n_parts : 1, N, lv, longest)) return GE_ERR_BAD_ARG;
+  if (dtype != GE_F32 && dtype != GE_BF16) return GE_ERR_UNSUPPORTED;
+  const int vn = dtype == GE_F32 ? 4 : 8;
+  bool vec = true;
+  for (int l = 0; l < n_parts; ++l) {
+    const bool empty = lv.s[l + 1] == lv.s[l];
+    if ((!parts[l] && !empty) || col[l] < 0 || col[l] + C > pitch[l]) return GE_ERR_BAD_ARG;
+    vec = vec && pitch[l] % vn == 0 && col[l] % vn == 0 && nh_aligned(parts[l]);
+    pt.p[l] = parts[l]; pt.pitch[l] = pitch[l]; pt.col[l] = col[l];
+  }
+  int lpr, rpi;
+  if (!(dtype == GE_F32 ? nh_geom<float>(C, lpr, rpi) : nh_geom<bf16_t>(C, lpr, rpi)) || !vec || !nh_aligned(a0, a1, a2, out)) return GE_ERR_UNSUPPORTED;
+  const dim3 grid(nh_grid_apply((long)B * longest, rpi), n_parts ? n_parts : 1);
+  hipStream_t s = ge_stream(stream);
+  if (dtype == GE_F32) token_grad_sum_k<float><<<grid, 256, 0, s>>>((const float*)a0, (const float*)a1, (const float*)a2, pt, n_parts > 0, (float*)out, B, N, C, lv, lpr, rpi);
+  else token_grad_sum_k<bf16_t><<<grid, 256, 0, s>>>((const bf16_t*)a0, (const bf16_t*)a1, (const bf16_t*)a2, pt, n_parts > 0, (bf16_t*)out, B, N, C, lv, lpr, rpi);
+  GE_LAUNCH_CHECK();
+  return GE_OK;
 }
 
 // ============================================================================ bias + GELU epilogue of the FFN's first Linear

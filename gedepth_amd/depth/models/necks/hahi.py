@@ -18,6 +18,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .... import kernels as K
+from .... import neck_kernels as NK
 from ....kernels import add_rows, concat_tokens_map, ms_deform_attn_raw, residual_dropout, tokens_from_map
 from ....mmrt import bricks
 from ....mmrt.bricks import BaseModule, ConvModule, build_positional_encoding, xavier_init
@@ -151,6 +152,7 @@ class HAHIHeteroNeck(BaseModule):
         self.multi_att = MultiScaleDeformableAttention(**att)
         self.self_attn = MultiScaleDeformableAttention(**att)
         self._ref_cache = {}
+        self._pos_cache = {}            # sine rows of the concatenated levels, per shape list
         self._order_cache = {}          # cross-attention query order (a speed heuristic): refreshed every ORDER_REFRESH forwards
 
     ORDER_REFRESH = 64
@@ -200,22 +202,59 @@ class HAHIHeteroNeck(BaseModule):
             self._ref_cache[key] = ref
         return self._ref_cache[key]
 
+    def _level_pos_rows(self, shapes, device):
+        """(sum HW, C) fp32: the sine rows of the levels one after the other, WITHOUT the level embedding (input-independent)."""
+        key = (tuple(shapes), str(device))
+        if key not in self._pos_cache:
+            if len(self._pos_cache) >= 8:
+                self._pos_cache.clear()
+            self._pos_cache[key] = torch.cat([self.trans_positional_encoding.grid(h, w, device).flatten(2)[0].t() for h, w in shapes], 0).contiguous()
+        return self._pos_cache[key]
+
+    def _level_tokens(self, feats_trans):
+        """The level-token route (neck_kernels.py): the ``trans_proj`` BatchNorm+ReLU kernels write the (B, sum HW, C) matrix themselves and
+        their backward reads its gradient in place.  -> the matrix, or None with the pre-BN maps when the route does not apply
+        (GE_DISABLE=neck_levels forces that, for A/B runs; GE_DISABLE=neck_fanin keeps the route but sums the gradients the old way)."""
+        if not (self.training and 'neck_levels' not in K.DISABLED and all(ft.is_cuda and K._is_cl(ft) for ft in feats_trans)
+                and self.level_embed.dtype == torch.float32 and len(feats_trans) <= min(self.level_embed.shape[0], NK.MAX_LEVELS)):
+            return None, None
+        slopes = [m._fused_bn_slope() if m.with_norm else None for m in self.trans_proj]
+        if any(s is None for s in slopes):
+            return None, None
+        pre = [m.conv_only(ft) for m, ft in zip(self.trans_proj, feats_trans)]
+        if not (NK.bn_act_levels_ok(pre) and pre[0].shape[1] % 8 == 0):
+            return None, pre
+        return NK.bn_act_levels(pre, [m.norm for m in self.trans_proj], slopes), pre
+
     def forward(self, inputs):
         assert len(inputs) == len(self.in_channels)
         feats = [conv(x) for conv, x in zip(self.lateral_convs, inputs)]
         feat_conv, feats_trans = feats[0], feats[1:]
         bs = feat_conv.shape[0]
         dev = feat_conv.device
-        shapes, srcs, poss = [], [], []
-        for i, ft in enumerate(feats_trans):
-            h, w = ft.shape[2:]
-            shapes.append((h, w))
-            pos = self.trans_positional_encoding.grid(h, w, dev).flatten(2).transpose(1, 2)
-            poss.append(pos + self.level_embed[i].view(1, 1, -1))
-            srcs.append(self.trans_proj[i](ft).flatten(2).transpose(1, 2))
-        src_flatten = torch.cat(srcs, 1)
-        pos_flatten = torch.cat(poss, 1)                      # (1, N, C) fp32: broadcast over the batch inside the add
-        if self.self_att:
+        shapes = [tuple(ft.shape[2:]) for ft in feats_trans]
+        level_rows = [h * w for h, w in shapes]
+        src_flatten, pre = self._level_tokens(feats_trans)
+        levels = src_flatten is not None
+        if not levels:
+            srcs, poss = [], []
+            for i, ft in enumerate(feats_trans):
+                h, w = shapes[i]
+                pos = self.trans_positional_encoding.grid(h, w, dev).flatten(2).transpose(1, 2)
+                poss.append(pos + self.level_embed[i].view(1, 1, -1))
+                srcs.append((self.trans_proj[i](ft) if pre is None else self.trans_proj[i].norm_act(pre[i])).flatten(2).transpose(1, 2))
+            src_flatten = torch.cat(srcs, 1)
+            pos_flatten = torch.cat(poss, 1)                      # (1, N, C) fp32: broadcast over the batch inside the add
+        if self.self_att and levels:
+            # query, value and identity are three aliases of the token matrix: their gradients meet in ONE fp32 sum (two pairwise adds
+            # before); the position add carries the level embedding, whose gradient is one read of the query's gradient
+            q_in, v_in, id_in = NK.fan_out(src_flatten, 3) if 'neck_fanin' not in K.DISABLED else (src_flatten,) * 3
+            ref = self._pixel_centres(shapes, dev).expand(bs, -1, -1, -1)
+            query = NK.add_rows_levels(q_in, self._level_pos_rows(shapes, dev), self.level_embed, level_rows)
+            order = (K.msda_tile_order(shapes, dev) if (os.environ.get('GE_MSDA_MM_SELF') == '1' and src_flatten.dtype == torch.bfloat16) else None)
+            src = self.self_attn(query, value=v_in, identity=id_in, query_pos=None, reference_points=ref, spatial_shapes=shapes,
+                                 query_shapes=shapes, query_order=order)
+        elif self.self_att:
             ref = self._pixel_centres(shapes, dev).expand(bs, -1, -1, -1)
             # The MFMA decomposition (csrc/msda_mm.hip) on 4 x 8 patches of the token maps is available for the self-attention too
             # (GE_MSDA_MM_SELF=1) but measured SLOWER than the LDS-window gather kernels here: the offset bias spreads the 8 points of a
@@ -228,6 +267,14 @@ class HAHIHeteroNeck(BaseModule):
         else:
             src = src_flatten
 
+        if levels and 'neck_fanin' not in K.DISABLED and src.dtype in (torch.float32, torch.bfloat16):
+            # the cross-attention's value and the three trans_fusion pieces alias `src`: the value's gradient and the token columns of the
+            # three concat gradients, read where they lie, are summed in one pass (split's backward cat and an add_ before)
+            src_value, *pieces = NK.fan_out_levels(src, level_rows)
+        else:
+            # one split (backward: ONE concatenating write of the level gradients) instead of per-level slices, whose backward
+            # zero-fills a full (B, sum HW, C) tensor per level and adds the three of them
+            src_value, pieces = src, torch.split(src, level_rows, dim=1)
         h, w = feat_conv.shape[2:]
         pos_map = self.conv_positional_encoding.grid(h, w, dev) if self.cross_att else None      # (1, C, h, w) fp32, cached
         query = None
@@ -247,13 +294,11 @@ class HAHIHeteroNeck(BaseModule):
                 ref = torch.stack((torch.mv(pm.t(), w[0]), torch.mv(pm.t(), w[1])), -1).add(b).sigmoid()[None]
             order = self._cross_order(ref[0], shapes[0]) if (conv_skip.is_cuda and src.dtype == torch.bfloat16) else None
             ref = ref[:, :, None, :].expand(bs, -1, len(shapes), 2)
-            fused = self.multi_att.forward_map(conv_skip, pos_map, src, ref, shapes, concat_with=feat_conv, query_order=order, query=query)
+            fused = self.multi_att.forward_map(conv_skip, pos_map, src_value, ref, shapes, concat_with=feat_conv, query_order=order, query=query)
         else:
             fused = torch.cat([conv_skip, feat_conv], dim=1)
-        # one split (backward: ONE concatenating write of the level gradients) instead of per-level slices, whose backward
-        # zero-fills a full (B, sum HW, C) tensor per level and adds the three of them
         outs = [self.conv_fusion(fused)]
-        for i, (ft, piece) in enumerate(zip(feats_trans, torch.split(src, [h * w for h, w in shapes], dim=1))):
+        for i, (ft, piece) in enumerate(zip(feats_trans, pieces)):
             outs.append(self.trans_fusion[i](concat_tokens_map(piece, ft, tokens_first=False)))
         return tuple(outs)
 

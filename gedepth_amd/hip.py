@@ -11,7 +11,8 @@ five.  ``EXTRA_HEADERS`` is a second table of headers, parsed by the same loop: 
 KITTI front end, merge and metric sums; its ``GeBatchFrame`` struct is mirrored in gedepth_amd/batch_kernels.py).  ``SCENE_HEADERS`` is a
 third: ``SCENE_SIGNATURES`` for include/gedepth_scene.h (the scene clouds; its ``GeSceneLayer`` struct is mirrored in
 gedepth_amd/scene_kernels.py).  ``STRATA_HEADERS`` is a fourth: ``STRATA_SIGNATURES`` for include/gedepth_strata.h (the stratified
-metric sums, wrapped in gedepth_amd/strata_kernels.py).  ``lib()`` binds the entry points of all four tables.
+metric sums, wrapped in gedepth_amd/strata_kernels.py).  ``NECK_HEADERS`` is a fifth: ``NECK_SIGNATURES`` for include/gedepth_neck.h (the HAHI
+neck's level-token kernels, wrapped in gedepth_amd/neck_kernels.py).  ``lib()`` binds the entry points of all five tables.
 
 There is deliberately NO fallback: if the shared library is missing, or a tensor is not a
 contiguous CUDA(HIP) tensor of the expected dtype, the call raises.  Build the library with
@@ -30,6 +31,7 @@ HEADERS = {'SIGNATURES': 'gedepth_hip.h', 'EVAL_SIGNATURES': 'gedepth_eval.h', '
 EXTRA_HEADERS = {'BATCH_SIGNATURES': 'gedepth_batch.h'}      # headers added after the five: same parsing, same binding
 SCENE_HEADERS = {'SCENE_SIGNATURES': 'gedepth_scene.h'}      # and after those
 STRATA_HEADERS = {'STRATA_SIGNATURES': 'gedepth_strata.h'}   # and after those
+NECK_HEADERS = {'NECK_SIGNATURES': 'gedepth_neck.h'}         # and after those
 GE_F32, GE_BF16 = 0, 1
 GE_COLORIZE_VMIN_DATA, GE_COLORIZE_VMAX_DATA, GE_COLORIZE_EQUAL = 1, 2, 4      # ge_depth_colorize flags
 
@@ -61,7 +63,7 @@ def parse_header(text):
     return sigs
 
 
-for _table, _header in {**HEADERS, **EXTRA_HEADERS, **SCENE_HEADERS, **STRATA_HEADERS}.items():          # SIGNATURES, EVAL_SIGNATURES, ...: name -> (restype, argtypes)
+for _table, _header in {**HEADERS, **EXTRA_HEADERS, **SCENE_HEADERS, **STRATA_HEADERS, **NECK_HEADERS}.items():          # SIGNATURES, EVAL_SIGNATURES, ...: name -> (restype, argtypes)
     with open(os.path.join(os.path.dirname(_HERE), 'include', _header)) as _fh:
         globals()[_table] = parse_header(_fh.read())
 
@@ -81,7 +83,7 @@ def lib():
                 f'{LIB_PATH} is missing: the gfx950 HIP kernels are not built. '
                 f'Run gedepth_amd/csrc/build.sh (hipcc --offload-arch=gfx950). There is no CPU/eager fallback.')
         handle = ctypes.CDLL(LIB_PATH)
-        for table in (*HEADERS, *EXTRA_HEADERS, *SCENE_HEADERS, *STRATA_HEADERS):
+        for table in (*HEADERS, *EXTRA_HEADERS, *SCENE_HEADERS, *STRATA_HEADERS, *NECK_HEADERS):
             for name, (res, args) in globals()[table].items():
                 fn = getattr(handle, name)   # AttributeError here == ABI mismatch: fail loudly
                 fn.restype, fn.argtypes = res, args

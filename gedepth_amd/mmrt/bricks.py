@@ -454,18 +454,23 @@ class ConvModule(nn.Module):
             return float(self.activate.negative_slope)
         return None
 
+    def conv_only(self, x):
+        """The convolution of ``forward`` without norm and activation (a caller that fuses those itself, e.g. the HAHI neck's level tokens)."""
+        if x.is_cuda and self.conv.bias is None:
+            from .. import kernels
+            if kernels.conv3x3_ok(self.conv, x):              # hand-written MFMA implicit GEMM (forward + data gradient)
+                return kernels.conv3x3(self.conv, x)
+            return kernels.conv_lib(self.conv, x)             # library convolution, weight from the bf16 shadow arena
+        return self.conv(x)
+
     def forward(self, x):
         slope = self._fused_slope() if x.is_cuda else None
         if slope is not None:
             return conv_bias_act(self.conv, x, slope)
-        if x.is_cuda and self.conv.bias is None:
-            from .. import kernels
-            if kernels.conv3x3_ok(self.conv, x):              # hand-written MFMA implicit GEMM (forward + data gradient)
-                x = kernels.conv3x3(self.conv, x)
-            else:
-                x = kernels.conv_lib(self.conv, x)            # library convolution, weight from the bf16 shadow arena
-        else:
-            x = self.conv(x)
+        return self.norm_act(self.conv_only(x))
+
+    def norm_act(self, x):
+        """Norm and activation of ``forward`` on the convolution's output."""
         if x.is_cuda and self.with_norm and x.dtype in (torch.float32, torch.bfloat16):
             slope = self._fused_bn_slope()
             if slope is not None:                       # training-mode BatchNorm2d (+ ReLU): the fused HIP kernels
