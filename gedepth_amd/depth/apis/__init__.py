@@ -1,3 +1,4 @@
-from .inference import inference_depther, inference_ground, inference_point_cloud, inference_scene_cloud, init_depther
+from .inference import (inference_depther, inference_error_map, inference_ground, inference_point_cloud, inference_scene_cloud,
+                        init_depther)
 
-__all__ = ['init_depther', 'inference_depther', 'inference_point_cloud', 'inference_ground', 'inference_scene_cloud']
+__all__ = ['init_depther', 'inference_depther', 'inference_point_cloud', 'inference_ground', 'inference_scene_cloud', 'inference_error_map']

@@ -101,10 +101,10 @@ class BatchDepthInferencer(DepthInferencer):
             self.static_out.copy_(pred)
 
     def _single(self, *a, **kw):
-        raise NotImplementedError('a BatchDepthInferencer runs batch(imgs); single frames, points, scene_points and ground_maps go through the '
+        raise NotImplementedError('a BatchDepthInferencer runs batch(imgs); single frames, points, scene_points, error_map and ground_maps go through the '
                                   'DepthInferencer of engine_for(model, bf16)')
 
-    __call__ = ground_maps = points = scene_points = _single
+    __call__ = ground_maps = points = scene_points = error_map = _single
 
     def batch(self, imgs, pes=None, calib=None, cam_height=1.65, graph=True, to_host=True, paths=None):
         """n <= F frames -> their maps.  ``imgs``: paths, (H, W, 3) uint8 BGR arrays, or frames already decoded by ``decode_ahead`` (then
@@ -131,6 +131,7 @@ class BatchDepthInferencer(DepthInferencer):
             devs = [up(b, self.device) for up, b in zip(self._stagings, bgrs)]
             K.infer_front_batch(devs, raws, self.static_in, tops, lefts, s['mean'], s['std'], s['views'], s['to_rgb'], s['pe_max'],
                                 s['depth_scale'])
+            self.last_frames = list(zip(devs, tops, lefts))   # kept for the error images, as last_frame is
             self._run(self._key(), graph, lambda: self._body(metas))
             self.last_n = n
             if to_host:
@@ -145,6 +146,7 @@ class BatchDepthInferencer(DepthInferencer):
         super().reset()
         self.last_n = 0                              # the frame count of the last batch
         self.last_ground_depths = None               # the raw (H, W) f32 ground depths the last batch's front end was given
+        self.last_frames = None                      # [(device uint8 BGR frame, top, left)] of the last batch, for the error images
 
     def run(self, imgs, pes=None, calib=None, cam_height=1.65, graph=True):
         """Any number of frames, in batches of F with the next batch decoding ahead -> one host map per frame, in order."""

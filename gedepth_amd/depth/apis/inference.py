@@ -36,7 +36,7 @@ from ..datasets.pipelines import loading    # _DDAD_CAMERA_HEIGHT is read throug
 from ..models import build_depther
 from ..utils.pinned import PinnedUpload
 
-__all__ = ['init_depther', 'inference_depther', 'inference_point_cloud', 'inference_ground', 'inference_scene_cloud', 'DepthInferencer',
+__all__ = ['init_depther', 'inference_depther', 'inference_point_cloud', 'inference_ground', 'inference_scene_cloud', 'inference_error_map', 'DepthInferencer',
            'kitti_front_spec', 'ddad_front_spec', 'front_spec', 'SCENE_LAYERS']
 
 # test-time transforms of MultiScaleFlipAug the device front end restates (ImageToTensor / Collect are layout only)
@@ -508,6 +508,43 @@ class DepthInferencer:
         cur.wait_stream(self.stream)
         return out
 
+    def error_map(self, img, gt, tau=0.05, radius=1, background=1, pe=None, calib=None, cam_height=1.65, graph=True, to_host=True, rect=None):
+        """One frame and its ground truth -> ``(image (352, 1216, 3) uint8 BGR, err (352, 1216) float32)``: every LiDAR return painted
+        with the band of its abs-rel error over the frame's own pixels, and the error plane itself (include/gedepth_error.h;
+        ``kernels.error_image``).  ``gt``: a 16-bit PNG path or an (H, W) uint16 array of the frame's size, uploaded as ``scene_points``
+        uploads it; ``tau`` in (0, 1]: the abs-rel error of the middle threshold (0.05: red from 5 %); ``radius`` 0 .. 3: a return is
+        drawn (2 radius + 1) pixels wide, the worst return winning; ``background``: 0 the frame, 1 the frame halved, 2 black;
+        ``rect=(r0, r1, c0, c1)``: the rows and columns of the crop whose returns count (None: all of it).  The depth limits are the decode
+        head's, the ground truth is divided by 256.  The frame runs as in ``__call__`` with ``to_host=False`` (its capture and key);
+        ``ge_error_image`` then reads ``static_out``, the frame uploaded for this call and its KB-crop offsets on ``self.stream``, outside
+        the captured graph.  ``to_host=False``: device tensors, without synchronising."""
+        if self.ddad:
+            raise NotImplementedError('error_map on a DDAD engine: the DDAD ground truth is a float map at another resolution and DDADResize '
+                                      'leaves no uint8 frame at the map\'s size; the error images are built for the KITTI protocol')
+        from ...error_kernels import error_image, paint_args
+        tau, radius, background = paint_args(tau, radius, background)           # every argument error before any device work
+        s = self.spec
+        rect = (0, s['height'], 0, s['width']) if rect is None else tuple(int(v) for v in rect)
+        if len(rect) != 4 or not (0 <= rect[0] <= s['height'] and 0 <= rect[1] <= s['height'] and 0 <= rect[2] <= s['width']
+                                  and 0 <= rect[3] <= s['width']):
+            raise ValueError(f'rect {rect} is not (r0, r1, c0, c1) inside the {(s["height"], s["width"])} crop')
+        bgr = _decode(img)
+        H, W = bgr.shape[:2]
+        self.front.frame(self, H, W, None, None)
+        raw_gt = _scene_gt(gt, H, W)
+        head = self.model.decode_head
+        self._frame(img, pe, calib, cam_height, graph, False, None, False, bgr)
+        dev, top, left = self.last_frame
+        cur = torch.cuda.current_stream(self.device)
+        with torch.cuda.stream(self.stream):
+            self.last_gt = self._gt_staging(raw_gt, self.device)
+            out, err = error_image(self.static_out[0], self.last_gt, dev, top, left, rect, 256.0, float(head.min_depth), float(head.max_depth),
+                                   tau, radius, background)
+            if to_host:
+                out, err = out.cpu().numpy(), err.cpu().numpy()
+        cur.wait_stream(self.stream)
+        return out, err
+
 
 SCENE_LAYERS = ('prediction', 'ground', 'gt', 'adjusted')          # the reference's concatenation order
 _SCENE_COLOURS = {'prediction': None, 'ground': (255, 0, 0), 'gt': (0, 255, 0), 'adjusted': (0, 0, 255)}
@@ -699,3 +736,44 @@ def inference_scene_cloud(model, img, gt=None, layers=None, out_file=None, pe=No
             write_scene_ply(o, pts, counts)
         clouds.append((pts, counts))
     return clouds
+
+
+def inference_error_map(model, img, gt, out_file=None, tau=0.05, radius=1, background=1, pe=None, calib=None, cam_height=1.65, bf16=False,
+                        graph=True, rect=None):
+    """The error image of each frame of ``img`` (a path, an (H, W, 3) uint8 BGR array, or a list of these) against its ground truth
+    ``gt`` (a 16-bit PNG path or an (H, W) uint16 array; a list: one per frame): a list with one ``(image, err)`` per frame, from
+    ``DepthInferencer.error_map`` — ``image`` (352, 1216, 3) uint8 BGR, every LiDAR return in the colour of its abs-rel error's band over
+    the frame's pixels, ``err`` (352, 1216) float32, the error at the returns and -1 elsewhere.  ``tau``, ``radius``, ``background`` and
+    ``rect`` as there; frames, ground depth, ``bf16`` and ``graph`` as in ``inference_depther``.  ``out_file`` (a path, or a list with one
+    per frame): the pictures are written too.  Every argument error is raised for the whole list before any device work.  A DDAD config
+    raises ``NotImplementedError``."""
+    from ...error_kernels import paint_args
+    from ..models.depther.base import _imwrite_bgr
+    from .batch_inference import frame_size
+    imgs = img if isinstance(img, list) else [img]
+    if gt is None:
+        raise ValueError('inference_error_map needs gt= (a 16-bit PNG path or an (H, W) uint16 array per frame)')
+    pes = _per_frame(pe, len(imgs), '{n} ground-depth maps for {m} frames')
+    gts = _per_frame(gt, len(imgs), '{n} ground truths for {m} frames')
+    outs = _per_frame(out_file if out_file is None or isinstance(out_file, list) else [out_file], len(imgs),
+                      'out_file must be a list with one path per frame ({m} frames)')
+    spec, prefix = config = _config_of(model)                                 # argument errors before any device work
+    if spec['protocol'] == 'ddad':
+        raise NotImplementedError('inference_error_map with a DDAD config: the error images are built for the KITTI protocol (a uint16 '
+                                  'ground truth and a uint8 frame in the KB-crop window)')
+    paint_args(tau, radius, background)
+    if calib is None and any(p is None and _pe_file(spec, prefix, i) is None for i, p in zip(imgs, pes)):
+        raise ValueError(_NO_PE)
+    for i, g in zip(imgs, gts):
+        H, W = frame_size(i)
+        if H < spec['height'] or W < spec['width']:
+            raise ValueError(f'frame {(H, W)} is smaller than the KB crop {(spec["height"], spec["width"])}')
+        _scene_gt(g, H, W, load=False)
+    eng = engine_for(model, bf16, config)
+    results = []
+    for i, g, p, o in zip(imgs, gts, pes, outs):
+        picture, err = eng.error_map(i, g, tau, radius, background, p, calib, cam_height, graph, rect=rect)
+        if o is not None:
+            _imwrite_bgr(picture, o)
+        results.append((picture, err))
+    return results

@@ -18,6 +18,14 @@ ten sums per distance bin and on / off ground class (include/gedepth_strata.h), 
 (``last_ground_depth`` / ``last_ground_depths``).  Both buffers come back in the loop's one synchronisation and the loop returns
 ``(results, rows)``, ``rows`` (N, S, 10) float64; ``dataset.evaluate_strata`` prints the table.  Speed: README "Where the error is".
 
+``errors=ErrorMaps(...)`` (with ``device_eval``; KITTI protocol, any ``eval_batch``, also with ``strata`` and ``ground_dir``) shows where in
+the picture the error is (include/gedepth_error.h): behind the metric call, on the same upload of the ground truth, one
+``ge_error_accumulate[_batch]`` call adds every return's abs-rel error into a per-pixel float64 sum and uint32 count held by ``errors``,
+and with ``errors.out_dir`` one ``ge_error_image[_batch]`` call paints the batch's error pictures over the frames the front end was fed
+(``last_frame`` / ``last_frames``).  A batch's pictures reach the host in one copy and are encoded on a thread pool while the next batch
+computes; the planes come back in the loop's one synchronisation.  The loop returns what it returns without ``errors``.  Speed: README
+"Where in the image the error is".
+
 ``ground_dir`` writes every image's ground maps (``DepthInferencer.ground_maps`` -> ``show_ground``: attention, slope and ground-depth
 pictures, or one ``.npz`` under ``format_only``).  The maps exist on the engine's route only, so the frames go through the engine: alone
 (no result list), or in the same pass as ``device_eval``; with the host loop's ``pre_eval`` it raises.  Speed: not measured.
@@ -148,10 +156,72 @@ def _scene_only(model, data_loader, scene_dir):
     return []
 
 
-def _device_eval_batches(dataset, eng, indices, frames, sums, size, graph, strata=None, rows=None):
+class _ErrorPictures:
+    """The error pictures' way from the device to ``out_dir``: per batch ONE copy of its pictures into a pinned host buffer on
+    the engine's stream, with an event; when the loop has queued the next batch's device work, ``flush`` waits for the event (long
+    reached), takes the pictures out of the pinned buffer — which is free for the next copy from then on — and hands their PNG encoding
+    to a pool of ``DECODE_WORKERS`` threads, which runs while the device computes.  ``close`` writes the last batch and raises what an encoding raised."""
+
+    def __init__(self, slots, device):
+        from concurrent.futures import ThreadPoolExecutor
+        from .batch_inference import DECODE_WORKERS
+        self.device = device
+        self.dev = torch.empty(slots, 352, 1216, 3, device=device, dtype=torch.uint8)          # what ge_error_image[_batch] writes
+        self.host = torch.empty(slots, 352, 1216, 3, dtype=torch.uint8, pin_memory=True)
+        # DECODE_WORKERS threads whatever the batch size: one picture takes longer to encode than one frame to compute, and the pictures
+        # queue up behind the loop (at most MAX_QUEUED of them: then the loop waits for the oldest)
+        self.pool = ThreadPoolExecutor(max_workers=DECODE_WORKERS)
+        self.pending, self.futures = None, []
+
+    MAX_QUEUED = 32
+
+    def copy(self, n, files):
+        """Queue the copy of the first ``n`` pictures of ``self.dev`` on the current stream; ``files``: where they go."""
+        self.flush()                                                       # the last batch has left the pinned buffer
+        self.host[:n].copy_(self.dev[:n], non_blocking=True)
+        done = torch.cuda.Event()
+        done.record()
+        self.pending = (n, list(files), done)
+
+    def flush(self):
+        from ..models.depther.base import _imwrite_bgr
+        if self.pending is None:
+            return
+        n, files, done = self.pending
+        self.pending = None
+        done.synchronize()
+        pictures = self.host[:n].numpy().copy()                            # the pinned buffer is the next batch's again
+        while len(self.futures) + n > self.MAX_QUEUED:
+            self.futures.pop(0).result()                                   # raises what the encoding raised
+        self.futures += [self.pool.submit(_imwrite_bgr, pictures[k], files[k]) for k in range(n)]
+
+    def close(self):
+        try:
+            self.flush()
+            for f in self.futures:
+                f.result()
+        finally:
+            self.pool.shutdown(wait=True)
+
+
+def _unpadded(n, total, rank, world):
+    """How many of a rank's ``n`` sampler indices are the split's own: a non-shuffled DistributedSampler deals the indices round-robin
+    (position ``k * world + rank`` for the rank's k-th) and pads the last round with the split's first entries when ``total % world != 0``;
+    the positions from ``total`` on are that padding.  ``interleave_shards`` cuts it off the results; the error planes must never see it."""
+    return sum(1 for k in range(n) if k * world + rank < total)
+
+
+def _error_file(dataset, index, out_dir):
+    """``out_dir/replace_str(<the image's name in the split>)``."""
+    return osp.join(out_dir, replace_str(dataset.img_infos[index]['filename']))
+
+
+def _device_eval_batches(dataset, eng, indices, frames, sums, size, graph, strata=None, rows=None, errors=None, pictures=None, real=None):
     """``_device_eval``'s frames in batches of ``size``: the pool decodes the next batch's image and ground-truth PNGs while the batched
     engine and ``pre_eval_device_batch`` work on the current one; batch k fills rows ``k * size ..`` of ``sums`` (and, with ``strata``, of
-    ``rows``, from the same uploads and the ground depths the batch's front end was fed)."""
+    ``rows``, from the same uploads and the ground depths the batch's front end was fed; with ``errors``, the planes and pictures of
+    ``pre_eval_device_errors_batch``, from the same uploads and the frames the batch's front end was fed; only the first ``real``
+    frames of the loop enter the planes and get a picture)."""
     from .batch_inference import decode_ahead
     from .inference import _decode
     jobs = [(lambda i=i, f=f: (_decode(f['img']), dataset.gt_raw(i))) for i, f in zip(indices, frames)]
@@ -160,7 +230,15 @@ def _device_eval_batches(dataset, eng, indices, frames, sums, size, graph, strat
         n = len(decoded)
         preds = eng.batch([d[0] for d in decoded], graph=graph, to_host=False, paths=[f['img'] for f in frames[row:row + n]])
         with torch.cuda.stream(eng.stream):
-            if strata is None:
+            if errors is not None:
+                ground = strata is not None and _strata_ground(eng, strata, True)
+                dataset.pre_eval_device_errors_batch(preds, indices[row:row + n], errors, eng.last_frames, pictures and pictures.dev,
+                                                     raws=[d[1] for d in decoded], sums_rows=sums[row:row + n], strata=strata,
+                                                     rows=None if strata is None else rows[row:row + n], grounds=ground or None,
+                                                     count=min(max(real - row, 0), n))
+                if pictures and real > row:
+                    pictures.copy(min(real - row, n), [_error_file(dataset, i, errors.out_dir) for i in indices[row:min(real, row + n)]])
+            elif strata is None:
                 dataset.pre_eval_device_batch(preds, indices[row:row + n], sums[row:row + n], raws=[d[1] for d in decoded])
             else:
                 dataset.pre_eval_device_strata_batch(preds, indices[row:row + n], rows[row:row + n], strata, _strata_ground(eng, strata, True),
@@ -179,12 +257,14 @@ def _strata_ground(eng, strata, batched=False):
 
 
 def _device_eval(model, data_loader, pre_eval, format_only, show, out_dir, ply_dir=None, ground_dir=None, eval_batch=1, engine_graph=True,
-                 strata=None):
+                 strata=None, errors=None):
     """The ``device_eval`` loop of ``single_gpu_test``: the list of metric tuples ``pre_eval`` yields, in the sampler's order.
     ``eval_batch=F > 1``: the sampler's indices in batches of F through the batched engine and ``pre_eval_device_batch``, image and
     ground-truth PNGs of the next batch decoding ahead; same rows of the same buffer, same one copy at the end.  ``strata`` (a
     ``core.StrataSpec``): every image's sums per stratum as well, into an (N, S, 10) buffer that comes back in the same synchronisation;
-    the result is ``(the list, rows)``."""
+    the result is ``(the list, rows)``.  ``errors`` (a ``core.ErrorMaps``): every image also goes into its error planes and, with its
+    ``out_dir``, into an error picture (``pre_eval_device_errors[_batch]``, which then makes the metric and strata calls itself, on the
+    same upload); the planes come back in the same synchronisation and the result is unchanged."""
     from ..core.evaluation import metrics_from_sums
     dataset = data_loader.dataset
     if not pre_eval or format_only:
@@ -196,27 +276,47 @@ def _device_eval(model, data_loader, pre_eval, format_only, show, out_dir, ply_d
     depther, eng, indices, frames = _engine_frames(model, data_loader, 'device_eval', batch=eval_batch)
     sums = torch.empty(max(len(indices), 1), 10, device=eng.device, dtype=torch.float64)
     rows = None if strata is None else torch.empty(max(len(indices), 1), strata.count, 10, device=eng.device, dtype=torch.float64)
-    if eval_batch != 1:
-        _device_eval_batches(dataset, eng, indices, frames, sums, eval_batch, engine_graph, strata, rows)
-    else:
-        for row, (i, frame) in enumerate(zip(indices, frames)):
-            if ground_dir:
-                maps = eng.ground_maps(to_host=False, graph=engine_graph, **frame)
-                pred = maps['depth']
-            else:
-                pred = eng(to_host=False, graph=engine_graph, **frame)
-            with torch.cuda.stream(eng.stream):
-                if strata is None:
-                    dataset.pre_eval_device(pred, i, sums[row])
+    pictures, real = None, len(indices)
+    if errors is not None:
+        rank, world = get_dist_info()
+        real = _unpadded(len(indices), len(dataset), rank, world)      # a padded shard's last frame is the split's first again: keep it out
+        errors.begin(eng.device, dataset.eval_rect(352, 1216))
+        pictures = _ErrorPictures(eval_batch, eng.device) if errors.out_dir else None
+    try:
+        if eval_batch != 1:
+            _device_eval_batches(dataset, eng, indices, frames, sums, eval_batch, engine_graph, strata, rows, errors, pictures, real)
+        else:
+            for row, (i, frame) in enumerate(zip(indices, frames)):
+                if ground_dir:
+                    maps = eng.ground_maps(to_host=False, graph=engine_graph, **frame)
+                    pred = maps['depth']
                 else:
-                    dataset.pre_eval_device_strata(pred, i, rows[row], strata, _strata_ground(eng, strata), sums_row=sums[row])
-            if ground_dir:
-                depther.show_ground(maps, _ground_file(dataset, i, ground_dir))
+                    pred = eng(to_host=False, graph=engine_graph, **frame)
+                with torch.cuda.stream(eng.stream):
+                    if errors is not None and row < real:
+                        dataset.pre_eval_device_errors(pred, i, errors, eng.last_frame, pictures and pictures.dev[0], sums_row=sums[row],
+                                                       strata=strata, rows=None if strata is None else rows[row],
+                                                       ground=None if strata is None else _strata_ground(eng, strata))
+                        if pictures:
+                            pictures.copy(1, [_error_file(dataset, i, errors.out_dir)])
+                    elif strata is None:
+                        dataset.pre_eval_device(pred, i, sums[row])
+                    else:
+                        dataset.pre_eval_device_strata(pred, i, rows[row], strata, _strata_ground(eng, strata), sums_row=sums[row])
+                if ground_dir:
+                    depther.show_ground(maps, _ground_file(dataset, i, ground_dir))
+    finally:
+        if pictures:
+            pictures.close()
     with torch.cuda.stream(eng.stream):
         if strata is not None:
             host_rows = torch.empty(len(indices), strata.count, 10, dtype=torch.float64, pin_memory=True)
             host_rows.copy_(rows[:len(indices)], non_blocking=True)    # ordered before the copy below on the same stream
+        if errors is not None:
+            errors.download()                                          # the planes: ordered before the copy below, too
         host = sums[:len(indices)].cpu().numpy()                       # the one copy (and the one synchronisation) of the loop
+    if errors is not None:
+        errors.finish()
     torch.cuda.current_stream(eng.device).wait_stream(eng.stream)
     results = [metrics_from_sums(r) for r in host]
     return results if strata is None else (results, host_rows.numpy().copy())
@@ -224,7 +324,7 @@ def _device_eval(model, data_loader, pre_eval, format_only, show, out_dir, ply_d
 
 def single_gpu_test(model, data_loader, pre_eval=False, format_only=False, format_args=None, device=None, *, show=False,
                     out_dir=None, device_eval=False, ply_dir=None, ground_dir=None, eval_batch=1, engine_graph=True, scene_dir=None,
-                    strata=None):
+                    strata=None, errors=None):
     """Returns a list with one entry per image: the metric tuple (``pre_eval``) or the ``(1, H, W)`` depth map.  ``show`` / ``out_dir``:
     ``show_result`` of every image's map, written to ``out_dir/replace_str(ori_filename)`` (``format_only``: the raw map as
     ``out_dir/<ori_filename without extension>.npy``).  ``ply_dir``: every image's point cloud as ``ply_dir/<ori_filename with .ply>``
@@ -235,8 +335,19 @@ def single_gpu_test(model, data_loader, pre_eval=False, format_only=False, forma
     protocol; alone): every image's scene cloud as ``scene_dir/<ori_filename with .ply>`` (module docstring); the result is an empty list.
     ``strata`` (a ``core.StrataSpec``; with ``device_eval``, KITTI protocol, any ``eval_batch``): the loop also reduces every map to its
     metric sums per distance bin and on / off ground class (include/gedepth_strata.h) and returns ``(results, rows)``: ``results`` the list
-    it returns without ``strata``, ``rows`` an (N, S, 10) float64 array in the same order (``dataset.evaluate_strata`` prints its table)."""
+    it returns without ``strata``, ``rows`` an (N, S, 10) float64 array in the same order (``dataset.evaluate_strata`` prints its table).
+    ``errors`` (a ``core.ErrorMaps``; with ``device_eval``, KITTI protocol, any ``eval_batch``, also with ``strata`` and ``ground_dir``): the
+    loop also adds every LiDAR return's abs-rel error into the per-pixel planes of ``errors`` and, with ``errors.out_dir``, writes every
+    image's error picture to ``out_dir/replace_str(<name in the split>)`` (include/gedepth_error.h); the result is what the loop returns
+    without ``errors``."""
     model.eval()
+    if errors is not None:
+        if not device_eval:
+            raise NotImplementedError('errors: the error maps are reduced by the device evaluation loop: it needs device_eval=True (the host '
+                                      'loop is not covered)')
+        if getattr(data_loader.dataset, 'device_protocol', None) != 'kitti':
+            raise NotImplementedError(f'errors: {type(data_loader.dataset).__name__} is not evaluated by the KITTI protocol (the error maps need '
+                                      'its uint16 ground truth and its uint8 frame in the KB-crop window; the DDAD protocol is not covered)')
     if strata is not None:
         if not device_eval:
             raise NotImplementedError('strata are reduced by the device evaluation loop: it needs device_eval=True (the host loop is not covered)')
@@ -244,14 +355,15 @@ def single_gpu_test(model, data_loader, pre_eval=False, format_only=False, forma
             raise NotImplementedError(f'strata: {type(data_loader.dataset).__name__} is not evaluated by the KITTI protocol (the DDAD protocol\'s '
                                       'ge_depth_metrics_resized has no stratified form)')
     if scene_dir:
-        if pre_eval or format_only or show or out_dir or ply_dir or ground_dir or device_eval:
-            raise NotImplementedError('scene_dir with pre_eval / format_only / show / out_dir / ply_dir / ground_dir / device_eval: the scene '
+        if pre_eval or format_only or show or out_dir or ply_dir or ground_dir or device_eval or errors is not None:
+            raise NotImplementedError('scene_dir with pre_eval / format_only / show / out_dir / ply_dir / ground_dir / device_eval / errors: the scene '
                                       'clouds come from an engine loop of their own that returns no results; run them apart')
         return _scene_only(model, data_loader, scene_dir)
     if eval_batch != 1 and not device_eval:
         raise NotImplementedError('eval_batch > 1 batches the device evaluation loop: it needs device_eval=True')
     if device_eval:
-        return _device_eval(model, data_loader, pre_eval, format_only, show, out_dir, ply_dir, ground_dir, eval_batch, engine_graph, strata)
+        return _device_eval(model, data_loader, pre_eval, format_only, show, out_dir, ply_dir, ground_dir, eval_batch, engine_graph, strata,
+                            errors)
     if ground_dir:
         if pre_eval:
             raise NotImplementedError('ground_dir with the host loop\'s pre_eval: the ground maps exist on the engine\'s route only; '
@@ -283,16 +395,26 @@ def single_gpu_test(model, data_loader, pre_eval=False, format_only=False, forma
 
 
 def multi_gpu_test(model, data_loader, pre_eval=False, format_only=False, format_args=None, device=None, *, show=False, out_dir=None,
-                   device_eval=False, ply_dir=None, ground_dir=None, eval_batch=1, engine_graph=True, scene_dir=None, strata=None):
+                   device_eval=False, ply_dir=None, ground_dir=None, eval_batch=1, engine_graph=True, scene_dir=None, strata=None,
+                   errors=None):
     """Each rank evaluates its shard of a non-shuffled DistributedSampler; rank 0 receives the results in dataset order.  ``show`` /
     ``out_dir`` / ``ply_dir`` / ``ground_dir`` / ``scene_dir`` / ``device_eval`` / ``eval_batch`` / ``engine_graph`` / ``strata`` as in
-    ``single_gpu_test``: every rank writes the files of its own shard; with ``strata`` rank 0 receives ``(results, rows)``."""
+    ``single_gpu_test``: every rank writes the files of its own shard; with ``strata`` rank 0 receives ``(results, rows)``.  ``errors``:
+    every rank writes its shard's pictures, and rank 0's ``errors`` receives the planes of all ranks, ``sum`` added in rank order, ``count``
+    added exactly; the frames the sampler pads the last round with enter no plane and get no picture (``_unpadded``), so every image of
+    the split is counted once."""
     part = single_gpu_test(model, data_loader, pre_eval, format_only, format_args, device, show=show, out_dir=out_dir,
                            device_eval=device_eval, ply_dir=ply_dir, ground_dir=ground_dir, eval_batch=eval_batch, engine_graph=engine_graph,
-                           scene_dir=scene_dir, strata=strata)
+                           scene_dir=scene_dir, strata=strata, errors=errors)
     rank, world = get_dist_info()
     if world == 1:
         return part
+    if errors is not None:
+        planes = [None] * world
+        dist.all_gather_object(planes, (errors.sum, errors.count, errors.frames))
+        if rank == 0:
+            for s, c, f in planes[1:]:
+                errors.add(s, c, f)
     gathered = [None] * world
     dist.all_gather_object(gathered, part)
     if rank != 0:

@@ -88,6 +88,99 @@ class StrataSpec:
         return f'StrataSpec(edges={self.edges}, ground={self.ground}, ground_tol={self.ground_tol})'
 
 
+class ErrorMaps:
+    """Where in the picture a split's error is (include/gedepth_error.h), for ``single_gpu_test(..., device_eval=True, errors=ErrorMaps(...))``:
+    the loop adds every LiDAR return's abs-rel error e = |gt - pred| / gt into a per-pixel float64 ``sum`` and uint32 ``count`` on the
+    device (a NaN or infinite e enters neither) and, with ``out_dir``, writes one error picture per image there.  After the loop ``sum``
+    and ``count`` are (352, 1216) numpy planes, ``frames`` the number of images, ``rect`` the dataset's evaluation rectangle.
+
+    ``tau`` in (0, 1]: the abs-rel error at the middle threshold of the ten colour bands (0.05: red from 5 %); ``radius`` 0 .. 3: a return
+    is drawn (2 radius + 1) pixels wide, the worst one winning; ``background``: 0 the frame, 1 the frame halved, 2 black.  They are the
+    caller's choices, not measured constants."""
+
+    def __init__(self, out_dir=None, tau=0.05, radius=1, background=1):
+        if out_dir is not None and not isinstance(out_dir, str):
+            raise TypeError(f'ErrorMaps: out_dir must be a directory path or None, got {out_dir!r}')
+        from ...error_kernels import paint_args                        # the one statement of the three ranges (the module loads no library)
+        self.tau, self.radius, self.background = paint_args(tau, radius, background)
+        self.out_dir = out_dir
+        self.sum = self.count = self.rect = None
+        self.frames = 0
+        self.device_sum = self.device_count = None     # the loop's device planes, between ``begin`` and ``finish``
+
+    def begin(self, device, rect, shape=(352, 1216)):
+        """Zeroed device planes for a new loop on ``device``; ``rect``: the rectangle the loop evaluates."""
+        import torch
+        self.device_sum = torch.zeros(shape, device=device, dtype=torch.float64)
+        self.device_count = torch.zeros(shape, device=device, dtype=torch.int32).view(torch.uint32)
+        self.rect, self.frames = tuple(int(v) for v in rect), 0
+        self.sum = self.count = None
+
+    def download(self):
+        """Queue the copies of the device planes into pinned host buffers on the current stream, without synchronising."""
+        import torch
+        self._host = (torch.empty(self.device_sum.shape, dtype=torch.float64, pin_memory=True),
+                      torch.empty(self.device_count.shape, dtype=torch.int32, pin_memory=True))
+        self._host[0].copy_(self.device_sum, non_blocking=True)
+        self._host[1].copy_(self.device_count.view(torch.int32), non_blocking=True)
+
+    def finish(self):
+        """After the stream of ``download`` has been synchronised: the planes as numpy arrays -> ``self``."""
+        self.sum = self._host[0].numpy().copy()
+        self.count = self._host[1].numpy().view(np.uint32).copy()
+        self.device_sum = self.device_count = self._host = None
+        return self
+
+    def add(self, other_sum, other_count, frames=0):
+        """Another shard's planes onto these (``multi_gpu_test`` adds the ranks' in rank order: ``count`` adds exactly)."""
+        self.sum = self.sum + np.asarray(other_sum, np.float64)
+        self.count = self.count + np.asarray(other_count, np.uint32)
+        self.frames += int(frames)
+
+    def _planes(self):
+        if self.sum is None:
+            raise RuntimeError('ErrorMaps holds no planes yet: run single_gpu_test(..., device_eval=True, errors=this) first')
+        return self.sum, self.count
+
+    def mean(self):
+        """(352, 1216) float64: the mean abs-rel error of the returns at each pixel, NaN where no return was counted."""
+        s, n = self._planes()
+        with np.errstate(invalid='ignore', divide='ignore'):
+            return np.where(n > 0, s / n, np.nan)
+
+    def rows(self, step=1):
+        """``(mean, count)`` per band of ``step`` image rows: the mean abs-rel error of all returns in the rows (NaN where none) and their
+        number, arrays of ``ceil(352 / step)`` entries."""
+        s, n = self._planes()
+        step = int(step)
+        if step < 1:
+            raise ValueError(f'rows: step must be a positive number of image rows, got {step}')
+        starts = range(0, s.shape[0], step)
+        tot = np.array([s[r:r + step].sum() for r in starts], np.float64)
+        cnt = np.array([n[r:r + step].sum(dtype=np.int64) for r in starts], np.int64)
+        with np.errstate(invalid='ignore', divide='ignore'):
+            return np.where(cnt > 0, tot / cnt, np.nan), cnt
+
+    def save(self, out_dir):
+        """``out_dir/summary.npz`` (``sum``, ``count``, ``tau``, ``rect``, ``frames``) and ``out_dir/mean_abs_rel.png``: the band of
+        ``mean() / tau`` in the error images' colours, black where no return was counted."""
+        import os
+        from PIL import Image
+        from ..utils.error_bands import ERROR_COLOURS, error_bands
+        s, n = self._planes()
+        os.makedirs(out_dir, exist_ok=True)
+        np.savez(os.path.join(out_dir, 'summary.npz'), sum=s, count=n, tau=np.float64(self.tau), rect=np.array(self.rect, np.int64),
+                 frames=np.int64(self.frames))
+        mean = self.mean()
+        picture = np.zeros(s.shape + (3,), np.uint8)
+        hit = n > 0
+        picture[hit] = ERROR_COLOURS[error_bands((mean[hit] / self.tau).astype(np.float32))]
+        Image.fromarray(picture).save(os.path.join(out_dir, 'mean_abs_rel.png'), compress_level=1)      # ERROR_COLOURS is RGB
+
+    def __repr__(self):
+        return f'ErrorMaps(out_dir={self.out_dir!r}, tau={self.tau}, radius={self.radius}, background={self.background})'
+
+
 def strata_table(rows, spec, min_depth=1e-3, max_depth=80):
     """``rows`` (N, S, 10) float64, every image's metric sums per stratum -> OrderedDict stratum name -> OrderedDict of the nine metrics
     plus ``pixels`` (the stratum's share of all counted pixels) and ``images`` (the number of images where it is non-empty).  A stratum's

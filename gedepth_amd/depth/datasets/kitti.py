@@ -244,6 +244,98 @@ class KITTIDataset(Dataset):
         K.depth_metric_sums_strata_batch(preds, devs, tops, lefts, self.eval_rect(352, 1216), *limits, rows, spec.edges,
                                          list(grounds) if spec.ground else None, spec.ground_tol)
 
+    def pre_eval_device_errors(self, pred, index, errors, frame, out=None, raw=None, *, sums_row=None, strata=None, rows=None, ground=None):
+        """One image into the planes of ``errors`` (``core.ErrorMaps`` after ``begin``): ``ge_error_accumulate`` with the dataset's
+        ``eval_rect(352, 1216)``, ``depth_scale``, ``min_depth`` and ``max_depth``; with ``errors.out_dir`` also ``ge_error_image`` of the
+        image over ``frame`` = (the uploaded (H, W, 3) uint8 BGR frame, top, left), what the engine keeps as ``last_frame``, into ``out``
+        (a CUDA (352, 1216, 3) uint8 tensor, made when None) — returned, else None.  ``raw``: the ``gt_raw`` array when a thread has
+        decoded it ahead.  ``sums_row``: also run ``pre_eval_device``'s own call into this (10,) row; ``strata`` with ``rows`` and
+        ``ground``: also ``pre_eval_device_strata``'s; all on one upload of the ground truth.  Does not synchronise."""
+        import torch
+        from ... import kernels as K
+        if not (torch.is_tensor(pred) and pred.is_cuda and tuple(pred.shape) == (1, 352, 1216) and pred.dtype == torch.float32):
+            raise TypeError('pre_eval_device_errors takes a CUDA (1, 352, 1216) float32 prediction, got '
+                            f'{tuple(pred.shape) if torch.is_tensor(pred) else type(pred)}')
+        if errors.device_sum is None:
+            raise ValueError('pre_eval_device_errors: errors holds no device planes (ErrorMaps.begin makes them)')
+        if strata is not None and (rows is None or (strata.ground and ground is None)):
+            raise ValueError('pre_eval_device_errors: strata needs rows and, with spec.ground, the frame\'s ground depth')
+        raw = self.gt_raw(index) if raw is None else raw
+        h, w = raw.shape
+        top, left = int(h - 352), int((w - 1216) / 2)                   # eval_kb_crop
+        if errors.out_dir:
+            bgr, ftop, fleft = frame
+            if (ftop, fleft) != (top, left) or tuple(bgr.shape[:2]) != (h, w):
+                raise ValueError(f'pre_eval_device_errors: the frame {tuple(bgr.shape[:2])} at {(ftop, fleft)} is not the ground truth\'s '
+                                 f'{(h, w)} at {(top, left)}')
+        dev = self.__dict__.setdefault('_gt_upload', PinnedUpload())(raw, pred.device)      # one upload for every call below
+        rect, limits = self.eval_rect(352, 1216), (self.depth_scale, self.min_depth, self.max_depth)
+        if sums_row is not None:
+            K.depth_metric_sums(pred, dev, top, left, rect, *limits, sums_row)
+        if strata is not None:
+            K.depth_metric_sums_strata(pred, dev, top, left, rect, *limits, rows, strata.edges, ground if strata.ground else None,
+                                       strata.ground_tol)
+        K.error_accumulate(pred, dev, top, left, rect, *limits, errors.device_sum, errors.device_count)
+        errors.frames += 1
+        if not errors.out_dir:
+            return None
+        return K.error_image(pred, dev, bgr, top, left, rect, *limits, errors.tau, errors.radius, errors.background, want_err=False, out=out)[0]
+
+    def pre_eval_device_errors_batch(self, preds, indices, errors, frames, outs=None, raws=None, *, sums_rows=None, strata=None, rows=None,
+                                     grounds=None, count=None):
+        """``pre_eval_device_errors`` for n = ``len(indices)`` <= 8 images: one ``ge_error_accumulate_batch`` call (the images in index
+        order) and, with ``errors.out_dir``, one ``ge_error_image_batch`` call into the first n blocks of ``outs`` (a CUDA
+        (F >= n, 352, 1216, 3) uint8 tensor, made when None) — returned as (n, 352, 1216, 3), else None.  ``frames``: the n
+        (frame, top, left) the batched engine keeps as ``last_frames``; ``raws``, ``sums_rows``, ``strata`` / ``rows`` / ``grounds`` as in
+        the batch forms of ``pre_eval_device`` and ``pre_eval_device_strata``.  ``count`` = m <= n: only the first m images enter the planes
+        and get a picture (the loop keeps a padded shard's repeated frames out this way); the metric and strata calls still cover all n.
+        Does not synchronise."""
+        import torch
+        from ... import kernels as K
+        n = len(indices)
+        if not (torch.is_tensor(preds) and preds.is_cuda and preds.dim() == 4 and tuple(preds.shape[1:]) == (1, 352, 1216)
+                and preds.shape[0] >= n and preds.dtype == torch.float32):
+            raise TypeError(f'pre_eval_device_errors_batch takes a CUDA (F >= {n}, 1, 352, 1216) float32 tensor, got '
+                            f'{tuple(preds.shape) if torch.is_tensor(preds) else type(preds)}')
+        if not 1 <= n <= 8:
+            raise ValueError(f'pre_eval_device_errors_batch takes 1 .. 8 images, got {n}')
+        m = n if count is None else int(count)
+        if not 0 <= m <= n:
+            raise ValueError(f'pre_eval_device_errors_batch: count must lie in 0 .. {n}, got {count}')
+        if errors.device_sum is None:
+            raise ValueError('pre_eval_device_errors_batch: errors holds no device planes (ErrorMaps.begin makes them)')
+        if strata is not None and (rows is None or (strata.ground and (grounds is None or len(grounds) != n))):
+            raise ValueError('pre_eval_device_errors_batch: strata needs rows and, with spec.ground, every frame\'s ground depth')
+        if errors.out_dir and m and (frames is None or len(frames) != n):
+            raise ValueError(f'pre_eval_device_errors_batch: {n} images need their {n} uploaded frames')
+        raws = [self.gt_raw(i) for i in indices] if raws is None else raws
+        tops = [int(r.shape[0] - 352) for r in raws]                    # eval_kb_crop
+        lefts = [int((r.shape[1] - 1216) / 2) for r in raws]
+        if errors.out_dir and m:
+            for (bgr, ftop, fleft), raw, top, left in zip(frames, raws, tops, lefts):
+                if (ftop, fleft) != (top, left) or tuple(bgr.shape[:2]) != tuple(raw.shape):
+                    raise ValueError(f'pre_eval_device_errors_batch: a frame {tuple(bgr.shape[:2])} at {(ftop, fleft)} is not its ground '
+                                     f'truth\'s {tuple(raw.shape)} at {(top, left)}')
+        uploads = self.__dict__.setdefault('_gt_uploads', [])          # pre_eval_device_batch's staging buffers
+        while len(uploads) < n:
+            uploads.append(PinnedUpload())
+        devs = [up(raw, preds.device) for up, raw in zip(uploads, raws)]
+        rect, limits = self.eval_rect(352, 1216), (self.depth_scale, self.min_depth, self.max_depth)
+        if sums_rows is not None:
+            K.depth_metric_sums_batch(preds, devs, tops, lefts, rect, *limits, sums_rows)
+        if strata is not None:
+            K.depth_metric_sums_strata_batch(preds, devs, tops, lefts, rect, *limits, rows, strata.edges,
+                                             list(grounds) if strata.ground else None, strata.ground_tol)
+        if not m:
+            return None
+        K.error_accumulate_batch(preds, devs[:m], tops[:m], lefts[:m], rect, *limits, errors.device_sum, errors.device_count)
+        errors.frames += m
+        if not errors.out_dir:
+            return None
+        out, _ = K.error_image_batch(preds, devs[:m], [f[0] for f in frames[:m]], tops[:m], lefts[:m], rect, *limits, errors.tau,
+                                     errors.radius, errors.background, want_err=False, out=outs)
+        return out[:m]
+
     def evaluate_strata(self, rows, spec, logger=None):
         """``rows`` (N, S, 10) float64 from the device loop -> ``{'<stratum>.<metric>': value}`` (the nine metrics, ``pixels`` and ``images``
         of ``core.strata_table``); prints the table."""

@@ -1,4 +1,5 @@
 from .color_depth import colorize
+from .error_bands import ERROR_COLOURS, error_bands
 from .point_cloud import POINT_DTYPE, depth_to_points, kitti_intrinsics, scene_records_to_points, write_ply, write_scene_ply
 from .position_encoding import SinePositionalEncoding
 

@@ -12,7 +12,9 @@ KITTI front end, merge and metric sums; its ``GeBatchFrame`` struct is mirrored 
 third: ``SCENE_SIGNATURES`` for include/gedepth_scene.h (the scene clouds; its ``GeSceneLayer`` struct is mirrored in
 gedepth_amd/scene_kernels.py).  ``STRATA_HEADERS`` is a fourth: ``STRATA_SIGNATURES`` for include/gedepth_strata.h (the stratified
 metric sums, wrapped in gedepth_amd/strata_kernels.py).  ``NECK_HEADERS`` is a fifth: ``NECK_SIGNATURES`` for include/gedepth_neck.h (the HAHI
-neck's level-token kernels, wrapped in gedepth_amd/neck_kernels.py).  ``lib()`` binds the entry points of all five tables.
+neck's level-token kernels, wrapped in gedepth_amd/neck_kernels.py).  ``ERROR_HEADERS`` is a sixth: ``ERROR_SIGNATURES`` for
+include/gedepth_error.h (the error images and the split-level error planes, wrapped in gedepth_amd/error_kernels.py).  ``lib()`` binds the
+entry points of all six tables.
 
 There is deliberately NO fallback: if the shared library is missing, or a tensor is not a
 contiguous CUDA(HIP) tensor of the expected dtype, the call raises.  Build the library with
@@ -32,6 +34,7 @@ EXTRA_HEADERS = {'BATCH_SIGNATURES': 'gedepth_batch.h'}      # headers added aft
 SCENE_HEADERS = {'SCENE_SIGNATURES': 'gedepth_scene.h'}      # and after those
 STRATA_HEADERS = {'STRATA_SIGNATURES': 'gedepth_strata.h'}   # and after those
 NECK_HEADERS = {'NECK_SIGNATURES': 'gedepth_neck.h'}         # and after those
+ERROR_HEADERS = {'ERROR_SIGNATURES': 'gedepth_error.h'}      # and after those
 GE_F32, GE_BF16 = 0, 1
 GE_COLORIZE_VMIN_DATA, GE_COLORIZE_VMAX_DATA, GE_COLORIZE_EQUAL = 1, 2, 4      # ge_depth_colorize flags
 
@@ -63,7 +66,7 @@ def parse_header(text):
     return sigs
 
 
-for _table, _header in {**HEADERS, **EXTRA_HEADERS, **SCENE_HEADERS, **STRATA_HEADERS, **NECK_HEADERS}.items():          # SIGNATURES, EVAL_SIGNATURES, ...: name -> (restype, argtypes)
+for _table, _header in {**HEADERS, **EXTRA_HEADERS, **SCENE_HEADERS, **STRATA_HEADERS, **NECK_HEADERS, **ERROR_HEADERS}.items():          # SIGNATURES, EVAL_SIGNATURES, ...: name -> (restype, argtypes)
     with open(os.path.join(os.path.dirname(_HERE), 'include', _header)) as _fh:
         globals()[_table] = parse_header(_fh.read())
 
@@ -83,7 +86,7 @@ def lib():
                 f'{LIB_PATH} is missing: the gfx950 HIP kernels are not built. '
                 f'Run gedepth_amd/csrc/build.sh (hipcc --offload-arch=gfx950). There is no CPU/eager fallback.')
         handle = ctypes.CDLL(LIB_PATH)
-        for table in (*HEADERS, *EXTRA_HEADERS, *SCENE_HEADERS, *STRATA_HEADERS, *NECK_HEADERS):
+        for table in (*HEADERS, *EXTRA_HEADERS, *SCENE_HEADERS, *STRATA_HEADERS, *NECK_HEADERS, *ERROR_HEADERS):
             for name, (res, args) in globals()[table].items():
                 fn = getattr(handle, name)   # AttributeError here == ABI mismatch: fail loudly
                 fn.restype, fn.argtypes = res, args

@@ -2,6 +2,10 @@
 
 PyTorch is used for device memory, streams and autograd plumbing only; every forward and
 backward below is a call into libgedepth_hip.so through gedepth_amd.hip (no eager fallback).
+
+The entry points outside the versioned ABI of include/gedepth_hip.h are wrapped in modules of their own and re-exported at the end of
+this one: evaluation, point clouds, ground maps, batched inference, scene clouds, stratified sums, and the error images and error planes
+of error_kernels.py (include/gedepth_error.h).
 """
 import ctypes
 import os
@@ -2123,3 +2127,7 @@ from .scene_kernels import SceneLayer, scene_points  # noqa: E402,F401
 
 # --------------------------------------------------------------------- stratified metric sums (csrc/eval.hip, include/gedepth_strata.h)
 from .strata_kernels import depth_metric_sums_strata, depth_metric_sums_strata_batch  # noqa: E402,F401
+
+# --------------------------------------------------------------------- error images and split-level error planes (csrc/error.hip,
+# include/gedepth_error.h)
+from .error_kernels import error_accumulate, error_accumulate_batch, error_image, error_image_batch  # noqa: E402,F401

@@ -8,7 +8,9 @@ from files.  Round 0 warms up (the engines capture their graphs there) and is no
 ``--rounds`` rounds.  A pass is timed from the call to the returned list of metric tuples (the loop ends with its one synchronising copy).
 The last line is one JSON object: per F the median and the minimum of the passes in ms per frame.  ``--strata`` times every F twice, without
 and with ``strata=StrataSpec()`` (eight strata: four distance bins, on / off ground), alternated pass by pass; the keys of the second are
-``"<F>+strata"``."""
+``"<F>+strata"``.  ``--errors`` adds two more settings per F: ``errors=ErrorMaps()`` (the split's error planes only; ``"<F>+errors"``) and
+``errors=ErrorMaps(dir)`` (also one error picture per frame, copied to the host per batch and encoded as PNG on the thread pool;
+``"<F>+pictures"``)."""
 import argparse
 import json
 import os
@@ -64,6 +66,8 @@ def main(argv=None):
     p.add_argument('--bf16', action='store_true')
     p.add_argument('--seed', type=int, default=0)
     p.add_argument('--strata', action='store_true', help='time every setting without and with the stratified sums (StrataSpec())')
+    p.add_argument('--errors', action='store_true',
+                   help='time every setting without and with the error maps: ErrorMaps() (planes only) and ErrorMaps(dir) (a PNG per frame)')
     args = p.parse_args(argv)
     assert torch.cuda.is_available(), 'tools/benchmark_eval.py measures the MI355X'
     cfg = Config.fromfile(args.config)
@@ -74,17 +78,20 @@ def main(argv=None):
         ds = build_dataset(cfg.data.test, dict(test_mode=True))
         loader = build_dataloader(ds, 1, 0, dist=False, shuffle=False)
         assert len(ds) == args.frames
-        from gedepth_amd.depth.core import StrataSpec
-        settings = [(F, spec) for F in args.eval_batch for spec in ((None, StrataSpec()) if args.strata else (None,))]
-        spent = {f'{F}+strata' if spec else F: [] for F, spec in settings}
+        from gedepth_amd.depth.core import ErrorMaps, StrataSpec
+        pictures = osp.join(root, 'error_pictures')
+        extras = [('', None, None)] + ([('+strata', StrataSpec(), None)] if args.strata else [])
+        extras += [('+errors', None, lambda: ErrorMaps()), ('+pictures', None, lambda: ErrorMaps(pictures))] if args.errors else []
+        settings = [(f'{F}{tag}' if tag else F, F, spec, errors) for F in args.eval_batch for tag, spec, errors in extras]
+        spent = {key: [] for key, _, _, _ in settings}
         summary = {}
         for rnd in range(args.rounds + 1):
-            for F, spec in settings:
-                key = f'{F}+strata' if spec else F
+            for key, F, spec, errors in settings:
                 torch.cuda.synchronize()
                 t0 = time.perf_counter()
                 with torch.autocast('cuda', dtype=torch.bfloat16, enabled=args.bf16):
-                    res = single_gpu_test(model, loader, pre_eval=True, device_eval=True, eval_batch=F, strata=spec)
+                    res = single_gpu_test(model, loader, pre_eval=True, device_eval=True, eval_batch=F, strata=spec,
+                                          errors=errors and errors())
                 elapsed = time.perf_counter() - t0
                 res = res[0] if spec else res
                 if rnd:
