@@ -70,8 +70,10 @@ def train_depther(model, dataset, cfg, distributed=False, validate=False, timest
     runner.batch_transform = batch_transform
     if timestamp:
         runner.timestamp = timestamp
-    runner.register_training_hooks(cfg.lr_config, dict(grad_clip=cfg.get('optimizer_config', {}).get('grad_clip')),
-                                   cfg.get('checkpoint_config'), cfg.get('log_config'))
+    opt_cfg = cfg.get('optimizer_config', {})
+    hook_cfg = dict(grad_clip=opt_cfg.get('grad_clip'))
+    hook_cfg.update({k: opt_cfg[k] for k in ('type', 'cumulative_iters') if k in opt_cfg})       # GradientCumulativeOptimizerHook
+    runner.register_training_hooks(cfg.lr_config, hook_cfg, cfg.get('checkpoint_config'), cfg.get('log_config'))
     if validate and evaluate_fn is not None:
         runner.register_hook(EvalHook(evaluate_fn, **dict(cfg.get('evaluation', {}))))
     if cfg.get('resume_from'):

@@ -13,8 +13,9 @@ third: ``SCENE_SIGNATURES`` for include/gedepth_scene.h (the scene clouds; its `
 gedepth_amd/scene_kernels.py).  ``STRATA_HEADERS`` is a fourth: ``STRATA_SIGNATURES`` for include/gedepth_strata.h (the stratified
 metric sums, wrapped in gedepth_amd/strata_kernels.py).  ``NECK_HEADERS`` is a fifth: ``NECK_SIGNATURES`` for include/gedepth_neck.h (the HAHI
 neck's level-token kernels, wrapped in gedepth_amd/neck_kernels.py).  ``ERROR_HEADERS`` is a sixth: ``ERROR_SIGNATURES`` for
-include/gedepth_error.h (the error images and the split-level error planes, wrapped in gedepth_amd/error_kernels.py).  ``lib()`` binds the
-entry points of all six tables.
+include/gedepth_error.h (the error images and the split-level error planes, wrapped in gedepth_amd/error_kernels.py).  ``ACCUM_HEADERS`` is a
+seventh: ``ACCUM_SIGNATURES`` for include/gedepth_accum.h (the optimizer's gradient accumulation, wrapped in gedepth_amd/accum_kernels.py).
+``lib()`` binds the entry points of all seven tables.
 
 There is deliberately NO fallback: if the shared library is missing, or a tensor is not a
 contiguous CUDA(HIP) tensor of the expected dtype, the call raises.  Build the library with
@@ -35,6 +36,7 @@ SCENE_HEADERS = {'SCENE_SIGNATURES': 'gedepth_scene.h'}      # and after those
 STRATA_HEADERS = {'STRATA_SIGNATURES': 'gedepth_strata.h'}   # and after those
 NECK_HEADERS = {'NECK_SIGNATURES': 'gedepth_neck.h'}         # and after those
 ERROR_HEADERS = {'ERROR_SIGNATURES': 'gedepth_error.h'}      # and after those
+ACCUM_HEADERS = {'ACCUM_SIGNATURES': 'gedepth_accum.h'}      # and after those
 GE_F32, GE_BF16 = 0, 1
 GE_COLORIZE_VMIN_DATA, GE_COLORIZE_VMAX_DATA, GE_COLORIZE_EQUAL = 1, 2, 4      # ge_depth_colorize flags
 
@@ -66,7 +68,7 @@ def parse_header(text):
     return sigs
 
 
-for _table, _header in {**HEADERS, **EXTRA_HEADERS, **SCENE_HEADERS, **STRATA_HEADERS, **NECK_HEADERS, **ERROR_HEADERS}.items():          # SIGNATURES, EVAL_SIGNATURES, ...: name -> (restype, argtypes)
+for _table, _header in {**HEADERS, **EXTRA_HEADERS, **SCENE_HEADERS, **STRATA_HEADERS, **NECK_HEADERS, **ERROR_HEADERS, **ACCUM_HEADERS}.items():          # SIGNATURES, EVAL_SIGNATURES, ...: name -> (restype, argtypes)
     with open(os.path.join(os.path.dirname(_HERE), 'include', _header)) as _fh:
         globals()[_table] = parse_header(_fh.read())
 
@@ -86,7 +88,7 @@ def lib():
                 f'{LIB_PATH} is missing: the gfx950 HIP kernels are not built. '
                 f'Run gedepth_amd/csrc/build.sh (hipcc --offload-arch=gfx950). There is no CPU/eager fallback.')
         handle = ctypes.CDLL(LIB_PATH)
-        for table in (*HEADERS, *EXTRA_HEADERS, *SCENE_HEADERS, *STRATA_HEADERS, *NECK_HEADERS, *ERROR_HEADERS):
+        for table in (*HEADERS, *EXTRA_HEADERS, *SCENE_HEADERS, *STRATA_HEADERS, *NECK_HEADERS, *ERROR_HEADERS, *ACCUM_HEADERS):
             for name, (res, args) in globals()[table].items():
                 fn = getattr(handle, name)   # AttributeError here == ABI mismatch: fail loudly
                 fn.restype, fn.argtypes = res, args

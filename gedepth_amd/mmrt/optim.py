@@ -117,6 +117,20 @@ class GradArena:
         for p in self.params:
             p._ge_lp_version = p._version
 
+    # ---- second gradient arena: the sum over the iterations of an accumulation window ----
+    def enable_accum(self):
+        """Allocate (on first use) and return ``flat_accum``: fp32, laid out like ``flat_grad``, 4 B / parameter.  In adopt mode every
+        backward WRITES its gradients into ``flat_grad`` (``zero_grad`` sets ``p.grad = None`` and the first producer of a step stores, it
+        does not add), so the sum over several iterations needs storage of its own.  Not zeroed: the first accumulation of a window
+        overwrites it (``ge_grad_accum`` with ``first``).  It follows its parameters through ``permute``."""
+        if getattr(self, 'flat_accum', None) is None:
+            self.flat_accum = torch.empty(self.numel, device=self.flat_param.device, dtype=torch.float32)
+            self.on_permute(self._accum_permuted)
+        return self.flat_accum
+
+    def _accum_permuted(self, remap):
+        self.flat_accum = remap(self.flat_accum)
+
     def reattach(self):
         """Copy externally-assigned ``.grad`` tensors into the arena and re-point them (tests / foreign code)."""
         self.collect()
@@ -281,7 +295,8 @@ class FusedAdamW(torch.optim.Optimizer):
         # ring of pinned staging buffers: the H2D copy of the step scalars never blocks the host
         self._ring = [(torch.zeros(10, dtype=torch.float32).pin_memory(), torch.cuda.Event()) for _ in range(8)]
         self.gnorm_sq = torch.zeros(1, device=dev, dtype=torch.float64)
-        if bf16_shadow:                            # 2 B / parameter: the autocast forward reads weights from here, no per-tensor casts
+        self._accum_count, self._accum_norm = 0, False       # gradients in arena.flat_accum since the last step; gnorm_sq holds their norm
+        if bf16_shadow:                           # 2 B / parameter: the autocast forward reads weights from here, no per-tensor casts
             self.arena.enable_shadow()
             self.arena.refresh_shadow(copy=True)
         self.arena.on_permute(self._arena_permuted)
@@ -328,17 +343,42 @@ class FusedAdamW(torch.optim.Optimizer):
     def launch(self):
         """Device half of a step: gradient norm + clip + AdamW (+ bf16 shadow) over the arenas.  Capturable."""
         a = self.arena
-        a.collect()                            # gradients autograd handed over (not yet brought in by FlatDDP) -> arena
-        self.gnorm_sq.zero_()
-        hip.call('ge_sumsq', hip.ptr(a.flat_grad), a.numel, hip.ptr(self.gnorm_sq), hip.stream())
+        if self._accum_count:                  # an accumulation window: its sum is the gradient, and the last accumulate may have left its norm
+            grad = a.flat_accum
+            if not self._accum_norm:
+                self.gnorm_sq.zero_()
+                hip.call('ge_sumsq', hip.ptr(grad), a.numel, hip.ptr(self.gnorm_sq), hip.stream())
+            self._accum_count, self._accum_norm = 0, False
+        else:
+            a.collect()                        # gradients autograd handed over (not yet brought in by FlatDDP) -> arena
+            grad = a.flat_grad
+            self.gnorm_sq.zero_()
+            hip.call('ge_sumsq', hip.ptr(grad), a.numel, hip.ptr(self.gnorm_sq), hip.stream())
         shadow = getattr(a, 'flat_shadow', None)
         if shadow is None:
-            hip.call('ge_adamw_step', hip.ptr(a.flat_param), hip.ptr(a.flat_grad), hip.ptr(self.exp_avg), hip.ptr(self.exp_avg_sq),
+            hip.call('ge_adamw_step', hip.ptr(a.flat_param), hip.ptr(grad), hip.ptr(self.exp_avg), hip.ptr(self.exp_avg_sq),
                      hip.ptr(self.wd_mask), hip.ptr(self.hyper), hip.ptr(self.gnorm_sq), a.numel, hip.stream())
         else:
-            hip.call('ge_adamw_step_shadow', hip.ptr(a.flat_param), hip.ptr(a.flat_grad), hip.ptr(self.exp_avg), hip.ptr(self.exp_avg_sq),
+            hip.call('ge_adamw_step_shadow', hip.ptr(a.flat_param), hip.ptr(grad), hip.ptr(self.exp_avg), hip.ptr(self.exp_avg_sq),
                      hip.ptr(self.wd_mask), hip.ptr(self.hyper), hip.ptr(self.gnorm_sq), a.numel, hip.ptr(shadow), hip.stream())
             a.refresh_shadow(copy=False)
+
+    @torch.no_grad()
+    def accumulate(self, last=False):
+        """Add the current gradients into the accumulation arena (``GradArena.enable_accum``; the first call of a window writes them) instead
+        of stepping: one ``ge_grad_accum`` pass.  The next ``step()`` takes the sum as its gradient and starts a new window; ``step_count``
+        and the bias corrections advance once per step, not per accumulation.  ``last``: this is the window's last gradient, so the pass also
+        leaves the squared norm of the sum in ``gnorm_sq`` and the step runs no ``ge_sumsq`` of its own.  A partial window is not part of
+        ``state_dict``."""
+        from ..accum_kernels import grad_accum
+        a = self.arena
+        acc = a.enable_accum()
+        a.collect()
+        if last:
+            self.gnorm_sq.zero_()
+        grad_accum(acc, a.flat_grad, first=self._accum_count == 0, sumsq=self.gnorm_sq if last else None, n=a.numel)
+        self._accum_count += 1
+        self._accum_norm = bool(last)
 
     @torch.no_grad()
     def step(self, closure=None):

@@ -68,6 +68,63 @@ class OptimizerHook(Hook):
         runner.optimizer.step()
 
 
+class GradientCumulativeOptimizerHook(OptimizerHook):
+    """mmcv's hook of the same name: the gradients of ``cumulative_iters`` = N iterations are summed and one optimizer step taken on the sum,
+    so that N iterations of b images step like one of N b.  ``runner.iter``, ``max_iters``, the lr schedule and the logging, checkpoint and
+    evaluation intervals keep counting iterations.
+
+    Windows are counted from the iteration the run starts at (``start``, non-zero after a resume): ``pos = (iter - start) % N``.  The last
+    ``R = (max_iters - start) % N`` iterations form a short final window.  Every iteration back-propagates ``loss / N`` (``loss / R`` inside
+    that final window), runs the gradient exchange like ``OptimizerHook`` and calls ``optimizer.accumulate(last=boundary)``; at a boundary
+    (``pos == N - 1``, or the run's last iteration) ``optimizer.step()`` follows, with the learning rate of that iteration.  ``log_vars`` keep
+    the unscaled loss.  The sum lives in a second gradient arena (``GradArena.enable_accum``: 4 B per parameter).
+
+    ``cumulative_iters == 1`` is ``OptimizerHook``: no ``accumulate``, no second arena.  A captured training step (``hip_graph``) contains the
+    optimizer, so it cannot be combined with N > 1."""
+
+    def __init__(self, cumulative_iters=1, grad_clip=None):
+        super().__init__(grad_clip=grad_clip)
+        if isinstance(cumulative_iters, bool) or not isinstance(cumulative_iters, int) or cumulative_iters < 1:
+            raise ValueError(f'cumulative_iters must be an integer >= 1, got {cumulative_iters!r}')
+        self.cumulative_iters = cumulative_iters
+        self.start = 0
+
+    def before_run(self, runner):
+        n = self.cumulative_iters
+        self.start = runner.iter
+        if n == 1:
+            return
+        if getattr(runner, 'hip_graph', False):
+            raise NotImplementedError(f'--hip-graph captures the optimizer inside the training step and cannot accumulate gradients: '
+                                      f'run cumulative_iters={n} without it, or cumulative_iters=1')
+        model = runner.model.module if hasattr(runner.model, 'module') else runner.model
+        if any(isinstance(m, torch.nn.modules.batchnorm._BatchNorm) for m in model.modules()):
+            runner.logger(f'GradientCumulativeOptimizerHook: the model has BatchNorm layers; their statistics stay per iteration '
+                          f'(not per {n} iterations): cumulative_iters={n} does not enlarge the BatchNorm batch')
+        odd = sorted({h.interval for h in runner.hooks if isinstance(h, CheckpointHook) and h.interval > 0 and h.interval % n})
+        if odd:
+            runner.logger(f'GradientCumulativeOptimizerHook: checkpoint interval {", ".join(map(str, odd))} is not a multiple of '
+                          f'cumulative_iters={n}: a resume from such a checkpoint drops the gradients of its partial window')
+
+    def after_train_iter(self, runner):
+        n = self.cumulative_iters
+        if n == 1:
+            return super().after_train_iter(runner)
+        pos = (runner.iter - self.start) % n
+        short = (runner.max_iters - self.start) % n               # length of the final window when the run does not end on a full one
+        factor = short if runner.iter >= runner.max_iters - short else n
+        (runner.outputs['loss'] / factor).backward()
+        if hasattr(runner.model, 'finish'):
+            runner.model.finish()
+        boundary = pos == n - 1 or runner.iter == runner.max_iters - 1
+        runner.optimizer.accumulate(last=boundary)
+        if boundary:
+            runner.optimizer.step()
+
+
+OPTIMIZER_HOOKS = dict(OptimizerHook=OptimizerHook, GradientCumulativeOptimizerHook=GradientCumulativeOptimizerHook)
+
+
 class CheckpointHook(Hook):
 
     def __init__(self, interval=-1, by_epoch=False, max_keep_ckpts=-1, out_dir=None, save_optimizer=True, **kwargs):
@@ -206,7 +263,11 @@ class IterBasedRunner:
     def register_training_hooks(self, lr_config, optimizer_config=None, checkpoint_config=None, log_config=None):
         lr_cfg = dict(lr_config)
         self.register_hook(LrUpdaterHook(**lr_cfg))
-        self.register_hook(OptimizerHook(**(optimizer_config or {})))
+        opt_cfg = dict(optimizer_config or {})
+        typ = opt_cfg.pop('type', 'OptimizerHook')
+        if typ not in OPTIMIZER_HOOKS:
+            raise KeyError(f'{typ} is not a known optimizer hook')
+        self.register_hook(OPTIMIZER_HOOKS[typ](**opt_cfg))
         if checkpoint_config:
             self.register_hook(CheckpointHook(**checkpoint_config))
         if log_config:

@@ -30,7 +30,7 @@ from gedepth_amd.mmrt.config import Config, DictAction  # noqa: E402
 from gedepth_amd.mmrt.ddp import init_dist  # noqa: E402
 
 
-def parse_args():
+def parse_args(argv=None):
     p = argparse.ArgumentParser(description='Train a depther')
     p.add_argument('config', help='train config file path')
     p.add_argument('--work-dir', help='the dir to save logs and models')
@@ -60,7 +60,22 @@ def parse_args():
     p.add_argument('--layout', default='nhwc', choices=['nchw', 'nhwc'], help='nhwc: channels-last conv stack (depth/models/utils/layout.py)')
     p.add_argument('--gemm-tuning', default='load', choices=['off', 'load', 'tune'],
                    help='hipBLASLt/rocBLAS solution table for the Linear layers (gedepth_amd/mmrt/tuning.py)')
-    return p.parse_args()
+    p.add_argument('--cumulative-iters', type=int, default=1,
+                   help='sum the gradients of N iterations before each optimizer step (GradientCumulativeOptimizerHook, also '
+                        'cfg.optimizer_config): N iterations of b images step like one of N b; iterations, not steps, are counted by '
+                        'total_iters and every interval.  Not with --hip-graph')
+    return p.parse_args(argv)
+
+
+def set_cumulative_iters(cfg, n):
+    """``--cumulative-iters N``: N > 1 makes ``cfg.optimizer_config`` a GradientCumulativeOptimizerHook's and keeps its ``grad_clip``; 1 leaves
+    the config as it is."""
+    if n < 1:
+        raise ValueError(f'--cumulative-iters must be >= 1, got {n}')
+    if n > 1:
+        cfg.optimizer_config = dict(type='GradientCumulativeOptimizerHook', cumulative_iters=n,
+                                    grad_clip=cfg.get('optimizer_config', {}).get('grad_clip'))
+    return cfg
 
 
 def main():
@@ -79,6 +94,7 @@ def main():
         cfg.amp = 'bf16'
     if args.fp32:
         cfg.amp = 'fp32'
+    set_cumulative_iters(cfg, args.cumulative_iters)
     distributed = args.launcher != 'none'
     rank, local, world = init_dist(cfg.get('dist_params', {}).get('backend', 'nccl')) if distributed else (0, 0, 1)
     if not distributed:
