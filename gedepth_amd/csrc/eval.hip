@@ -1,6 +1,7 @@
 // Metric sums of the KITTI evaluation protocol on the device (include/gedepth_eval.h; depth/core/evaluation.py `calculate` behind
 // depth/datasets/kitti.py `pre_eval`): one image leaves the GPU as ten f64 numbers.  ge_depth_metrics_resized (include/gedepth_ddad.h) is the
-// same reduction for the DDAD protocol, with the bilinear resize of the prediction to the ground truth folded into the pass.
+// same reduction for the DDAD protocol, with the bilinear resize of the prediction to the ground truth folded into the pass;
+// ge_depth_metrics_resized_batch (include/gedepth_ddad_batch.h) runs it for up to GE_BATCH_MAX images of one ground-truth size.
 //
 // The discontinuous part is numpy's float32 arithmetic, bit for bit: gt = (float)raw / depth_scale, the mask gt > min && gt < max, and
 // ratio = maximum(gt / pred, pred / gt) < 1.25^p with true IEEE divisions (no reciprocal, no contraction) and a NaN-propagating maximum.
@@ -17,6 +18,7 @@
 #include "batch_table.h"
 #include "../../include/gedepth_eval.h"
 #include "../../include/gedepth_ddad.h"
+#include "../../include/gedepth_ddad_batch.h"
 #include "../../include/gedepth_strata.h"
 #include <cmath>
 
@@ -224,13 +226,10 @@ __global__ void __launch_bounds__(GE_EVAL_THREADS) metrics_strata_partial_k(cons
 // wy0 * (wx0 * v00 + wx1 * v01) + wy1 * (wx0 * v10 + wx1 * v11), in f32 without contraction.
 // GV: gt is 16-byte aligned and W % 4 == 0 (one float4 per group); otherwise element loads, each one bounds-checked against W.
 struct ResizedArgs { int h, w, H, W; float lo, hi; };
+// one lane's sums over the ground truth of one image, as workgroup blockIdx.x of gridDim.x
 template <bool GV>
-__global__ void __launch_bounds__(GE_EVAL_THREADS) metrics_resized_partial_k(const float* __restrict__ pred, const float* __restrict__ gt,
-                                                                             ResizedArgs a, double* __restrict__ partials) {
-  __shared__ double red[GE_EVAL_THREADS / GE_WAVE][GE_EVAL_SUMS];
-  double acc[GE_EVAL_SUMS];
-#pragma unroll
-  for (int k = 0; k < GE_EVAL_SUMS; ++k) acc[k] = 0.0;
+__device__ __forceinline__ void metrics_resized_sums(const float* __restrict__ pred, const float* __restrict__ gt, const ResizedArgs& a,
+                                                     double acc[GE_EVAL_SUMS]) {
   const float sy = ge_scale(a.h, a.H, true), sx = ge_scale(a.w, a.W, true);
   const int G = (a.W + 3) >> 2;                                       // groups per ground-truth row
   const long items = (long)a.H * G;
@@ -262,7 +261,26 @@ __global__ void __launch_bounds__(GE_EVAL_THREADS) metrics_resized_partial_k(con
       metric_pixel(p, g[k], inside, a.lo, a.hi, acc);
     }
   }
-  metrics_block_fold(acc, red, partials + (long)blockIdx.x * GE_EVAL_SUMS);
+}
+
+// Image f = blockIdx.y of the table (batch_table.h; `image` the (H, W) f32 ground truth, one size for all images): pred (n, h, w), partials
+// (n, gridDim.x, 10).  The ground truth's 16-byte loads (GV) are a per-image choice, uniform over the workgroup.  The images share the block
+// partition, so an image's bits do not depend on how many images the launch has: ge_depth_metrics_resized is the launch of one
+// (include/gedepth_ddad_batch.h).
+__global__ void __launch_bounds__(GE_EVAL_THREADS) metrics_resized_partial_k(const float* __restrict__ pred, BatchTable t, ResizedArgs a,
+                                                                             double* __restrict__ partials) {
+  __shared__ double red[GE_EVAL_THREADS / GE_WAVE][GE_EVAL_SUMS];
+  const GeBatchFrame fr = t.f[blockIdx.y];
+  double acc[GE_EVAL_SUMS];
+#pragma unroll
+  for (int k = 0; k < GE_EVAL_SUMS; ++k) acc[k] = 0.0;
+  const float* p = pred + (long)blockIdx.y * a.h * a.w;
+  const float* gt = (const float*)fr.image;
+  if (((uintptr_t)fr.image & 15) == 0 && (a.W & 3) == 0)
+    metrics_resized_sums<true>(p, gt, a, acc);
+  else
+    metrics_resized_sums<false>(p, gt, a, acc);
+  metrics_block_fold(acc, red, partials + ((long)blockIdx.y * gridDim.x + blockIdx.x) * GE_EVAL_SUMS);
 }
 
 // row blockIdx.x (an image, or an (image, stratum) pair): its partials in index order
@@ -391,20 +409,41 @@ extern "C" int ge_depth_metrics_strata_batch(const float* pred, const GeBatchFra
 
 extern "C" size_t ge_depth_metrics_resized_workspace(int H, int W) { return ge_depth_metrics_workspace(H, W); }
 
+// the two launches over n checked images whose ground truths share (H, W) = frames[0]'s
+static int metrics_resized_launch(const float* pred, int h, int w, const GeBatchFrame* frames, int n, float min_depth, float max_depth,
+                                  double* partials, double* sums, void* stream) {
+  hipStream_t s = ge_stream(stream);
+  ResizedArgs a;
+  a.h = h; a.w = w; a.H = frames[0].H; a.W = frames[0].W; a.lo = min_depth; a.hi = max_depth;
+  const unsigned blocks = metrics_blocks(a.H, a.W);
+  const dim3 grid(blocks, (unsigned)n);
+  metrics_resized_partial_k<<<grid, GE_EVAL_THREADS, 0, s>>>(pred, batch_table(frames, n), a, partials);
+  GE_LAUNCH_CHECK();
+  metrics_fold_k<<<(unsigned)n, GE_WAVE, 0, s>>>(partials, (int)blocks, sums);
+  GE_LAUNCH_CHECK();
+  return GE_OK;
+}
+
 extern "C" int ge_depth_metrics_resized(const float* pred, int h, int w, const float* gt, int H, int W, float min_depth, float max_depth,
                                         double* partials, double* sums, void* stream) {
   if (!pred || !gt || !partials || !sums || h <= 0 || w <= 0 || H <= 0 || W <= 0) return GE_ERR_BAD_ARG;
   if (((uintptr_t)pred & 3) || ((uintptr_t)gt & 3) || ((uintptr_t)partials & 7) || ((uintptr_t)sums & 7)) return GE_ERR_UNSUPPORTED;
-  hipStream_t s = ge_stream(stream);
-  ResizedArgs a;
-  a.h = h; a.w = w; a.H = H; a.W = W; a.lo = min_depth; a.hi = max_depth;
-  const unsigned blocks = metrics_blocks(H, W);
-  if (((uintptr_t)gt & 15) == 0 && (W & 3) == 0)
-    metrics_resized_partial_k<true><<<blocks, GE_EVAL_THREADS, 0, s>>>(pred, gt, a, partials);
-  else
-    metrics_resized_partial_k<false><<<blocks, GE_EVAL_THREADS, 0, s>>>(pred, gt, a, partials);
-  GE_LAUNCH_CHECK();
-  metrics_fold_k<<<1, GE_WAVE, 0, s>>>(partials, (int)blocks, sums);
-  GE_LAUNCH_CHECK();
-  return GE_OK;
+  const GeBatchFrame fr = {gt, nullptr, H, W, 0, 0};
+  return metrics_resized_launch(pred, h, w, &fr, 1, min_depth, max_depth, partials, sums, stream);
+}
+
+extern "C" size_t ge_depth_metrics_resized_batch_workspace(int n, int H, int W) { return ge_depth_metrics_batch_workspace(n, H, W); }
+
+extern "C" int ge_depth_metrics_resized_batch(const float* pred, int h, int w, const GeBatchFrame* frames, int n, float min_depth,
+                                              float max_depth, double* partials, double* sums, void* stream) {
+  if (!pred || !partials || !sums || h <= 0 || w <= 0) return GE_ERR_BAD_ARG;
+  if (int e = batch_frames_check(frames, n, 1, 1, false)) return e;           // the frame list itself; the whole ground truth counts: no window
+  for (int f = 0; f < n; ++f)
+    if (frames[f].top != 0 || frames[f].left != 0) return GE_ERR_BAD_ARG;
+  for (int f = 1; f < n; ++f)
+    if (frames[f].H != frames[0].H || frames[f].W != frames[0].W) return GE_ERR_UNSUPPORTED;      // one block partition for all images
+  if (((uintptr_t)pred & 3) || ((uintptr_t)partials & 7) || ((uintptr_t)sums & 7)) return GE_ERR_UNSUPPORTED;
+  for (int f = 0; f < n; ++f)
+    if ((uintptr_t)frames[f].image & 3) return GE_ERR_UNSUPPORTED;
+  return metrics_resized_launch(pred, h, w, frames, n, min_depth, max_depth, partials, sums, stream);
 }

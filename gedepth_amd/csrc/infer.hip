@@ -1,7 +1,8 @@
 // KITTI / DDAD inference (depth/apis/inference.py of the reference; gedepth_amd/depth/apis/inference.py and batch_inference.py here): the
 // test pipeline's per-frame front end and the flip-TTA merge of encoder_decoder.py aug_test, each as one streaming launch around the
-// forward of the flip views.  The KITTI kernels take up to GE_BATCH_MAX frames per launch, the frame index on blockIdx.y
-// (include/gedepth_batch.h); the single-frame entry points of gedepth_hip.h are their launch of one frame.
+// forward of the flip views.  The kernels take up to GE_BATCH_MAX frames per launch, the frame index on blockIdx.y
+// (include/gedepth_batch.h, include/gedepth_ddad_batch.h); the single-frame entry points of gedepth_hip.h and gedepth_ddad.h are their
+// launch of one frame.
 //
 // The KITTI front end restates, op for op, LoadImageFromFile(USEPE) -> KBCrop -> MultiScaleFlipAug(RandomFlip, Normalize) of
 // configs/_base_/datasets/kitti_gedepth.py, i.e. the composition ge_aug_load -> ge_aug_color_normalize(color_on = 0) ->
@@ -11,6 +12,7 @@
 #pragma clang fp contract(off)
 #include "batch_table.h"
 #include "../../include/gedepth_ddad.h"
+#include "../../include/gedepth_ddad_batch.h"
 
 struct InferNorm { double mean[3], stdinv[3]; float pe_max, depth_scale; int to_rgb; };
 static InferNorm infer_norm(float pe_max, const double* mean3, const double* std3, float depth_scale, int to_rgb) {
@@ -99,12 +101,18 @@ extern "C" int ge_infer_front_batch(const GeBatchFrame* frames, int n, float* ds
 // The output array is indexed by `oc` (BGR -> RGB), which the compiler resolves into selects: 77 VGPRs, no scratch.  The row span of the
 // area filter is formed again for each of the four pixels, inside the shared ge_area_u8_pixel: one launch per frame of 7 680 threads
 // (384 x 640), sized by launch latency, so the shared function stays whole rather than being split for this caller.
-// dst (1, 5, Hd, Wd) planar f32; Wd % 4 == 0, dst 16-byte aligned (checked by the caller).
-__global__ void __launch_bounds__(256) infer_front_ddad_k(const uint8_t* __restrict__ bgr, const float* __restrict__ pe, float* __restrict__ dst,
-                                                          int H, int W, int Hd, int Wd, InferNorm p) {
+// Frame f = blockIdx.y of the table (batch_table.h; `image` the frame, `aux` its camera's ground depth, H and W its own) -> image f of dst
+// (n, 5, Hd, Wd) planar f32; Wd % 4 == 0, dst 16-byte aligned (checked by the caller).  The frames share grid.x, so a frame's bits do not
+// depend on how many frames the launch has: ge_infer_front_ddad is the launch of one (include/gedepth_ddad_batch.h).
+__global__ void __launch_bounds__(256) infer_front_ddad_k(BatchTable t, float* __restrict__ dst, int Hd, int Wd, InferNorm p) {
+  const GeBatchFrame fr = t.f[blockIdx.y];
+  const uint8_t* __restrict__ bgr = (const uint8_t*)fr.image;
+  const float* __restrict__ pe = (const float*)fr.aux;
+  const int H = fr.H, W = fr.W;
   const int G = Wd >> 2;
   const long n = (long)Hd * Wd, groups = (long)Hd * G;
   const double dy = (double)H / (double)Hd, dx = (double)W / (double)Wd;
+  dst += (long)blockIdx.y * 5 * n;
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < groups; i += (long)gridDim.x * 256) {
     const int y = (int)(i / G), g = (int)(i - (long)y * G);
     const int ys = ge_nearest_src(y, dy, H);                // aug_resize_k mode 0
@@ -116,9 +124,9 @@ __global__ void __launch_bounds__(256) infer_front_ddad_k(const uint8_t* __restr
       ge_area_u8_pixel(bgr, H, W, Hd, Wd, y, x, v);         // aug_area_u8_k
 #pragma unroll
       for (int c = 0; c < 3; ++c) {
-        const float t = truncf(v[c]);                       // aug_color_k: a no-op on a uint8 value; BGR -> RGB, f64 (x - mean) * (1 / std)
+        const float u = truncf(v[c]);                       // aug_color_k: a no-op on a uint8 value; BGR -> RGB, f64 (x - mean) * (1 / std)
         const int oc = p.to_rgb ? 2 - c : c;
-        o[oc][k] = (float)(((double)t - p.mean[oc]) * p.stdinv[oc]);
+        o[oc][k] = (float)(((double)u - p.mean[oc]) * p.stdinv[oc]);
       }
       const float raw = pe[(long)ys * W + ge_nearest_src(x, dx, W)];
       float f = raw;                                        // LoadDDADImageFromFile: > pe_max or < 0 zeroed; Normalize: / depth_scale where > 0
@@ -133,16 +141,33 @@ __global__ void __launch_bounds__(256) infer_front_ddad_k(const uint8_t* __restr
     for (int c = 0; c < 5; ++c) *(float4*)(dst + c * n + r) = make_float4(o[c][0], o[c][1], o[c][2], o[c][3]);
   }
 }
+// the launch of n checked frames
+static int infer_front_ddad_launch(const GeBatchFrame* frames, int n, float* dst, int Hd, int Wd, const InferNorm& p, void* stream) {
+  const dim3 grid(ge_blocks((long)Hd * (Wd / 4), 256, 65536), (unsigned)n);
+  infer_front_ddad_k<<<grid, 256, 0, ge_stream(stream)>>>(batch_table(frames, n), dst, Hd, Wd, p);
+  GE_LAUNCH_CHECK();
+  return GE_OK;
+}
 extern "C" int ge_infer_front_ddad(const uint8_t* bgr_hwc, const float* pe, float* dst, int H, int W, int Hd, int Wd, float pe_max,
                                    const double* mean3, const double* std3, float depth_scale, int to_rgb, void* stream) {
   if (!bgr_hwc || !pe || !dst || !mean3 || !std3 || H <= 0 || W <= 0 || Hd <= 0 || Wd <= 0) return GE_ERR_BAD_ARG;
   if (Hd > H || Wd > W) return GE_ERR_UNSUPPORTED;          // the area filter is the shrinking branch, as in ge_aug_area_u8
   if ((Wd & 3) || ((uintptr_t)dst & 15) || ((uintptr_t)pe & 3)) return GE_ERR_UNSUPPORTED;
-  const long groups = (long)Hd * (Wd / 4);
-  infer_front_ddad_k<<<ge_blocks(groups, 256, 65536), 256, 0, ge_stream(stream)>>>(bgr_hwc, pe, dst, H, W, Hd, Wd,
-                                                                                    infer_norm(pe_max, mean3, std3, depth_scale, to_rgb));
-  GE_LAUNCH_CHECK();
-  return GE_OK;
+  const GeBatchFrame fr = {bgr_hwc, pe, H, W, 0, 0};
+  return infer_front_ddad_launch(&fr, 1, dst, Hd, Wd, infer_norm(pe_max, mean3, std3, depth_scale, to_rgb), stream);
+}
+extern "C" int ge_infer_front_ddad_batch(const GeBatchFrame* frames, int n, float* dst, int Hd, int Wd, float pe_max, const double* mean3,
+                                         const double* std3, float depth_scale, int to_rgb, void* stream) {
+  if (!dst || !mean3 || !std3 || Hd <= 0 || Wd <= 0) return GE_ERR_BAD_ARG;
+  if (int e = batch_frames_check(frames, n, 1, 1, true)) return e;            // the frame list itself; the whole frame is resized: no window
+  for (int f = 0; f < n; ++f)
+    if (frames[f].top != 0 || frames[f].left != 0) return GE_ERR_BAD_ARG;
+  for (int f = 0; f < n; ++f)
+    if (Hd > frames[f].H || Wd > frames[f].W) return GE_ERR_UNSUPPORTED;      // the area filter is the shrinking branch
+  if ((Wd & 3) || ((uintptr_t)dst & 15)) return GE_ERR_UNSUPPORTED;
+  for (int f = 0; f < n; ++f)
+    if ((uintptr_t)frames[f].aux & 3) return GE_ERR_UNSUPPORTED;
+  return infer_front_ddad_launch(frames, n, dst, Hd, Wd, infer_norm(pe_max, mean3, std3, depth_scale, to_rgb), stream);
 }
 
 // encoder_decoder.py aug_test over the two flip views: (out0 + flip(out1)) / 2, in that order (sum, then divide by the view count;

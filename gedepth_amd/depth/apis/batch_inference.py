@@ -16,7 +16,13 @@ crosses samples (BatchNorm uses its running statistics, attention windows and th
 slot f holds does not reach another slot's map.
 
 ``decode_ahead`` is the host side: a pool of at most ``DECODE_WORKERS`` threads decodes the next batch's PNGs (PIL releases the GIL while
-inflating) while the device computes the current one.  DDAD, ``points`` and ``ground_maps`` stay single-frame (``DepthInferencer``)."""
+inflating) while the device computes the current one.  ``points`` and ``ground_maps`` stay single-frame (``DepthInferencer``).
+
+``BatchDDADInferencer`` is the same engine for the DDAD protocol (one view per frame, no merge): n uploads, ONE
+``ge_infer_front_ddad_batch`` into the first n images of the static ``(F, 5, Hd, Wd)`` input, the n cameras' heights into the static
+``(F,)`` tensor the adaptive ground embedding reads (one small copy, outside the graph), one captured forward over all F slots.  The slots
+of a batch may hold different cameras.  ``inference_depther(batch > 1)`` stays refused for a DDAD config (``check_batch``): files to
+maps in batches is ``BatchDDADInferencer.run``, the loop's route is ``single_gpu_test(device_eval=True, eval_batch=F)``."""
 from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
@@ -26,20 +32,24 @@ from PIL import Image
 from ... import kernels as K
 from ...batch_kernels import BATCH_MAX
 from ..utils.pinned import PinnedUpload
-from .inference import DepthInferencer, _config_of, _decode
+from ..datasets.pipelines import loading    # _DDAD_CAMERA_HEIGHT is read through the module at every use, as apis/inference.py does
+from .inference import DepthInferencer, _config_of, _ddad_camera, _decode, _per_frame
 
-__all__ = ['BatchDepthInferencer', 'check_batch', 'decode_ahead', 'DECODE_WORKERS']
+__all__ = ['BatchDepthInferencer', 'BatchDDADInferencer', 'check_batch', 'check_ddad_batch', 'decode_ahead', 'DECODE_WORKERS']
 
 DECODE_WORKERS = 4                 # a constant, never the machine's core count: decoding one batch ahead needs no more
 
 
-def check_batch(batch, spec=None, what='batch'):
-    """The argument errors of a frame count, before any device work: 1 .. 8, and more than 1 on the KITTI protocol only."""
+def check_batch(batch, spec=None, what='batch', ddad=False):
+    """The argument errors of a frame count, before any device work: 1 .. 8, and more than 1 on the KITTI protocol only — unless the
+    caller has a DDAD route (``ddad=True``: the device evaluation loop, which runs a ``BatchDDADInferencer``; ``inference_depther`` has
+    none and keeps refusing)."""
     if isinstance(batch, bool) or not isinstance(batch, int) or not 1 <= batch <= BATCH_MAX:
         raise ValueError(f'{what} must be an integer in 1 .. {BATCH_MAX} (the frame slots of one ge_infer_front_batch launch), got {batch!r}')
-    if batch > 1 and spec is not None and spec['protocol'] == 'ddad':
+    if batch > 1 and not ddad and spec is not None and spec['protocol'] == 'ddad':
         raise NotImplementedError(f'{what}={batch} with a DDAD config: the batched engine implements the KITTI protocol only; DDAD frames '
-                                  f'run one at a time ({what}=1)')
+                                  f'run one at a time ({what}=1), or in batches through BatchDDADInferencer.run and '
+                                  'single_gpu_test(device_eval=True, eval_batch=F)')
     return batch
 
 
@@ -155,4 +165,130 @@ class BatchDepthInferencer(DepthInferencer):
         for k, bgrs in enumerate(decode_ahead([(lambda i=i: _decode(i)) for i in imgs], F)):
             part = slice(k * F, k * F + len(bgrs))
             out += self.batch(bgrs, pes[part], calib, cam_height, graph, paths=[i if isinstance(i, str) else None for i in imgs[part]])
+        return out
+
+
+def check_ddad_batch(spec, slots, sizes, pes, cameras, paths, frame_size=None):
+    """The argument errors of one DDAD batch, host work only -> ``(cameras, the frames' one (H, W))``.  ``sizes``: the frames' (H, W);
+    ``pes`` / ``cameras`` / ``paths``: None or one entry per frame; ``frame_size``: what the engine has taken so far, or None."""
+    n = len(sizes)
+    if not 1 <= n <= slots:
+        raise ValueError(f'{n} frames for an engine of {slots} slots')
+    for name, v in (('ground depths', pes), ('cameras', cameras), ('paths', paths)):
+        if v is not None and len(v) != n:
+            raise ValueError(f'{len(v)} {name} for {n} frames')
+    cameras = cameras if cameras is not None else [None] * n
+    paths = paths if paths is not None else [None] * n
+    cams = [_ddad_camera(c, p) for c, p in zip(cameras, paths)]           # ValueError for a camera without a known height
+    if any(c is None for c in cams):
+        raise ValueError(f'no camera for frame {cams.index(None)}: pass cameras= (out of {", ".join(sorted(loading._DDAD_CAMERA_HEIGHT))}) or '
+                         'image paths whose parent directory is the camera name')
+    for H, W in sizes:
+        if H < spec['height'] or W < spec['width']:
+            raise ValueError(f'frame {(H, W)} is smaller than DDADResize\'s shape {(spec["height"], spec["width"])}')
+        if frame_size is not None and frame_size != (H, W):
+            raise ValueError(f'frame {(H, W)}: this engine takes frames of {frame_size} (reset() to change)')
+        frame_size = (H, W)
+    return cams, frame_size
+
+
+class BatchDDADInferencer(DepthInferencer):
+    """The DDAD engine with ``frames`` = F slots (module docstring).  ``batch(imgs)`` runs n <= F frames, which may come from different
+    cameras: each slot has its own ground depth and its own entry of ``static_height``.  Captures are keyed as ``DepthInferencer``'s plus
+    ``('batch', F)``; the capture itself and the in-place contract on the parameters are the base class's, and so is the rule that one
+    engine takes frames of one size."""
+
+    def __init__(self, model, frames, bf16=False, config=None):
+        config = config or _config_of(model)
+        self.frames = check_batch(frames, what='frames')
+        if config[0]['protocol'] != 'ddad':
+            raise NotImplementedError('BatchDDADInferencer with a KITTI config: the KITTI protocol runs in a BatchDepthInferencer')
+        super().__init__(model, bf16, config)
+        s, F = self.spec, self.frames
+        # zeros, and a camera's height: a slot no frame has filled yet still holds finite values for the forward that runs over all slots
+        self.static_in = torch.zeros(F, 5, s['height'], s['width'], device=self.device, dtype=torch.float32)
+        self.static_out = torch.empty(F, 1, s['height'], s['width'], device=self.device, dtype=torch.float32)
+        self._heights = [float(min(loading._DDAD_CAMERA_HEIGHT.values()))] * F
+        self.static_height = torch.tensor(self._heights, device=self.device, dtype=torch.float32)
+        self._forward_kw = dict(height=self.static_height)
+        self._heights_host, self._heights_done = torch.empty(F, dtype=torch.float32, pin_memory=True), None
+        self._stagings = [PinnedUpload() for _ in range(F)]
+
+    def _key(self, ground=False):
+        return super()._key(ground) + ('batch', self.frames)
+
+    def _body(self, metas, ground=False):
+        with torch.no_grad(), torch.autocast('cuda', dtype=torch.bfloat16, enabled=self.bf16):
+            pred = self.model.encode_decode(self.static_in, metas, rescale=True, **self._forward_kw)
+        self.static_out.copy_(pred)                           # all F slots: the captured forward does not depend on n
+
+    def _single(self, *a, **kw):
+        raise NotImplementedError('a BatchDDADInferencer runs batch(imgs); single frames and ground_maps go through the DepthInferencer of '
+                                  'engine_for(model, bf16); points, scene_points and error_map are built for the KITTI protocol')
+
+    __call__ = ground_maps = points = scene_points = error_map = _single
+
+    def batch(self, imgs, pes=None, cameras=None, graph=True, to_host=True, paths=None):
+        """n <= F frames -> their maps.  ``imgs``: paths, (H, W, 3) uint8 BGR arrays, or frames already decoded by ``decode_ahead`` (then
+        ``paths`` names their files, for the camera); ``pes``: one raw ground depth per frame (an entry may be None) or None: the
+        camera's ``ddad_pe.npz``; ``cameras``: one name per frame (an entry may be None) or None: the path's parent directory.  Returns a
+        list of n fresh (1, Hd, Wd) float32 host arrays, or with ``to_host=False`` the view ``static_out[:n]`` of the static device
+        buffer, without synchronising: valid until the next call, ordered on ``self.stream``.  Every argument error is raised before any
+        device work."""
+        n, s = len(imgs), self.spec
+        if not 1 <= n <= self.frames:
+            raise ValueError(f'{n} frames for an engine of {self.frames} slots')
+        paths = paths if paths is not None else [i if isinstance(i, str) else None for i in imgs]
+        if len(paths) != n:
+            raise ValueError(f'{len(paths)} paths for {n} frames')
+        bgrs = [_decode(i) for i in imgs]
+        cams, self.frame_size = check_ddad_batch(s, self.frames, [b.shape[:2] for b in bgrs], pes, cameras, paths, self.frame_size)
+        pes = pes if pes is not None else [None] * n
+        metas = [m for b, p in zip(bgrs, paths) for m in self._metas(p, b.shape[:2], tuple(b.shape[:2]) + (5,))]
+        metas += metas[-1:] * (self.frames - n)
+        self._heights[:n] = [float(loading._DDAD_CAMERA_HEIGHT[c]) for c in cams]      # the other slots keep the height they had
+        cur = torch.cuda.current_stream(self.device)
+        self.stream.wait_stream(cur)
+        with torch.cuda.stream(self.stream):
+            raws = [self.ground_depth_ddad(c, b.shape[0], b.shape[1], pe) for c, b, pe in zip(cams, bgrs, pes)]
+            devs = [up(b, self.device) for up, b in zip(self._stagings, bgrs)]
+            K.infer_front_ddad_batch(devs, raws, self.static_in, s['mean'], s['std'], s['to_rgb'], s['pe_max'], s['depth_scale'])
+            # one small copy into the tensor the captured forward reads through its device pointer; the order of PinnedUpload
+            if self._heights_done is not None:
+                self._heights_done.synchronize()
+            self._heights_host.numpy()[...] = self._heights
+            self.static_height.copy_(self._heights_host, non_blocking=True)
+            self._heights_done = torch.cuda.Event()
+            self._heights_done.record()
+            self._run(self._key(), graph, lambda: self._body(metas))
+            self.last_n, self.last_cameras = n, cams
+            if to_host:
+                host = self.static_out[:n].cpu().numpy()                           # synchronises the engine's stream
+                out = [host[f].copy() for f in range(n)]
+            else:
+                out = self.static_out[:n]
+        cur.wait_stream(self.stream)
+        return out
+
+    def reset(self):
+        super().reset()
+        self.last_n = 0                              # the frame count of the last batch
+        self.last_cameras = None                     # and its cameras
+
+    def run(self, imgs, pes=None, cameras=None, graph=True):
+        """Any number of frames, in batches of F with the next batch decoding ahead -> one host map per frame, in order: the files-to-maps
+        route of a DDAD config (``inference_depther(batch > 1)`` refuses it).  ``pes`` / ``cameras``: a value for every frame, or a
+        list with one per frame."""
+        imgs = imgs if isinstance(imgs, list) else [imgs]
+        pes = _per_frame(pes, len(imgs), '{n} ground-depth maps for {m} frames')
+        cameras = _per_frame(cameras, len(imgs), '{n} cameras for {m} frames')
+        paths = [i if isinstance(i, str) else None for i in imgs]
+        for c, p in zip(cameras, paths):                                          # every frame's camera, before the first batch runs
+            if _ddad_camera(c, p) is None:
+                raise ValueError(f'no camera for a frame: pass cameras= (out of {", ".join(sorted(loading._DDAD_CAMERA_HEIGHT))}) or image '
+                                 'paths whose parent directory is the camera name')
+        F, out = self.frames, []
+        for k, bgrs in enumerate(decode_ahead([(lambda i=i: _decode(i)) for i in imgs], F)):
+            part = slice(k * F, k * F + len(bgrs))
+            out += self.batch(bgrs, pes[part], cameras[part], graph, paths=paths[part])
         return out

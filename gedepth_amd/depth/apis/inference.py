@@ -20,6 +20,7 @@ so a replayed graph follows it) and the forward's (1, Hd, Wd) map is the output.
 (``<pe_root>/<camera>/ddad_pe.npz``) and the height: the ``camera=`` argument, else the image path's parent directory.
 ``_KITTIFront`` / ``_DDADFront`` hold what the protocols do differently per frame; ``engine_for`` keeps a model's engines for every caller.
 ``inference_depther(batch=F)`` runs F KITTI frames per forward instead (apis/batch_inference.py); ``batch=1``, the default, is this engine.
+F DDAD frames per forward: ``BatchDDADInferencer`` there (``engine_for(model, bf16, batch=F)``), which ``inference_depther`` does not reach.
 """
 import gc
 import os.path as osp
@@ -589,7 +590,7 @@ _DDAD_NO_POINTS = ('point clouds on a DDAD engine: DDADResize feeds the network 
 def engine_for(model, bf16=False, config=None, batch=1):
     """The engine of ``model``, ``bf16`` and ``batch`` frame slots in ``model._ge_inferencers``, rebuilt when ``config`` (default
     ``_config_of(model)``) has changed.  ``batch=1``: the ``DepthInferencer`` under key ``bf16``; ``batch=F > 1``: a
-    ``BatchDepthInferencer`` (apis/batch_inference.py) under key ``(bf16, F)``."""
+    ``BatchDepthInferencer`` (apis/batch_inference.py) under key ``(bf16, F)``, for a DDAD config a ``BatchDDADInferencer``."""
     spec, prefix = config = config or _config_of(model)
     engines = model.__dict__.setdefault('_ge_inferencers', {})
     bf16 = bool(bf16)
@@ -598,8 +599,8 @@ def engine_for(model, bf16=False, config=None, batch=1):
         if batch == 1:
             engines[key] = DepthInferencer(model, bf16, config)
         else:
-            from .batch_inference import BatchDepthInferencer
-            engines[key] = BatchDepthInferencer(model, batch, bf16, config)
+            from .batch_inference import BatchDDADInferencer, BatchDepthInferencer
+            engines[key] = (BatchDDADInferencer if spec['protocol'] == 'ddad' else BatchDepthInferencer)(model, batch, bf16, config)
     return engines[key]
 
 
@@ -622,7 +623,8 @@ def inference_depther(model, img, pe=None, calib=None, cam_height=1.65, bf16=Fal
     ``batch=F`` (2 .. 8; KITTI protocol): the list runs F frames per forward through a ``BatchDepthInferencer`` (apis/batch_inference.py),
     the next batch's files decoding on a small thread pool meanwhile; the result is the same list in the same order.  The frames of a
     batch may differ in size.  Every argument error — also a frame smaller than the crop — is raised for the whole list before any
-    device work.  With a DDAD config ``batch > 1`` raises ``NotImplementedError``.
+    device work.  With a DDAD config ``batch > 1`` raises ``NotImplementedError``: DDAD files run in batches through
+    ``engine_for(model, bf16, batch=F).run(files)`` (``BatchDDADInferencer``, apis/batch_inference.py).
 
     With a DDAD config every frame needs its camera: ``camera`` (a name, or a list with one per frame), else the image path's parent
     directory.  The result is one (1, Hd, Wd) map per frame at DDADResize's shape — what ``simple_test`` returns; the ground depth comes

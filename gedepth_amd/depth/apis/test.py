@@ -8,9 +8,11 @@ engine (apis/inference.py: flip-TTA for KITTI, the single view of DDADResize's s
 map to ten float64 sums on the engine's stream (csrc/eval.hip); the whole split comes back in one copy at the end.  For DDAD the kernel
 resamples the prediction at the ground-truth pixels in float32 (include/gedepth_ddad.h), which is not bit-equal to the host's
 ``F.interpolate``: the largest relative difference measured is 3.4e-7, so a threshold count can move by the pixels whose ratio lies that
-close to 1.25^p.  ``show`` / ``out_dir`` and ``mask_pe`` are not covered.  ``eval_batch=F`` (KITTI protocol, 2 .. 8) runs F frames per forward through the
+close to 1.25^p.  ``show`` / ``out_dir`` and ``mask_pe`` are not covered.  ``eval_batch=F`` (2 .. 8) runs F frames per forward through the
 batched engine (apis/batch_inference.py) and one ``ge_depth_metrics_batch`` call per batch, the next batch's image and ground-truth PNGs
-decoding on a thread pool meanwhile; same rows, same tuples.  Speed: README "KITTI speed" (KITTI); DDAD not measured.
+decoding on a thread pool meanwhile; same rows, same tuples.  With DDAD the batched engine is ``BatchDDADInferencer`` (every slot its own
+camera), the pool decodes the PNG and inflates the ground truth's ``.npz``, and ``ge_depth_metrics_resized_batch`` reduces the batch; the
+rows carry the bits ``eval_batch=1`` gives the same maps.  Speed: README "KITTI speed" (KITTI) and "DDAD speed" (DDAD).
 
 ``strata=StrataSpec(...)`` (with ``device_eval``; KITTI protocol, any ``eval_batch``) adds one ``ge_depth_metrics_strata[_batch]`` call per
 frame or batch behind the unchanged ``ge_depth_metrics[_batch]`` call, on the same stream and the same upload of the ground truth: the
@@ -115,7 +117,7 @@ def _engine_frames(model, data_loader, what, evaluates=True, batch=1):
     bf16 = bool(torch.is_autocast_enabled('cuda') and torch.get_autocast_dtype('cuda') == torch.bfloat16)      # what the caller asks for
     if batch != 1:
         from .batch_inference import check_batch
-        check_batch(batch, spec, 'eval_batch')
+        check_batch(batch, spec, 'eval_batch', ddad=True)               # this loop has a batched engine for either protocol
     eng = engine_for(depther, bf16, config, batch)
     indices = [i for part in data_loader.batch_sampler for i in part]
     frames = [dataset.engine_frame(i) for i in indices]
@@ -224,11 +226,13 @@ def _device_eval_batches(dataset, eng, indices, frames, sums, size, graph, strat
     frames of the loop enter the planes and get a picture)."""
     from .batch_inference import decode_ahead
     from .inference import _decode
-    jobs = [(lambda i=i, f=f: (_decode(f['img']), dataset.gt_raw(i))) for i, f in zip(indices, frames)]
+    jobs = [(lambda i=i, f=f: (_decode(f['img']), dataset.gt_raw(i))) for i, f in zip(indices, frames)]       # DDAD: the PNG and the .npz
+    ddad = dataset.device_protocol == 'ddad'
     row = 0
     for decoded in decode_ahead(jobs, size):
         n = len(decoded)
-        preds = eng.batch([d[0] for d in decoded], graph=graph, to_host=False, paths=[f['img'] for f in frames[row:row + n]])
+        own = dict(cameras=[f['camera'] for f in frames[row:row + n]]) if ddad else {}       # each slot its camera's ground depth and height
+        preds = eng.batch([d[0] for d in decoded], graph=graph, to_host=False, paths=[f['img'] for f in frames[row:row + n]], **own)
         with torch.cuda.stream(eng.stream):
             if errors is not None:
                 ground = strata is not None and _strata_ground(eng, strata, True)
@@ -330,7 +334,7 @@ def single_gpu_test(model, data_loader, pre_eval=False, format_only=False, forma
     ``out_dir/<ori_filename without extension>.npy``).  ``ply_dir``: every image's point cloud as ``ply_dir/<ori_filename with .ply>``
     (``save_point_cloud`` with the image's ``cam_intrinsic`` meta and its KB-crop offsets).  ``device_eval`` (with ``pre_eval``; KITTI or
     DDAD protocol): the module docstring.  ``ground_dir``: every image's ground maps (module docstring); without ``device_eval`` the
-    result is an empty list.  ``eval_batch=F`` (2 .. 8; with ``device_eval``, KITTI protocol, no ``ground_dir``): F frames per forward
+    result is an empty list.  ``eval_batch=F`` (2 .. 8; with ``device_eval``, KITTI or DDAD protocol, no ``ground_dir``): F frames per forward
     (``_device_eval``).  ``engine_graph=False``: the engine of ``device_eval`` runs eagerly and captures no hipGraph.  ``scene_dir`` (KITTI
     protocol; alone): every image's scene cloud as ``scene_dir/<ori_filename with .ply>`` (module docstring); the result is an empty list.
     ``strata`` (a ``core.StrataSpec``; with ``device_eval``, KITTI protocol, any ``eval_batch``): the loop also reduces every map to its

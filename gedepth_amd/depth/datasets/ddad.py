@@ -116,6 +116,45 @@ class DDADDataset(Dataset):
         dev = self.__dict__.setdefault('_gt_upload', PinnedUpload())(np.asarray(gt, dtype=np.float32), pred.device)      # float32 as in pre_eval
         K.depth_metric_sums_resized(pred, dev, self.min_depth, self.max_depth, sums_row)
 
+    def gt_raw(self, index):
+        """Split entry ``index``'s ground truth as ``pre_eval_device`` uploads it, the ``.npz``'s ``depth`` as an (H, W) float32 array: host
+        work only (inflating the file releases the GIL), so a thread may load it ahead of the device."""
+        path = self.img_infos[index]['ann']['depth_map']
+        gt = np.load(path)['depth']
+        if gt.ndim != 2:
+            raise TypeError(f'{path}: the ground truth must be a 2-D depth array, got shape {gt.shape}')
+        return np.ascontiguousarray(gt, dtype=np.float32)
+
+    def pre_eval_device_batch(self, preds, indices, sums_rows, raws=None):
+        """``pre_eval_device`` for n = ``len(indices)`` <= 8 images: ``preds`` a CUDA ``(F, 1, Hd, Wd)`` float32 tensor whose first n maps
+        belong to ``indices``, ``sums_rows`` n rows of the device ``(N, 10)`` float64 buffer.  Each row gets the bits ``pre_eval_device``
+        gives that image.  The n ground truths go up as float32, each through its own reused pinned buffer, on the current stream
+        (``raws``: their ``gt_raw`` arrays when a thread has loaded them ahead); then one ``ge_depth_metrics_resized_batch`` call (two
+        launches) per run of consecutive images whose ground truths have one size — a DDAD split has one, so one call.  Does not
+        synchronise."""
+        from ... import kernels as K
+        n = len(indices)
+        if not (torch.is_tensor(preds) and preds.is_cuda and preds.dim() == 4 and preds.shape[1] == 1 and preds.shape[0] >= n
+                and preds.dtype == torch.float32):
+            raise TypeError(f'pre_eval_device_batch takes a CUDA (F >= {n}, 1, Hd, Wd) float32 tensor, got '
+                            f'{(tuple(preds.shape), preds.dtype, preds.device.type) if torch.is_tensor(preds) else type(preds)}')
+        if not 1 <= n <= 8 or tuple(sums_rows.shape) != (n, 10):
+            raise ValueError(f'pre_eval_device_batch takes 1 .. 8 images and one (10,) row each, got {n} and {tuple(sums_rows.shape)}')
+        raws = [self.gt_raw(i) for i in indices] if raws is None else raws
+        if len(raws) != n:
+            raise ValueError(f'{len(raws)} ground truths for {n} images')
+        uploads = self.__dict__.setdefault('_gt_uploads', [])          # one staging buffer per slot: n copies are in flight at once
+        while len(uploads) < n:
+            uploads.append(PinnedUpload())
+        devs = [up(raw, preds.device) for up, raw in zip(uploads, raws)]
+        start = 0
+        while start < n:                                               # runs of equal ground-truth size
+            end = start + 1
+            while end < n and raws[end].shape == raws[start].shape:
+                end += 1
+            K.depth_metric_sums_resized_batch(preds[start:end], devs[start:end], self.min_depth, self.max_depth, sums_rows[start:end])
+            start = end
+
     def evaluate(self, results, metric='eigen', logger=None, **kwargs):
         if len(results) and isinstance(results[0], np.ndarray):
             results = self.pre_eval(list(results), list(range(len(results))))[0]

@@ -2131,3 +2131,7 @@ from .strata_kernels import depth_metric_sums_strata, depth_metric_sums_strata_b
 # --------------------------------------------------------------------- error images and split-level error planes (csrc/error.hip,
 # include/gedepth_error.h)
 from .error_kernels import error_accumulate, error_accumulate_batch, error_image, error_image_batch  # noqa: E402,F401
+
+# --------------------------------------------------------------------- batched DDAD inference / evaluation (csrc/infer.hip,
+# csrc/eval.hip, include/gedepth_ddad_batch.h)
+from .ddad_batch_kernels import depth_metric_sums_resized_batch, infer_front_ddad_batch  # noqa: E402,F401

@@ -27,8 +27,8 @@ engine; it runs alone, without ``--eval`` or any other output.
 
 ``--device-eval`` (with ``--eval`` and ``--synthetic 0``; KITTI or DDAD protocol) evaluates on the device: frames go through the graphed
 engine (flip-TTA for KITTI, the single view for DDAD) and each map is reduced to its metric sums by a HIP kernel, so no map is copied to the
-host (``single_gpu_test(device_eval=True)``).  ``--eval-batch F`` (KITTI protocol, 2 .. 8) runs F frames per forward and one metric launch
-per batch, with the next batch's image and ground-truth PNGs decoding on a thread pool meanwhile.
+host (``single_gpu_test(device_eval=True)``).  ``--eval-batch F`` (2 .. 8; KITTI or DDAD protocol) runs F frames per forward and one metric
+call per batch, with the next batch's image PNGs and ground truths (KITTI: PNGs, DDAD: compressed ``.npz``) decoding on a thread pool meanwhile.
 
 ``--strata [EDGE ...]`` (with ``--eval --device-eval``; KITTI protocol) also reduces every map per distance bin of the ground truth (bare
 ``--strata``: edges 20 40 60 metres) and per on / off ground class: a LiDAR return is on the ground when it lies within
@@ -72,7 +72,7 @@ def parse_args(argv=None):
     p.add_argument('--device-eval', action='store_true',
                    help='with --eval and --synthetic 0: the graphed inference engine and the metric-sum kernel instead of the host loop')
     p.add_argument('--eval-batch', type=int, default=1,
-                   help='with --device-eval (KITTI protocol): frames per forward, 1 .. 8; the next batch\'s PNGs decode on a thread pool')
+                   help='with --device-eval (KITTI or DDAD protocol): frames per forward, 1 .. 8; the next batch\'s files decode on a thread pool')
     p.add_argument('--strata', nargs='*', type=float, default=None, metavar='EDGE',
                    help='with --eval --device-eval (KITTI protocol): metrics per distance bin (edges in metres; none given: 20 40 60) and '
                         'on / off ground')
