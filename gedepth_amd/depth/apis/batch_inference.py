@@ -81,7 +81,44 @@ def frame_size(img):
     return tuple(np.shape(img)[:2])
 
 
-class BatchDepthInferencer(DepthInferencer):
+class _BatchEngine(DepthInferencer):
+    """What the two engines of ``frames`` = F slots share: the capture key, the head and the tail of ``batch``, the chunks of ``run``
+    and what ``reset`` clears.  The front-end calls, the forward and the order of work on the engine's stream are each engine's own."""
+
+    # plain attributes (the base class derives them from its one frame): a batch keeps lists of its own under these names
+    last_frames = last_ground_depths = None
+
+    def _key(self, ground=False):
+        return super()._key(ground) + ('batch', self.frames)
+
+    def _head(self, imgs, paths):
+        """The frame count of ``batch(imgs)`` against the slots -> ``(n, paths, by default the images that are paths)``."""
+        n = len(imgs)
+        if not 1 <= n <= self.frames:
+            raise ValueError(f'{n} frames for an engine of {self.frames} slots')
+        return n, paths if paths is not None else [i if isinstance(i, str) else None for i in imgs]
+
+    def _maps(self, n, to_host):
+        """The tail of ``batch``, on the engine's stream behind ``_run``: n fresh host arrays, or the view ``static_out[:n]``."""
+        self.last_n = n
+        if not to_host:
+            return self.static_out[:n]
+        host = self.static_out[:n].cpu().numpy()                               # synchronises the engine's stream
+        return [host[f].copy() for f in range(n)]
+
+    def _chunks(self, imgs):
+        """``run``'s frames in batches of F, the next batch decoding ahead -> ``(their slice of imgs, the decoded frames)``."""
+        for k, bgrs in enumerate(decode_ahead([(lambda i=i: _decode(i)) for i in imgs], self.frames)):
+            yield slice(k * self.frames, k * self.frames + len(bgrs)), bgrs
+
+    def reset(self):
+        super().reset()
+        self.last_n = 0                              # the frame count of the last batch
+        self.last_ground_depths = None               # KITTI: the raw (H, W) f32 ground depths the last batch's front end was given
+        self.last_frames = None                      # KITTI: [(device uint8 BGR frame, top, left)] of the last batch, for the error images
+
+
+class BatchDepthInferencer(_BatchEngine):
     """The flip-TTA engine with ``frames`` = F slots (module docstring); KITTI protocol.  ``batch(imgs)`` runs n <= F frames.  Captures are
     keyed as ``DepthInferencer``'s plus ``('batch', F)``; the capture itself (``_run``) and the contract that parameters are updated IN PLACE
     (a replay then sees the new values: ``FusedAdamW`` updates its arena in place) are the base class's."""
@@ -97,9 +134,6 @@ class BatchDepthInferencer(DepthInferencer):
         self.static_in = torch.zeros(s['views'] * F, 5, s['height'], s['width'], device=self.device, dtype=torch.float32)
         self.static_out = torch.empty(F, 1, s['height'], s['width'], device=self.device, dtype=torch.float32)
         self._stagings = [PinnedUpload() for _ in range(F)]
-
-    def _key(self, ground=False):
-        return super()._key(ground) + ('batch', self.frames)
 
     def _body(self, metas, ground=False):
         with torch.no_grad(), torch.autocast('cuda', dtype=torch.bfloat16, enabled=self.bf16):
@@ -121,11 +155,8 @@ class BatchDepthInferencer(DepthInferencer):
         ``paths`` names their files, for the ground depth of the test tree); ``pes``: one raw ground depth per frame or None.  Returns a
         list of n fresh (1, 352, 1216) float32 host arrays, or with ``to_host=False`` the view ``static_out[:n]`` of the static device
         buffer, without synchronising: valid until the next call, ordered on ``self.stream``."""
-        n, s = len(imgs), self.spec
-        if not 1 <= n <= self.frames:
-            raise ValueError(f'{n} frames for an engine of {self.frames} slots')
+        (n, paths), s = self._head(imgs, paths), self.spec
         pes = pes if pes is not None else [None] * n
-        paths = paths if paths is not None else [i if isinstance(i, str) else None for i in imgs]
         bgrs = [_decode(i) for i in imgs]
         for b in bgrs:
             self.front.frame(self, b.shape[0], b.shape[1], None, None)           # a frame smaller than the crop, before any device work
@@ -143,27 +174,15 @@ class BatchDepthInferencer(DepthInferencer):
                                 s['depth_scale'])
             self.last_frames = list(zip(devs, tops, lefts))   # kept for the error images, as last_frame is
             self._run(self._key(), graph, lambda: self._body(metas))
-            self.last_n = n
-            if to_host:
-                host = self.static_out[:n].cpu().numpy()                           # synchronises the engine's stream
-                out = [host[f].copy() for f in range(n)]
-            else:
-                out = self.static_out[:n]
+            out = self._maps(n, to_host)
         cur.wait_stream(self.stream)
         return out
-
-    def reset(self):
-        super().reset()
-        self.last_n = 0                              # the frame count of the last batch
-        self.last_ground_depths = None               # the raw (H, W) f32 ground depths the last batch's front end was given
-        self.last_frames = None                      # [(device uint8 BGR frame, top, left)] of the last batch, for the error images
 
     def run(self, imgs, pes=None, calib=None, cam_height=1.65, graph=True):
         """Any number of frames, in batches of F with the next batch decoding ahead -> one host map per frame, in order."""
         pes = pes if pes is not None else [None] * len(imgs)
-        F, out = self.frames, []
-        for k, bgrs in enumerate(decode_ahead([(lambda i=i: _decode(i)) for i in imgs], F)):
-            part = slice(k * F, k * F + len(bgrs))
+        out = []
+        for part, bgrs in self._chunks(imgs):
             out += self.batch(bgrs, pes[part], calib, cam_height, graph, paths=[i if isinstance(i, str) else None for i in imgs[part]])
         return out
 
@@ -192,7 +211,7 @@ def check_ddad_batch(spec, slots, sizes, pes, cameras, paths, frame_size=None):
     return cams, frame_size
 
 
-class BatchDDADInferencer(DepthInferencer):
+class BatchDDADInferencer(_BatchEngine):
     """The DDAD engine with ``frames`` = F slots (module docstring).  ``batch(imgs)`` runs n <= F frames, which may come from different
     cameras: each slot has its own ground depth and its own entry of ``static_height``.  Captures are keyed as ``DepthInferencer``'s plus
     ``('batch', F)``; the capture itself and the in-place contract on the parameters are the base class's, and so is the rule that one
@@ -214,9 +233,6 @@ class BatchDDADInferencer(DepthInferencer):
         self._heights_host, self._heights_done = torch.empty(F, dtype=torch.float32, pin_memory=True), None
         self._stagings = [PinnedUpload() for _ in range(F)]
 
-    def _key(self, ground=False):
-        return super()._key(ground) + ('batch', self.frames)
-
     def _body(self, metas, ground=False):
         with torch.no_grad(), torch.autocast('cuda', dtype=torch.bfloat16, enabled=self.bf16):
             pred = self.model.encode_decode(self.static_in, metas, rescale=True, **self._forward_kw)
@@ -235,10 +251,7 @@ class BatchDDADInferencer(DepthInferencer):
         list of n fresh (1, Hd, Wd) float32 host arrays, or with ``to_host=False`` the view ``static_out[:n]`` of the static device
         buffer, without synchronising: valid until the next call, ordered on ``self.stream``.  Every argument error is raised before any
         device work."""
-        n, s = len(imgs), self.spec
-        if not 1 <= n <= self.frames:
-            raise ValueError(f'{n} frames for an engine of {self.frames} slots')
-        paths = paths if paths is not None else [i if isinstance(i, str) else None for i in imgs]
+        (n, paths), s = self._head(imgs, paths), self.spec
         if len(paths) != n:
             raise ValueError(f'{len(paths)} paths for {n} frames')
         bgrs = [_decode(i) for i in imgs]
@@ -261,19 +274,14 @@ class BatchDDADInferencer(DepthInferencer):
             self._heights_done = torch.cuda.Event()
             self._heights_done.record()
             self._run(self._key(), graph, lambda: self._body(metas))
-            self.last_n, self.last_cameras = n, cams
-            if to_host:
-                host = self.static_out[:n].cpu().numpy()                           # synchronises the engine's stream
-                out = [host[f].copy() for f in range(n)]
-            else:
-                out = self.static_out[:n]
+            self.last_cameras = cams
+            out = self._maps(n, to_host)
         cur.wait_stream(self.stream)
         return out
 
     def reset(self):
         super().reset()
-        self.last_n = 0                              # the frame count of the last batch
-        self.last_cameras = None                     # and its cameras
+        self.last_cameras = None                     # the cameras of the last batch
 
     def run(self, imgs, pes=None, cameras=None, graph=True):
         """Any number of frames, in batches of F with the next batch decoding ahead -> one host map per frame, in order: the files-to-maps
@@ -287,8 +295,7 @@ class BatchDDADInferencer(DepthInferencer):
             if _ddad_camera(c, p) is None:
                 raise ValueError(f'no camera for a frame: pass cameras= (out of {", ".join(sorted(loading._DDAD_CAMERA_HEIGHT))}) or image '
                                  'paths whose parent directory is the camera name')
-        F, out = self.frames, []
-        for k, bgrs in enumerate(decode_ahead([(lambda i=i: _decode(i)) for i in imgs], F)):
-            part = slice(k * F, k * F + len(bgrs))
+        out = []
+        for part, bgrs in self._chunks(imgs):
             out += self.batch(bgrs, pes[part], cameras[part], graph, paths=paths[part])
         return out

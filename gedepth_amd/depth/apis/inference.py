@@ -287,6 +287,16 @@ class DepthInferencer:
         self.graphs, self.calls, self.captures, self.replays = {}, {}, 0, 0
         self.frame_size = None                   # DDAD: the (H, W) of the frames this engine has taken
 
+    @property
+    def last_frames(self):
+        """``[last_frame]`` or None: what the batched engines keep per slot under this name, so a loop reads one name from any engine."""
+        return None if self.last_frame is None else [self.last_frame]
+
+    @property
+    def last_ground_depths(self):
+        """``[last_ground_depth]`` or None, as ``last_frames``."""
+        return None if self.last_ground_depth is None else [self.last_ground_depth]
+
     # ---- ground depth
     def _cache(self, key, make):
         if key not in self._pe:

@@ -4,27 +4,28 @@ also goes through the model's ``show_result`` (a colorized image, or the raw ``.
 through ``save_point_cloud`` (a coloured point cloud per image, a binary ``.ply``).
 
 ``device_eval=True`` (opt-in; the KITTI and the DDAD protocol) evaluates where the prediction is: every frame goes through the graphed
-engine (apis/inference.py: flip-TTA for KITTI, the single view of DDADResize's shape for DDAD) and ``dataset.pre_eval_device`` reduces its
-map to ten float64 sums on the engine's stream (csrc/eval.hip); the whole split comes back in one copy at the end.  For DDAD the kernel
+engine (apis/inference.py: flip-TTA for KITTI, the single view of DDADResize's shape for DDAD) and ``dataset.pre_eval_device_batch``
+reduces its map to ten float64 sums on the engine's stream (csrc/eval.hip: ``ge_depth_metrics_batch`` or
+``ge_depth_metrics_resized_batch``, with one frame); the whole split comes back in one copy at the end.  For DDAD the kernel
 resamples the prediction at the ground-truth pixels in float32 (include/gedepth_ddad.h), which is not bit-equal to the host's
 ``F.interpolate``: the largest relative difference measured is 3.4e-7, so a threshold count can move by the pixels whose ratio lies that
 close to 1.25^p.  ``show`` / ``out_dir`` and ``mask_pe`` are not covered.  ``eval_batch=F`` (2 .. 8) runs F frames per forward through the
-batched engine (apis/batch_inference.py) and one ``ge_depth_metrics_batch`` call per batch, the next batch's image and ground-truth PNGs
-decoding on a thread pool meanwhile; same rows, same tuples.  With DDAD the batched engine is ``BatchDDADInferencer`` (every slot its own
-camera), the pool decodes the PNG and inflates the ground truth's ``.npz``, and ``ge_depth_metrics_resized_batch`` reduces the batch; the
+batched engine (apis/batch_inference.py) and the same one call per batch, now with F frames, the next batch's image and ground-truth
+PNGs decoding on a thread pool meanwhile; same rows, same tuples.  Either way the step behind a forward is ``_reduce``.  With DDAD the
+batched engine is ``BatchDDADInferencer`` (every slot its own camera), the pool decodes the PNG and inflates the ground truth's ``.npz``, and ``ge_depth_metrics_resized_batch`` reduces the batch; the
 rows carry the bits ``eval_batch=1`` gives the same maps.  Speed: README "KITTI speed" (KITTI) and "DDAD speed" (DDAD).
 
-``strata=StrataSpec(...)`` (with ``device_eval``; KITTI protocol, any ``eval_batch``) adds one ``ge_depth_metrics_strata[_batch]`` call per
-frame or batch behind the unchanged ``ge_depth_metrics[_batch]`` call, on the same stream and the same upload of the ground truth: the
+``strata=StrataSpec(...)`` (with ``device_eval``; KITTI protocol, any ``eval_batch``) adds one ``ge_depth_metrics_strata_batch`` call per
+frame or batch behind the unchanged ``ge_depth_metrics_batch`` call, on the same stream and the same upload of the ground truth: the
 ten sums per distance bin and on / off ground class (include/gedepth_strata.h), the ground plane being what the engine fed the front end
-(``last_ground_depth`` / ``last_ground_depths``).  Both buffers come back in the loop's one synchronisation and the loop returns
+(``last_ground_depths`` of either engine).  Both buffers come back in the loop's one synchronisation and the loop returns
 ``(results, rows)``, ``rows`` (N, S, 10) float64; ``dataset.evaluate_strata`` prints the table.  Speed: README "Where the error is".
 
 ``errors=ErrorMaps(...)`` (with ``device_eval``; KITTI protocol, any ``eval_batch``, also with ``strata`` and ``ground_dir``) shows where in
 the picture the error is (include/gedepth_error.h): behind the metric call, on the same upload of the ground truth, one
-``ge_error_accumulate[_batch]`` call adds every return's abs-rel error into a per-pixel float64 sum and uint32 count held by ``errors``,
-and with ``errors.out_dir`` one ``ge_error_image[_batch]`` call paints the batch's error pictures over the frames the front end was fed
-(``last_frame`` / ``last_frames``).  A batch's pictures reach the host in one copy and are encoded on a thread pool while the next batch
+``ge_error_accumulate_batch`` call adds every return's abs-rel error into a per-pixel float64 sum and uint32 count held by ``errors``,
+and with ``errors.out_dir`` one ``ge_error_image_batch`` call paints the batch's error pictures over the frames the front end was fed
+(``last_frames`` of either engine).  A batch's pictures reach the host in one copy and are encoded on a thread pool while the next batch
 computes; the planes come back in the loop's one synchronisation.  The loop returns what it returns without ``errors``.  Speed: README
 "Where in the image the error is".
 
@@ -168,7 +169,7 @@ class _ErrorPictures:
         from concurrent.futures import ThreadPoolExecutor
         from .batch_inference import DECODE_WORKERS
         self.device = device
-        self.dev = torch.empty(slots, 352, 1216, 3, device=device, dtype=torch.uint8)          # what ge_error_image[_batch] writes
+        self.dev = torch.empty(slots, 352, 1216, 3, device=device, dtype=torch.uint8)          # what ge_error_image_batch writes
         self.host = torch.empty(slots, 352, 1216, 3, dtype=torch.uint8, pin_memory=True)
         # DECODE_WORKERS threads whatever the batch size: one picture takes longer to encode than one frame to compute, and the pictures
         # queue up behind the loop (at most MAX_QUEUED of them: then the loop waits for the oldest)
@@ -218,12 +219,40 @@ def _error_file(dataset, index, out_dir):
     return osp.join(out_dir, replace_str(dataset.img_infos[index]['filename']))
 
 
-def _device_eval_batches(dataset, eng, indices, frames, sums, size, graph, strata=None, rows=None, errors=None, pictures=None, real=None):
+def _strata_ground(eng, strata):
+    """The ground depths the engine's front end was last fed, one per frame; None when ``strata`` has no ground class."""
+    if not strata.ground:
+        return None
+    if eng.last_ground_depths is None:
+        raise NotImplementedError('strata with spec.ground: the model\'s front end was fed no ground depth; use StrataSpec(ground=False)')
+    return eng.last_ground_depths
+
+
+def _reduce(dataset, eng, preds, indices, raws, row, sums, strata=None, rows=None, errors=None, pictures=None, real=None):
+    """What follows a forward of either engine, on its stream: the n = ``len(indices)`` first maps of ``preds`` (F >= n, 1, H, W) fill
+    rows ``row ..`` of ``sums`` (with ``strata`` also of ``rows``, from the ground depths the front end was fed; with ``errors`` the planes
+    and pictures, from the frames it was fed: only the first ``real`` frames of the loop enter them), all on one upload of the ground
+    truths (``raws``: decoded ahead, or None).  The pictures' copy to the host is queued behind."""
+    n = len(indices)
+    part = slice(row, row + n)
+    with torch.cuda.stream(eng.stream):
+        if errors is not None:
+            count = min(max(real - row, 0), n)
+            dataset.pre_eval_device_errors_batch(preds, indices, errors, eng.last_frames, pictures and pictures.dev, raws=raws,
+                                                 sums_rows=sums[part], strata=strata, rows=None if strata is None else rows[part],
+                                                 grounds=None if strata is None else _strata_ground(eng, strata), count=count)
+            if pictures and count:
+                pictures.copy(count, [_error_file(dataset, i, errors.out_dir) for i in indices[:count]])
+        elif strata is None:
+            dataset.pre_eval_device_batch(preds, indices, sums[part], raws=raws)
+        else:
+            dataset.pre_eval_device_strata_batch(preds, indices, rows[part], strata, _strata_ground(eng, strata), raws=raws,
+                                                 sums_rows=sums[part])
+
+
+def _device_eval_batches(dataset, eng, indices, frames, size, graph, **reduce):
     """``_device_eval``'s frames in batches of ``size``: the pool decodes the next batch's image and ground-truth PNGs while the batched
-    engine and ``pre_eval_device_batch`` work on the current one; batch k fills rows ``k * size ..`` of ``sums`` (and, with ``strata``, of
-    ``rows``, from the same uploads and the ground depths the batch's front end was fed; with ``errors``, the planes and pictures of
-    ``pre_eval_device_errors_batch``, from the same uploads and the frames the batch's front end was fed; only the first ``real``
-    frames of the loop enter the planes and get a picture)."""
+    engine and ``_reduce`` (its keyword arguments: ``reduce``) work on the current one; batch k fills rows ``k * size ..``."""
     from .batch_inference import decode_ahead
     from .inference import _decode
     jobs = [(lambda i=i, f=f: (_decode(f['img']), dataset.gt_raw(i))) for i, f in zip(indices, frames)]       # DDAD: the PNG and the .npz
@@ -233,42 +262,20 @@ def _device_eval_batches(dataset, eng, indices, frames, sums, size, graph, strat
         n = len(decoded)
         own = dict(cameras=[f['camera'] for f in frames[row:row + n]]) if ddad else {}       # each slot its camera's ground depth and height
         preds = eng.batch([d[0] for d in decoded], graph=graph, to_host=False, paths=[f['img'] for f in frames[row:row + n]], **own)
-        with torch.cuda.stream(eng.stream):
-            if errors is not None:
-                ground = strata is not None and _strata_ground(eng, strata, True)
-                dataset.pre_eval_device_errors_batch(preds, indices[row:row + n], errors, eng.last_frames, pictures and pictures.dev,
-                                                     raws=[d[1] for d in decoded], sums_rows=sums[row:row + n], strata=strata,
-                                                     rows=None if strata is None else rows[row:row + n], grounds=ground or None,
-                                                     count=min(max(real - row, 0), n))
-                if pictures and real > row:
-                    pictures.copy(min(real - row, n), [_error_file(dataset, i, errors.out_dir) for i in indices[row:min(real, row + n)]])
-            elif strata is None:
-                dataset.pre_eval_device_batch(preds, indices[row:row + n], sums[row:row + n], raws=[d[1] for d in decoded])
-            else:
-                dataset.pre_eval_device_strata_batch(preds, indices[row:row + n], rows[row:row + n], strata, _strata_ground(eng, strata, True),
-                                                     raws=[d[1] for d in decoded], sums_rows=sums[row:row + n])
+        _reduce(dataset, eng, preds, indices[row:row + n], [d[1] for d in decoded], row, **reduce)
         row += n
-
-
-def _strata_ground(eng, strata, batched=False):
-    """What the engine's front end was last fed as ground depth (a tensor, or the batch's list), None when ``strata`` has no ground class."""
-    if not strata.ground:
-        return None
-    ground = getattr(eng, 'last_ground_depths' if batched else 'last_ground_depth', None)
-    if ground is None:
-        raise NotImplementedError('strata with spec.ground: the model\'s front end was fed no ground depth; use StrataSpec(ground=False)')
-    return ground
 
 
 def _device_eval(model, data_loader, pre_eval, format_only, show, out_dir, ply_dir=None, ground_dir=None, eval_batch=1, engine_graph=True,
                  strata=None, errors=None):
-    """The ``device_eval`` loop of ``single_gpu_test``: the list of metric tuples ``pre_eval`` yields, in the sampler's order.
-    ``eval_batch=F > 1``: the sampler's indices in batches of F through the batched engine and ``pre_eval_device_batch``, image and
-    ground-truth PNGs of the next batch decoding ahead; same rows of the same buffer, same one copy at the end.  ``strata`` (a
-    ``core.StrataSpec``): every image's sums per stratum as well, into an (N, S, 10) buffer that comes back in the same synchronisation;
-    the result is ``(the list, rows)``.  ``errors`` (a ``core.ErrorMaps``): every image also goes into its error planes and, with its
-    ``out_dir``, into an error picture (``pre_eval_device_errors[_batch]``, which then makes the metric and strata calls itself, on the
-    same upload); the planes come back in the same synchronisation and the result is unchanged."""
+    """The ``device_eval`` loop of ``single_gpu_test``: the list of metric tuples ``pre_eval`` yields, in the sampler's order.  Every
+    forward is followed by ``_reduce``, with one frame (``eval_batch=1``: the single-frame engine, no pool) or with F.
+    ``eval_batch=F > 1``: the sampler's indices in batches of F through the batched engine, image and ground-truth PNGs of the next
+    batch decoding ahead; same rows of the same buffer, same one copy at the end.  ``strata`` (a ``core.StrataSpec``): every image's sums
+    per stratum as well, into an (N, S, 10) buffer that comes back in the same synchronisation; the result is ``(the list, rows)``.
+    ``errors`` (a ``core.ErrorMaps``): every image also goes into its error planes and, with its ``out_dir``, into an error picture
+    (``pre_eval_device_errors_batch``, which then makes the metric and strata calls itself, on the same upload); the planes come back in
+    the same synchronisation and the result is unchanged."""
     from ..core.evaluation import metrics_from_sums
     dataset = data_loader.dataset
     if not pre_eval or format_only:
@@ -286,27 +293,18 @@ def _device_eval(model, data_loader, pre_eval, format_only, show, out_dir, ply_d
         real = _unpadded(len(indices), len(dataset), rank, world)      # a padded shard's last frame is the split's first again: keep it out
         errors.begin(eng.device, dataset.eval_rect(352, 1216))
         pictures = _ErrorPictures(eval_batch, eng.device) if errors.out_dir else None
+    reduce = dict(sums=sums, strata=strata, rows=rows, errors=errors, pictures=pictures, real=real)
     try:
         if eval_batch != 1:
-            _device_eval_batches(dataset, eng, indices, frames, sums, eval_batch, engine_graph, strata, rows, errors, pictures, real)
-        else:
+            _device_eval_batches(dataset, eng, indices, frames, eval_batch, engine_graph, **reduce)
+        else:                                                          # one frame at a time: no pool, nothing decodes ahead
             for row, (i, frame) in enumerate(zip(indices, frames)):
                 if ground_dir:
                     maps = eng.ground_maps(to_host=False, graph=engine_graph, **frame)
                     pred = maps['depth']
                 else:
                     pred = eng(to_host=False, graph=engine_graph, **frame)
-                with torch.cuda.stream(eng.stream):
-                    if errors is not None and row < real:
-                        dataset.pre_eval_device_errors(pred, i, errors, eng.last_frame, pictures and pictures.dev[0], sums_row=sums[row],
-                                                       strata=strata, rows=None if strata is None else rows[row],
-                                                       ground=None if strata is None else _strata_ground(eng, strata))
-                        if pictures:
-                            pictures.copy(1, [_error_file(dataset, i, errors.out_dir)])
-                    elif strata is None:
-                        dataset.pre_eval_device(pred, i, sums[row])
-                    else:
-                        dataset.pre_eval_device_strata(pred, i, rows[row], strata, _strata_ground(eng, strata), sums_row=sums[row])
+                _reduce(dataset, eng, pred[None], [i], None, row, **reduce)
                 if ground_dir:
                     depther.show_ground(maps, _ground_file(dataset, i, ground_dir))
     finally:

@@ -99,26 +99,16 @@ class DDADDataset(Dataset):
         return out_metrics, out_preds
 
     def pre_eval_device(self, pred, index, sums_row):
-        """``pre_eval`` of one image where the prediction already is: ``pred`` a CUDA ``(1, Hd, Wd)`` float32 map, ``sums_row`` one row of
-        a device ``(N, 10)`` float64 buffer that receives the image's metric sums (``core.metrics_from_sums`` makes the tuple of
-        ``pre_eval`` from it).  The ground truth goes up as float32 through a reused pinned buffer on the current stream; the kernel
-        resamples the prediction at the ground-truth pixels that count (bilinear, align_corners=True, in float32: not bit-equal to
-        ``F.interpolate`` on the CPU, see include/gedepth_ddad.h) and reduces in the same pass, so the resized map is never written.
-        Does not synchronise: the row is valid once the current stream has reached this point."""
-        from ... import kernels as K
+        """``pre_eval_device_batch`` of one image: ``pred`` a CUDA ``(1, Hd, Wd)`` float32 map, ``sums_row`` one (10,) row of the device
+        ``(N, 10)`` float64 buffer."""
         if not (torch.is_tensor(pred) and pred.is_cuda and pred.dim() == 3 and pred.shape[0] == 1 and pred.dtype == torch.float32):
             raise TypeError('pre_eval_device takes a CUDA (1, Hd, Wd) float32 prediction, got '
                             f'{(tuple(pred.shape), pred.dtype, pred.device.type) if torch.is_tensor(pred) else type(pred)}')
-        path = self.img_infos[index]['ann']['depth_map']
-        gt = np.load(path)['depth']
-        if gt.ndim != 2:
-            raise TypeError(f'{path}: the ground truth must be a 2-D depth array, got shape {gt.shape}')
-        dev = self.__dict__.setdefault('_gt_upload', PinnedUpload())(np.asarray(gt, dtype=np.float32), pred.device)      # float32 as in pre_eval
-        K.depth_metric_sums_resized(pred, dev, self.min_depth, self.max_depth, sums_row)
+        self._reduce_device(pred[None], [index], sums_row[None], [self.gt_raw(index)])
 
     def gt_raw(self, index):
-        """Split entry ``index``'s ground truth as ``pre_eval_device`` uploads it, the ``.npz``'s ``depth`` as an (H, W) float32 array: host
-        work only (inflating the file releases the GIL), so a thread may load it ahead of the device."""
+        """Split entry ``index``'s ground truth as the device evaluation uploads it, the ``.npz``'s ``depth`` as an (H, W) float32 array
+        (float32 as in ``pre_eval``): host work only (inflating the file releases the GIL), so a thread may load it ahead of the device."""
         path = self.img_infos[index]['ann']['depth_map']
         gt = np.load(path)['depth']
         if gt.ndim != 2:
@@ -126,13 +116,15 @@ class DDADDataset(Dataset):
         return np.ascontiguousarray(gt, dtype=np.float32)
 
     def pre_eval_device_batch(self, preds, indices, sums_rows, raws=None):
-        """``pre_eval_device`` for n = ``len(indices)`` <= 8 images: ``preds`` a CUDA ``(F, 1, Hd, Wd)`` float32 tensor whose first n maps
-        belong to ``indices``, ``sums_rows`` n rows of the device ``(N, 10)`` float64 buffer.  Each row gets the bits ``pre_eval_device``
-        gives that image.  The n ground truths go up as float32, each through its own reused pinned buffer, on the current stream
-        (``raws``: their ``gt_raw`` arrays when a thread has loaded them ahead); then one ``ge_depth_metrics_resized_batch`` call (two
-        launches) per run of consecutive images whose ground truths have one size — a DDAD split has one, so one call.  Does not
-        synchronise."""
-        from ... import kernels as K
+        """``pre_eval`` of n = ``len(indices)`` <= 8 images where the predictions already are: ``preds`` a CUDA ``(F, 1, Hd, Wd)`` float32
+        tensor whose first n maps belong to ``indices``, ``sums_rows`` n rows of a device ``(N, 10)`` float64 buffer that receive the
+        images' metric sums (``core.metrics_from_sums`` makes the tuple of ``pre_eval`` from a row); a row carries the same bits whatever
+        n its image is reduced with.  The n ground truths go up as float32, each through its own reused pinned buffer, on the current
+        stream (``raws``: their ``gt_raw`` arrays when a thread has loaded them ahead); then one ``ge_depth_metrics_resized_batch`` call
+        (two launches) per run of consecutive images whose ground truths have one size -- a DDAD split has one, so one call.  The kernel
+        resamples the prediction at the ground-truth pixels that count (bilinear, align_corners=True, in float32: not bit-equal to
+        ``F.interpolate`` on the CPU, see include/gedepth_ddad.h) and reduces in the same pass, so the resized map is never written.
+        Does not synchronise: the rows are valid once the current stream has reached this point."""
         n = len(indices)
         if not (torch.is_tensor(preds) and preds.is_cuda and preds.dim() == 4 and preds.shape[1] == 1 and preds.shape[0] >= n
                 and preds.dtype == torch.float32):
@@ -143,7 +135,13 @@ class DDADDataset(Dataset):
         raws = [self.gt_raw(i) for i in indices] if raws is None else raws
         if len(raws) != n:
             raise ValueError(f'{len(raws)} ground truths for {n} images')
-        uploads = self.__dict__.setdefault('_gt_uploads', [])          # one staging buffer per slot: n copies are in flight at once
+        self._reduce_device(preds, indices, sums_rows, raws)
+
+    def _reduce_device(self, preds, indices, sums_rows, raws):
+        """The uploads and kernel calls of ``pre_eval_device_batch``, behind its checks."""
+        from ... import kernels as K
+        n = len(indices)
+        uploads = self.__dict__.setdefault('_gt_uploads', [])          # one staging buffer per slot, made on first use: n copies are in flight at once
         while len(uploads) < n:
             uploads.append(PinnedUpload())
         devs = [up(raw, preds.device) for up, raw in zip(uploads, raws)]

@@ -32,6 +32,11 @@ _P_RECT = {
 }
 
 
+def _one(t):
+    """A one-frame argument as the batch of one ``KITTIDataset._reduce_device`` takes (a view); None stays None."""
+    return None if t is None else t[None]
+
+
 @DATASETS.register_module()
 class KITTIDataset(Dataset):
     """Layout (reference docstring, kitti.py:103-134): ``data_root/input/<date>/<drive>/image_02/data/*.png``,
@@ -139,23 +144,6 @@ class KITTIDataset(Dataset):
             return int(0.3324324 * gh), int(0.91351351 * gh), int(0.0359477 * gw), int(0.96405229 * gw)
         return 0, gh, 0, gw
 
-    def pre_eval_device(self, pred, index, sums_row):
-        """``pre_eval`` of one image where the prediction already is: ``pred`` a CUDA ``(1, 352, 1216)`` float32 map, ``sums_row`` one row
-        of a device ``(N, 10)`` float64 buffer that receives the image's metric sums (``core.metrics_from_sums`` makes the tuple of
-        ``pre_eval`` from it).  The ground-truth PNG goes up undivided, as uint16, through a reused pinned buffer on the current stream;
-        the KB crop, the Garg / Eigen rectangle and the depth mask are applied by the kernel.  Does not synchronise: the row is valid once
-        the current stream has reached this point."""
-        import torch
-        from ... import kernels as K
-        if not (torch.is_tensor(pred) and pred.is_cuda and tuple(pred.shape) == (1, 352, 1216) and pred.dtype == torch.float32):
-            raise TypeError('pre_eval_device takes a CUDA (1, 352, 1216) float32 prediction, got '
-                            f'{tuple(pred.shape) if torch.is_tensor(pred) else type(pred)}')
-        raw = self.gt_raw(index)
-        h, w = raw.shape
-        dev = self.__dict__.setdefault('_gt_upload', PinnedUpload())(raw, pred.device)      # the staging buffer, made on first use
-        top, left = int(h - 352), int((w - 1216) / 2)                   # eval_kb_crop
-        K.depth_metric_sums(pred, dev, top, left, self.eval_rect(352, 1216), self.depth_scale, self.min_depth, self.max_depth, sums_row)
-
     def gt_raw(self, index):
         """Split entry ``index``'s ground-truth PNG as it is on disk, an (H, W) uint16 array at least as large as the KB crop: host work
         only, so a thread may decode it ahead of the device."""
@@ -168,155 +156,63 @@ class KITTIDataset(Dataset):
             raise ValueError(f'{path}: ground truth {(h, w)} is smaller than the KB crop (352, 1216)')
         return raw
 
-    def pre_eval_device_batch(self, preds, indices, sums_rows, raws=None):
-        """``pre_eval_device`` for n = ``len(indices)`` <= 8 images in one ``ge_depth_metrics_batch`` call (two launches instead of 2 n):
-        ``preds`` a CUDA ``(F, 1, 352, 1216)`` float32 tensor whose first n maps belong to ``indices``, ``sums_rows`` n rows of the device
-        ``(N, 10)`` float64 buffer.  Each row gets the bits ``pre_eval_device`` gives that image.  The n ground truths go up undivided,
-        each through its own reused pinned buffer, on the current stream; ``raws``: their ``gt_raw`` arrays when a thread has decoded them
-        ahead.  Does not synchronise."""
+    def _reduce_device(self, what, preds, indices, raws=None, *, sums_rows=None, strata=None, rows=None, grounds=None, errors=None,
+                       frames=None, outs=None, count=None):
+        """What the six ``pre_eval_device*`` methods do, for n = ``len(indices)`` in 1 .. 8 images, in the words of the public method
+        ``what``: ``preds`` a CUDA ``(F >= n, 1, 352, 1216)`` float32 tensor whose first n maps belong to ``indices``.  The n ground-truth
+        PNGs go up undivided, as uint16, each through its own reused pinned buffer, on the current stream (``raws``: their ``gt_raw``
+        arrays when a thread has decoded them ahead); the KB crop, the Garg / Eigen rectangle and the depth mask are applied by the kernels.
+        On these uploads, one call each, in this order:
+
+        * ``sums_rows`` (n rows of a device ``(N, 10)`` float64 buffer): ``ge_depth_metrics_batch`` writes every image's ten metric sums
+          (``core.metrics_from_sums`` makes the tuple of ``pre_eval`` from a row);
+        * ``strata`` (a ``core.StrataSpec``) with ``rows`` (n (S, 10) blocks of a device (N, S, 10) float64 buffer) and ``grounds`` (the
+          frames' raw (H, W) float32 ground depths on the device, what the front end was fed; read only with ``strata.ground``):
+          ``ge_depth_metrics_strata_batch`` writes the sums per stratum;
+        * ``errors`` (a ``core.ErrorMaps`` after ``begin``): ``ge_error_accumulate_batch`` adds the first ``count`` = m <= n images
+          (default: all), in index order, into its planes, and with ``errors.out_dir`` ``ge_error_image_batch`` paints them over
+          ``frames`` (the n (uploaded (H, W, 3) uint8 BGR frame, top, left) the engine keeps as ``last_frames``) into the first m blocks of
+          ``outs`` (a CUDA (F >= m, 352, 1216, 3) uint8 tensor, made when None) -- returned as (m, 352, 1216, 3), else None.  The loop keeps
+          a padded shard's repeated frames out of planes and pictures with ``count``; the metric and strata calls still cover all n.
+
+        Every image's results carry the same bits whatever n it is reduced with.  Does not synchronise: the results are valid once the
+        current stream has reached this point."""
         import torch
         from ... import kernels as K
-        n = len(indices)
+        n, one = len(indices), int(not what.endswith('_batch'))         # the one-frame forms hand in ``pred[None]``
         if not (torch.is_tensor(preds) and preds.is_cuda and preds.dim() == 4 and tuple(preds.shape[1:]) == (1, 352, 1216)
                 and preds.shape[0] >= n and preds.dtype == torch.float32):
-            raise TypeError(f'pre_eval_device_batch takes a CUDA (F >= {n}, 1, 352, 1216) float32 tensor, got '
-                            f'{tuple(preds.shape) if torch.is_tensor(preds) else type(preds)}')
-        if not 1 <= n <= 8 or tuple(sums_rows.shape) != (n, 10):
-            raise ValueError(f'pre_eval_device_batch takes 1 .. 8 images and one (10,) row each, got {n} and {tuple(sums_rows.shape)}')
-        raws = [self.gt_raw(i) for i in indices] if raws is None else raws
-        uploads = self.__dict__.setdefault('_gt_uploads', [])          # one staging buffer per slot: n copies are in flight at once
-        while len(uploads) < n:
-            uploads.append(PinnedUpload())
-        devs = [up(raw, preds.device) for up, raw in zip(uploads, raws)]
-        tops = [int(r.shape[0] - 352) for r in raws]                    # eval_kb_crop
-        lefts = [int((r.shape[1] - 1216) / 2) for r in raws]
-        K.depth_metric_sums_batch(preds, devs, tops, lefts, self.eval_rect(352, 1216), self.depth_scale, self.min_depth, self.max_depth,
-                                  sums_rows)
-
-    def pre_eval_device_strata(self, pred, index, rows, spec, ground, sums_row=None):
-        """``pre_eval_device`` per stratum of ``spec`` (``core.StrataSpec``): ``rows`` one (S, 10) block of a device (N, S, 10) float64 buffer,
-        ``ground`` the frame's raw (H, W) float32 ground depth on the device (what the front end was fed; ignored unless ``spec.ground``).
-        ``sums_row``: also run ``pre_eval_device``'s own call into this (10,) row, on the same upload of the ground truth.  Does not
-        synchronise."""
-        import torch
-        from ... import kernels as K
-        if not (torch.is_tensor(pred) and pred.is_cuda and tuple(pred.shape) == (1, 352, 1216) and pred.dtype == torch.float32):
-            raise TypeError('pre_eval_device_strata takes a CUDA (1, 352, 1216) float32 prediction, got '
-                            f'{tuple(pred.shape) if torch.is_tensor(pred) else type(pred)}')
-        if spec.ground and ground is None:
-            raise ValueError('pre_eval_device_strata: spec.ground needs the frame\'s ground depth')
-        raw = self.gt_raw(index)
-        h, w = raw.shape
-        dev = self.__dict__.setdefault('_gt_upload', PinnedUpload())(raw, pred.device)      # one upload for both calls
-        top, left = int(h - 352), int((w - 1216) / 2)                   # eval_kb_crop
-        limits = (self.depth_scale, self.min_depth, self.max_depth)
-        if sums_row is not None:
-            K.depth_metric_sums(pred, dev, top, left, self.eval_rect(352, 1216), *limits, sums_row)
-        K.depth_metric_sums_strata(pred, dev, top, left, self.eval_rect(352, 1216), *limits, rows, spec.edges,
-                                   ground if spec.ground else None, spec.ground_tol)
-
-    def pre_eval_device_strata_batch(self, preds, indices, rows, spec, grounds, raws=None, sums_rows=None):
-        """``pre_eval_device_strata`` for n = ``len(indices)`` <= 8 images in one ``ge_depth_metrics_strata_batch`` call: ``rows`` n
-        (S, 10) blocks, ``grounds`` the n frames' ground depths, ``raws`` as in ``pre_eval_device_batch``.  ``sums_rows``: also run
-        ``pre_eval_device_batch``'s own call into these (n, 10) rows, on the same uploads.  Does not synchronise."""
-        import torch
-        from ... import kernels as K
-        n = len(indices)
-        if not (torch.is_tensor(preds) and preds.is_cuda and preds.dim() == 4 and tuple(preds.shape[1:]) == (1, 352, 1216)
-                and preds.shape[0] >= n and preds.dtype == torch.float32):
-            raise TypeError(f'pre_eval_device_strata_batch takes a CUDA (F >= {n}, 1, 352, 1216) float32 tensor, got '
-                            f'{tuple(preds.shape) if torch.is_tensor(preds) else type(preds)}')
-        if not 1 <= n <= 8 or tuple(rows.shape) != (n, spec.count, 10):
-            raise ValueError(f'pre_eval_device_strata_batch takes 1 .. 8 images and one ({spec.count}, 10) block each, got {n} and '
-                             f'{tuple(rows.shape)}')
-        if spec.ground and (grounds is None or len(grounds) != n):
-            raise ValueError('pre_eval_device_strata_batch: spec.ground needs every frame\'s ground depth')
-        raws = [self.gt_raw(i) for i in indices] if raws is None else raws
-        uploads = self.__dict__.setdefault('_gt_uploads', [])          # pre_eval_device_batch's staging buffers
-        while len(uploads) < n:
-            uploads.append(PinnedUpload())
-        devs = [up(raw, preds.device) for up, raw in zip(uploads, raws)]
-        tops = [int(r.shape[0] - 352) for r in raws]                    # eval_kb_crop
-        lefts = [int((r.shape[1] - 1216) / 2) for r in raws]
-        limits = (self.depth_scale, self.min_depth, self.max_depth)
-        if sums_rows is not None:
-            K.depth_metric_sums_batch(preds, devs, tops, lefts, self.eval_rect(352, 1216), *limits, sums_rows)
-        K.depth_metric_sums_strata_batch(preds, devs, tops, lefts, self.eval_rect(352, 1216), *limits, rows, spec.edges,
-                                         list(grounds) if spec.ground else None, spec.ground_tol)
-
-    def pre_eval_device_errors(self, pred, index, errors, frame, out=None, raw=None, *, sums_row=None, strata=None, rows=None, ground=None):
-        """One image into the planes of ``errors`` (``core.ErrorMaps`` after ``begin``): ``ge_error_accumulate`` with the dataset's
-        ``eval_rect(352, 1216)``, ``depth_scale``, ``min_depth`` and ``max_depth``; with ``errors.out_dir`` also ``ge_error_image`` of the
-        image over ``frame`` = (the uploaded (H, W, 3) uint8 BGR frame, top, left), what the engine keeps as ``last_frame``, into ``out``
-        (a CUDA (352, 1216, 3) uint8 tensor, made when None) — returned, else None.  ``raw``: the ``gt_raw`` array when a thread has
-        decoded it ahead.  ``sums_row``: also run ``pre_eval_device``'s own call into this (10,) row; ``strata`` with ``rows`` and
-        ``ground``: also ``pre_eval_device_strata``'s; all on one upload of the ground truth.  Does not synchronise."""
-        import torch
-        from ... import kernels as K
-        if not (torch.is_tensor(pred) and pred.is_cuda and tuple(pred.shape) == (1, 352, 1216) and pred.dtype == torch.float32):
-            raise TypeError('pre_eval_device_errors takes a CUDA (1, 352, 1216) float32 prediction, got '
-                            f'{tuple(pred.shape) if torch.is_tensor(pred) else type(pred)}')
-        if errors.device_sum is None:
-            raise ValueError('pre_eval_device_errors: errors holds no device planes (ErrorMaps.begin makes them)')
-        if strata is not None and (rows is None or (strata.ground and ground is None)):
-            raise ValueError('pre_eval_device_errors: strata needs rows and, with spec.ground, the frame\'s ground depth')
-        raw = self.gt_raw(index) if raw is None else raw
-        h, w = raw.shape
-        top, left = int(h - 352), int((w - 1216) / 2)                   # eval_kb_crop
-        if errors.out_dir:
-            bgr, ftop, fleft = frame
-            if (ftop, fleft) != (top, left) or tuple(bgr.shape[:2]) != (h, w):
-                raise ValueError(f'pre_eval_device_errors: the frame {tuple(bgr.shape[:2])} at {(ftop, fleft)} is not the ground truth\'s '
-                                 f'{(h, w)} at {(top, left)}')
-        dev = self.__dict__.setdefault('_gt_upload', PinnedUpload())(raw, pred.device)      # one upload for every call below
-        rect, limits = self.eval_rect(352, 1216), (self.depth_scale, self.min_depth, self.max_depth)
-        if sums_row is not None:
-            K.depth_metric_sums(pred, dev, top, left, rect, *limits, sums_row)
+            takes = 'a CUDA (1, 352, 1216) float32 prediction' if one else f'a CUDA (F >= {n}, 1, 352, 1216) float32 tensor'
+            raise TypeError(f'{what} takes {takes}, got {tuple(preds.shape[one:]) if torch.is_tensor(preds) else type(preds)}')
+        if not 1 <= n <= 8 or (sums_rows is not None and tuple(sums_rows.shape) != (n, 10)):
+            raise ValueError(f'{what} takes 1 .. 8 images and one (10,) row each, got {n} and '
+                             f'{None if sums_rows is None else tuple(sums_rows.shape)}')
         if strata is not None:
-            K.depth_metric_sums_strata(pred, dev, top, left, rect, *limits, rows, strata.edges, ground if strata.ground else None,
-                                       strata.ground_tol)
-        K.error_accumulate(pred, dev, top, left, rect, *limits, errors.device_sum, errors.device_count)
-        errors.frames += 1
-        if not errors.out_dir:
-            return None
-        return K.error_image(pred, dev, bgr, top, left, rect, *limits, errors.tau, errors.radius, errors.background, want_err=False, out=out)[0]
-
-    def pre_eval_device_errors_batch(self, preds, indices, errors, frames, outs=None, raws=None, *, sums_rows=None, strata=None, rows=None,
-                                     grounds=None, count=None):
-        """``pre_eval_device_errors`` for n = ``len(indices)`` <= 8 images: one ``ge_error_accumulate_batch`` call (the images in index
-        order) and, with ``errors.out_dir``, one ``ge_error_image_batch`` call into the first n blocks of ``outs`` (a CUDA
-        (F >= n, 352, 1216, 3) uint8 tensor, made when None) — returned as (n, 352, 1216, 3), else None.  ``frames``: the n
-        (frame, top, left) the batched engine keeps as ``last_frames``; ``raws``, ``sums_rows``, ``strata`` / ``rows`` / ``grounds`` as in
-        the batch forms of ``pre_eval_device`` and ``pre_eval_device_strata``.  ``count`` = m <= n: only the first m images enter the planes
-        and get a picture (the loop keeps a padded shard's repeated frames out this way); the metric and strata calls still cover all n.
-        Does not synchronise."""
-        import torch
-        from ... import kernels as K
-        n = len(indices)
-        if not (torch.is_tensor(preds) and preds.is_cuda and preds.dim() == 4 and tuple(preds.shape[1:]) == (1, 352, 1216)
-                and preds.shape[0] >= n and preds.dtype == torch.float32):
-            raise TypeError(f'pre_eval_device_errors_batch takes a CUDA (F >= {n}, 1, 352, 1216) float32 tensor, got '
-                            f'{tuple(preds.shape) if torch.is_tensor(preds) else type(preds)}')
-        if not 1 <= n <= 8:
-            raise ValueError(f'pre_eval_device_errors_batch takes 1 .. 8 images, got {n}')
-        m = n if count is None else int(count)
-        if not 0 <= m <= n:
-            raise ValueError(f'pre_eval_device_errors_batch: count must lie in 0 .. {n}, got {count}')
-        if errors.device_sum is None:
-            raise ValueError('pre_eval_device_errors_batch: errors holds no device planes (ErrorMaps.begin makes them)')
-        if strata is not None and (rows is None or (strata.ground and (grounds is None or len(grounds) != n))):
-            raise ValueError('pre_eval_device_errors_batch: strata needs rows and, with spec.ground, every frame\'s ground depth')
-        if errors.out_dir and m and (frames is None or len(frames) != n):
-            raise ValueError(f'pre_eval_device_errors_batch: {n} images need their {n} uploaded frames')
+            if rows is None or tuple(rows.shape) != (n, strata.count, 10):
+                raise ValueError(f'{what}: strata need one ({strata.count}, 10) block for each of {n} images, got '
+                                 f'{None if rows is None else tuple(rows.shape)}')
+            if strata.ground and (grounds is None or len(grounds) != n or any(g is None for g in grounds)):
+                raise ValueError(f'{what}: spec.ground needs every frame\'s ground depth')
+        if sums_rows is None and strata is None and errors is None:
+            raise ValueError(f'{what}: no rows to reduce into')
+        m = 0
+        if errors is not None:
+            m = n if count is None else int(count)
+            if not 0 <= m <= n:
+                raise ValueError(f'{what}: count must lie in 0 .. {n}, got {count}')
+            if errors.device_sum is None:
+                raise ValueError(f'{what}: errors holds no device planes (ErrorMaps.begin makes them)')
+            if errors.out_dir and m and (frames is None or len(frames) != n):
+                raise ValueError(f'{what}: {n} images need their {n} uploaded frames')
         raws = [self.gt_raw(i) for i in indices] if raws is None else raws
         tops = [int(r.shape[0] - 352) for r in raws]                    # eval_kb_crop
         lefts = [int((r.shape[1] - 1216) / 2) for r in raws]
-        if errors.out_dir and m:
+        if m and errors.out_dir:
             for (bgr, ftop, fleft), raw, top, left in zip(frames, raws, tops, lefts):
                 if (ftop, fleft) != (top, left) or tuple(bgr.shape[:2]) != tuple(raw.shape):
-                    raise ValueError(f'pre_eval_device_errors_batch: a frame {tuple(bgr.shape[:2])} at {(ftop, fleft)} is not its ground '
-                                     f'truth\'s {tuple(raw.shape)} at {(top, left)}')
-        uploads = self.__dict__.setdefault('_gt_uploads', [])          # pre_eval_device_batch's staging buffers
+                    raise ValueError(f'{what}: a frame {tuple(bgr.shape[:2])} at {(ftop, fleft)} is not its ground truth\'s '
+                                     f'{tuple(raw.shape)} at {(top, left)}')
+        uploads = self.__dict__.setdefault('_gt_uploads', [])          # one staging buffer per slot: n copies are in flight at once
         while len(uploads) < n:
             uploads.append(PinnedUpload())
         devs = [up(raw, preds.device) for up, raw in zip(uploads, raws)]
@@ -335,6 +231,40 @@ class KITTIDataset(Dataset):
         out, _ = K.error_image_batch(preds, devs[:m], [f[0] for f in frames[:m]], tops[:m], lefts[:m], rect, *limits, errors.tau,
                                      errors.radius, errors.background, want_err=False, out=outs)
         return out[:m]
+
+    # The public forms: adapters over ``_reduce_device`` (its docstring is the contract).  Each calls the core and never a sibling, so
+    # one replaced on an instance is not entered through another.
+    def pre_eval_device_batch(self, preds, indices, sums_rows, raws=None):
+        """The metric sums of n = ``len(indices)`` <= 8 images into ``sums_rows`` (n, 10): one ``ge_depth_metrics_batch`` call."""
+        self._reduce_device('pre_eval_device_batch', preds, indices, raws, sums_rows=sums_rows)
+
+    def pre_eval_device_strata_batch(self, preds, indices, rows, spec, grounds, raws=None, sums_rows=None):
+        """The sums per stratum of ``spec`` into ``rows`` (n, S, 10): one ``ge_depth_metrics_strata_batch`` call; ``sums_rows``: also
+        ``pre_eval_device_batch``'s own call, on the same uploads."""
+        self._reduce_device('pre_eval_device_strata_batch', preds, indices, raws, sums_rows=sums_rows, strata=spec, rows=rows, grounds=grounds)
+
+    def pre_eval_device_errors_batch(self, preds, indices, errors, frames, outs=None, raws=None, *, sums_rows=None, strata=None, rows=None,
+                                     grounds=None, count=None):
+        """The first ``count`` (default: all n) images into the planes of ``errors`` and, with ``errors.out_dir``, into their pictures,
+        which are returned (else None); ``sums_rows``, ``strata`` / ``rows`` / ``grounds``: also the calls of the two forms above."""
+        return self._reduce_device('pre_eval_device_errors_batch', preds, indices, raws, sums_rows=sums_rows, strata=strata, rows=rows,
+                                   grounds=grounds, errors=errors, frames=frames, outs=outs, count=count)
+
+    def pre_eval_device(self, pred, index, sums_row):
+        """``pre_eval_device_batch`` of one image: ``pred`` a CUDA (1, 352, 1216) float32 map, ``sums_row`` one (10,) row."""
+        self._reduce_device('pre_eval_device', _one(pred), [index], sums_rows=_one(sums_row))
+
+    def pre_eval_device_strata(self, pred, index, rows, spec, ground, sums_row=None):
+        """``pre_eval_device_strata_batch`` of one image: ``rows`` one (S, 10) block, ``ground`` the frame's ground depth."""
+        self._reduce_device('pre_eval_device_strata', _one(pred), [index], sums_rows=_one(sums_row), strata=spec, rows=_one(rows),
+                            grounds=[ground])
+
+    def pre_eval_device_errors(self, pred, index, errors, frame, out=None, raw=None, *, sums_row=None, strata=None, rows=None, ground=None):
+        """``pre_eval_device_errors_batch`` of one image: ``frame`` what the engine keeps as ``last_frame``, ``out`` a CUDA
+        (352, 1216, 3) uint8 tensor (made when None); returns the (352, 1216, 3) picture, or None without ``errors.out_dir``."""
+        got = self._reduce_device('pre_eval_device_errors', _one(pred), [index], None if raw is None else [raw], sums_rows=_one(sums_row),
+                                  strata=strata, rows=_one(rows), grounds=[ground], errors=errors, frames=[frame], outs=_one(out))
+        return None if got is None else got[0]
 
     def evaluate_strata(self, rows, spec, logger=None):
         """``rows`` (N, S, 10) float64 from the device loop -> ``{'<stratum>.<metric>': value}`` (the nine metrics, ``pixels`` and ``images``
