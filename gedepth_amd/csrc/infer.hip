@@ -9,10 +9,13 @@
 // ge_aug_window(flip) of aug.hip, so that both produce the same bits.  Each thread reads four consecutive pixels of the crop window
 // once and writes them to view 0 and, reversed, to the mirrored position of view 1: one read of the window, 16-byte stores to both
 // views, no LDS.  Pure streaming work (~3.3 MB read, 17.1 MB written per frame): launch-latency-sized, no MFMA.
+// The prior sweep's front end (include/gedepth_sweep.h) is the same thread with a loop over ground-prior variants around its stores.
 #pragma clang fp contract(off)
 #include "batch_table.h"
 #include "../../include/gedepth_ddad.h"
 #include "../../include/gedepth_ddad_batch.h"
+#include "../../include/gedepth_sweep.h"
+#include <cmath>
 
 struct InferNorm { double mean[3], stdinv[3]; float pe_max, depth_scale; int to_rgb; };
 static InferNorm infer_norm(float pe_max, const double* mean3, const double* std3, float depth_scale, int to_rgb) {
@@ -23,6 +26,41 @@ static InferNorm infer_norm(float pe_max, const double* mean3, const double* std
 }
 
 extern "C" size_t ge_batch_frame_size(void) { return sizeof(GeBatchFrame); }
+
+// What a thread of the KITTI front ends does for its four consecutive pixels, shared by infer_front_k and infer_front_sweep_k so that
+// the two cannot drift.  front_pixel: pixel k of the four -> column k of o.  COLOUR: the three bytes at px -> rows 0 .. 2 (ge_aug_load:
+// (float)u8; ge_aug_color_normalize: truncf, a no-op on a uint8 value, BGR -> RGB, f64 (x - mean) * (1 / std)).  GROUND: the raw ground
+// depth -> row 3 (LoadImageFromFile: > pe_max or < 0 zeroed; Normalize: / depth_scale where > 0) and row 4 (the value itself).
+// infer_front_k does both per pixel; the sweep does COLOUR once and GROUND once per variant.  front_store: the five 16-byte rows to
+// view 0 and, reversed, to the mirrored position of view 1 (ge_aug_window(flip): x -> Wc - 1 - x); n = Hc * Wc, r = y * Wc.
+template <bool COLOUR, bool GROUND>
+__device__ __forceinline__ void front_pixel(const uint8_t* __restrict__ px, float raw, const InferNorm& p, int k, float (&o)[5][4]) {
+  if (COLOUR) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const float v = truncf((float)px[c]);
+      const int oc = p.to_rgb ? 2 - c : c;
+      o[oc][k] = (float)(((double)v - p.mean[oc]) * p.stdinv[oc]);
+    }
+  }
+  if (GROUND) {
+    float f = raw;
+    if (f > p.pe_max) f = 0.f;
+    if (f < 0.f) f = 0.f;
+    if (f > 0.f) f = f / p.depth_scale;
+    o[3][k] = f;
+    o[4][k] = raw;
+  }
+}
+__device__ __forceinline__ void front_store(float* __restrict__ dst, long n, long r, int g, int Wc, int views, const float (&o)[5][4]) {
+#pragma unroll
+  for (int c = 0; c < 5; ++c) *(float4*)(dst + c * n + r + 4 * g) = make_float4(o[c][0], o[c][1], o[c][2], o[c][3]);
+  if (views == 2) {
+    float* d1 = dst + 5 * n + r + (Wc - 4 - 4 * g);
+#pragma unroll
+    for (int c = 0; c < 5; ++c) *(float4*)(d1 + c * n) = make_float4(o[c][3], o[c][2], o[c][1], o[c][0]);
+  }
+}
 
 // Frame f = blockIdx.y of the table (batch_table.h) -> images views * f .. views * f + views - 1 of dst (views * n, 5, Hc, Wc) planar f32;
 // view 1 = view 0 mirrored horizontally.  Wc % 4 == 0, dst 16-byte aligned (checked by the caller).  The frames share grid.x, so a frame's
@@ -40,30 +78,8 @@ __global__ void __launch_bounds__(256) infer_front_k(BatchTable t, float* __rest
     const uint8_t* px = bgr + s * 3;
     float o[5][4];
 #pragma unroll
-    for (int k = 0; k < 4; ++k) {
-#pragma unroll
-      for (int c = 0; c < 3; ++c) {
-        // ge_aug_load: (float)u8; ge_aug_color_normalize: truncf (a no-op on a uint8 value), BGR -> RGB, f64 (x - mean) * (1 / std)
-        const float v = truncf((float)px[3 * k + c]);
-        const int oc = p.to_rgb ? 2 - c : c;
-        o[oc][k] = (float)(((double)v - p.mean[oc]) * p.stdinv[oc]);
-      }
-      const float raw = pe[s + k];
-      float f = raw;                                        // LoadImageFromFile: > pe_max or < 0 zeroed; Normalize: / depth_scale where > 0
-      if (f > p.pe_max) f = 0.f;
-      if (f < 0.f) f = 0.f;
-      if (f > 0.f) f = f / p.depth_scale;
-      o[3][k] = f;
-      o[4][k] = raw;
-    }
-    const long r = (long)y * Wc;
-#pragma unroll
-    for (int c = 0; c < 5; ++c) *(float4*)(dst + c * n + r + 4 * g) = make_float4(o[c][0], o[c][1], o[c][2], o[c][3]);
-    if (views == 2) {
-      float* d1 = dst + 5 * n + r + (Wc - 4 - 4 * g);      // ge_aug_window(flip): x -> Wc - 1 - x
-#pragma unroll
-      for (int c = 0; c < 5; ++c) *(float4*)(d1 + c * n) = make_float4(o[c][3], o[c][2], o[c][1], o[c][0]);
-    }
+    for (int k = 0; k < 4; ++k) front_pixel<true, true>(px + 3 * k, pe[s + k], p, k, o);
+    front_store(dst, n, (long)y * Wc, g, Wc, views, o);
   }
 }
 // the launch of n checked frames
@@ -91,6 +107,66 @@ extern "C" int ge_infer_front_batch(const GeBatchFrame* frames, int n, float* ds
   for (int f = 0; f < n; ++f)
     if ((uintptr_t)frames[f].aux & 3) return GE_ERR_UNSUPPORTED;
   return infer_front_launch(frames, n, dst, Hc, Wc, views, infer_norm(pe_max, mean3, std3, depth_scale, to_rgb), stream);
+}
+
+// The prior sweep (include/gedepth_sweep.h): one frame -> nv slots that differ only in channels 3 and 4.  prior_variant is the header's
+// rule, branch for branch; the baseline (c == 0, s == 1) hands the plane through, since 1 / (1 / pe) is not pe in f32.
+__device__ __forceinline__ float prior_variant(float pe, const GePriorVariant& v) {
+  if (v.drop) return 0.f;
+  if (v.c == 0.f && v.s == 1.f) return pe;
+  if (!(pe > 0.f)) return pe;
+  const float q = 1.f / pe + v.c;
+  return q > 0.f ? v.s / q : 0.f;
+}
+struct SweepTable { GePriorVariant v[GE_SWEEP_MAX]; };
+static_assert(sizeof(GePriorVariant) == 12 && sizeof(SweepTable) == 96, "the by-value variant table is 8 x {two floats, one int}");
+
+// Variant v of the table -> images views * v .. views * v + views - 1 of dst (views * nv, 5, Hc, Wc) planar f32, each with the bits
+// infer_front_k writes for the plane prior_variant(pe, v).  The variants are the INNER loop of a thread: it reads its twelve colour bytes
+// and four ground depths once, normalises the colour once (the float64 part of the work) and keeps the sixteen values in registers; per
+// variant it forms eight values and issues the ten 16-byte stores.  With the variants on blockIdx.y instead the frame would be read and
+// normalised nv times; here the launch reads ~3.3 MB once and writes 17.1 MB per variant.  The table is read at a uniform index (scalar
+// loads from the kernel-argument block).  No LDS, no atomics; Wc % 4 == 0, dst 16-byte aligned (checked by the caller).
+__global__ void __launch_bounds__(256) infer_front_sweep_k(const uint8_t* __restrict__ bgr, const float* __restrict__ pe, int W, int top,
+                                                           int left, SweepTable t, int nv, float* __restrict__ dst, int Hc, int Wc, int views,
+                                                           InferNorm p) {
+  const int G = Wc >> 2;
+  const long n = (long)Hc * Wc, groups = (long)Hc * G;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < groups; i += (long)gridDim.x * 256) {
+    const int y = (int)(i / G), g = (int)(i - (long)y * G);
+    const long s = (long)(y + top) * W + (left + 4 * g);
+    const uint8_t* px = bgr + s * 3;
+    float o[5][4], raw[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      front_pixel<true, false>(px + 3 * k, 0.f, p, k, o);
+      raw[k] = pe[s + k];
+    }
+    for (int v = 0; v < nv; ++v) {
+      const GePriorVariant var = t.v[v];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) front_pixel<false, true>(px, prior_variant(raw[k], var), p, k, o);
+      front_store(dst + (long)v * views * 5 * n, n, (long)y * Wc, g, Wc, views, o);
+    }
+  }
+}
+extern "C" size_t ge_prior_variant_size(void) { return sizeof(GePriorVariant); }
+extern "C" int ge_infer_front_sweep(const uint8_t* bgr_hwc, const float* pe, int H, int W, int top, int left, const GePriorVariant* variants,
+                                    int n, float* dst, int Hc, int Wc, int views, float pe_max, const double* mean3, const double* std3,
+                                    float depth_scale, int to_rgb, void* stream) {
+  if (!bgr_hwc || !pe || !variants || !dst || !mean3 || !std3 || n < 1 || n > GE_SWEEP_MAX || H <= 0 || W <= 0 || Hc <= 0 || Wc <= 0 ||
+      top < 0 || left < 0 || Hc > H - top || Wc > W - left || (views != 1 && views != 2))
+    return GE_ERR_BAD_ARG;
+  SweepTable t;
+  for (int v = 0; v < GE_SWEEP_MAX; ++v) t.v[v] = variants[v < n ? v : 0];      // entries >= n are never read
+  for (int v = 0; v < n; ++v)
+    if (!std::isfinite(t.v[v].c) || !std::isfinite(t.v[v].s) || !(t.v[v].s > 0.f)) return GE_ERR_BAD_ARG;
+  if ((Wc & 3) || ((uintptr_t)dst & 15) || ((uintptr_t)pe & 3)) return GE_ERR_UNSUPPORTED;
+  const unsigned grid = ge_blocks((long)Hc * (Wc / 4), 256, 65536);
+  infer_front_sweep_k<<<grid, 256, 0, ge_stream(stream)>>>(bgr_hwc, pe, W, top, left, t, n, dst, Hc, Wc, views,
+                                                          infer_norm(pe_max, mean3, std3, depth_scale, to_rgb));
+  GE_LAUNCH_CHECK();
+  return GE_OK;
 }
 
 // ge_infer_front_ddad restates LoadDDADImageFromFile(USEPE, USE_DYNAMIC_PE) -> DDADResize(shape, depth = False) -> Normalize of

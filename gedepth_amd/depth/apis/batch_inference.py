@@ -18,6 +18,10 @@ slot f holds does not reach another slot's map.
 ``decode_ahead`` is the host side: a pool of at most ``DECODE_WORKERS`` threads decodes the next batch's PNGs (PIL releases the GIL while
 inflating) while the device computes the current one.  ``points`` and ``ground_maps`` stay single-frame (``DepthInferencer``).
 
+``BatchDepthInferencer.sweep`` fills the slots with ONE frame under V <= F ground priors instead (include/gedepth_sweep.h: a global pitch,
+a height scale, the prior removed): one upload and one ``ge_infer_front_sweep`` launch in place of step 1 and 2, then steps 3 and 4
+unchanged, on the same captured graph.
+
 ``BatchDDADInferencer`` is the same engine for the DDAD protocol (one view per frame, no merge): n uploads, ONE
 ``ge_infer_front_ddad_batch`` into the first n images of the static ``(F, 5, Hd, Wd)`` input, the n cameras' heights into the static
 ``(F,)`` tensor the adaptive ground embedding reads (one small copy, outside the graph), one captured forward over all F slots.  The slots
@@ -175,6 +179,37 @@ class BatchDepthInferencer(_BatchEngine):
             self.last_frames = list(zip(devs, tops, lefts))   # kept for the error images, as last_frame is
             self._run(self._key(), graph, lambda: self._body(metas))
             out = self._maps(n, to_host)
+        cur.wait_stream(self.stream)
+        return out
+
+    def sweep(self, img, variants, pe=None, calib=None, cam_height=1.65, graph=True, to_host=True, path=None):
+        """ONE frame under V = ``len(variants)`` <= F ground priors -> its V maps, in the variants' order.  ``variants``: a
+        ``core.PriorSweep`` or its ``(c, s, drop)`` rows (include/gedepth_sweep.h states the rule); ``img``, ``pe``, ``calib``,
+        ``cam_height``, ``path`` as one frame of ``batch``.  One decode, one upload (slot 0's pinned buffer), one ``ground_depth`` and ONE
+        ``ge_infer_front_sweep`` launch fill the first ``views * V`` images of ``static_in``; the forward is ``batch``'s, under its
+        key and on its static buffers, so both share one captured graph.  Slots from V on keep what they held.  Returns as ``batch``;
+        ``last_ground_depths`` / ``last_frames`` hold the unperturbed plane / the uploaded frame V times."""
+        from ...sweep_kernels import variant_table
+        rows = variants.table() if hasattr(variants, 'table') else list(variants)
+        V, s = len(variant_table(rows)), self.spec                              # the rows' argument errors, before any device work
+        if V > self.frames:
+            raise ValueError(f'{V} variants for an engine of {self.frames} slots')
+        path = path if path is not None else (img if isinstance(img, str) else None)
+        bgr = _decode(img)
+        H, W = bgr.shape[:2]
+        self.front.frame(self, H, W, None, None)                                  # a frame smaller than the crop, before any device work
+        metas = self._metas(path, (H, W), (s['height'], s['width'], 5)) * self.frames
+        cur = torch.cuda.current_stream(self.device)
+        self.stream.wait_stream(cur)
+        with torch.cuda.stream(self.stream):
+            top, left = int(H - s['height']), int((W - s['width']) / 2)          # KBCrop
+            raw = self.ground_depth(H, W, path, pe, calib, cam_height)
+            dev = self._stagings[0](bgr, self.device)
+            K.infer_front_sweep(dev, raw, rows, self.static_in, top, left, s['mean'], s['std'], s['views'], s['to_rgb'], s['pe_max'],
+                                s['depth_scale'])
+            self.last_ground_depths, self.last_frames = [raw] * V, [(dev, top, left)] * V
+            self._run(self._key(), graph, lambda: self._body(metas))
+            out = self._maps(V, to_host)
         cur.wait_stream(self.stream)
         return out
 

@@ -37,7 +37,7 @@ from ..datasets.pipelines import loading    # _DDAD_CAMERA_HEIGHT is read throug
 from ..models import build_depther
 from ..utils.pinned import PinnedUpload
 
-__all__ = ['init_depther', 'inference_depther', 'inference_point_cloud', 'inference_ground', 'inference_scene_cloud', 'inference_error_map', 'DepthInferencer',
+__all__ = ['init_depther', 'inference_depther', 'inference_point_cloud', 'inference_ground', 'inference_scene_cloud', 'inference_error_map', 'inference_prior_sweep', 'DepthInferencer',
            'kitti_front_spec', 'ddad_front_spec', 'front_spec', 'SCENE_LAYERS']
 
 # test-time transforms of MultiScaleFlipAug the device front end restates (ImageToTensor / Collect are layout only)
@@ -679,6 +679,37 @@ def inference_ground(model, img, pe=None, calib=None, cam_height=1.65, bf16=Fals
     imgs, pes, cams, config = _frames(model, img, pe, calib, camera)
     eng = engine_for(model, bf16, config)
     return [eng.ground_maps(i, p, calib, cam_height, graph, camera=c) for i, p, c in zip(imgs, pes, cams)]
+
+
+def sweep_slots(sweep):
+    """The frame slots of the batched engine that runs ``sweep`` (a ``core.PriorSweep``): its variant count, and 2 for a sweep of the
+    baseline alone (``engine_for(batch=1)`` is the single-frame engine, which has no ``sweep``)."""
+    return max(int(sweep.count), 2)
+
+
+def inference_prior_sweep(model, img, sweep, pe=None, calib=None, bf16=False, graph=True):
+    """One frame (a path or an (H, W, 3) uint8 BGR array) under every ground prior of ``sweep`` (a ``core.PriorSweep``): a list with one
+    (1, 352, 1216) float32 map per variant, in the sweep's order (``sweep.names``), the first being the map ``inference_depther`` gives the
+    frame — for looking at what a calibration error does to one frame's map.  Ground depth, ``bf16`` and ``graph`` as in
+    ``inference_depther`` (``calib`` with ``sweep.cam_height``), with the same argument errors before any device work; the frame runs
+    through ``BatchDepthInferencer.sweep`` of ``engine_for(model, bf16, batch=V)``.  A DDAD config raises ``NotImplementedError``: the
+    per-camera height also feeds the network there, so the meaning of the variants needs its own decision."""
+    from ..core.evaluation import PriorSweep
+    if not isinstance(sweep, PriorSweep):
+        raise TypeError(f'sweep must be a depth.core.PriorSweep, got {type(sweep).__name__}')
+    if isinstance(img, list):
+        raise TypeError('inference_prior_sweep takes one frame (a path or an (H, W, 3) uint8 BGR array), not a list')
+    spec, prefix = config = _config_of(model)                                 # argument errors before any device work
+    if spec['protocol'] == 'ddad':
+        raise NotImplementedError('inference_prior_sweep with a DDAD config: the prior sweep is built for the KITTI protocol (on DDAD the '
+                                  'per-camera height also feeds the network, so the variants\' meaning needs its own decision)')
+    if calib is None and pe is None and _pe_file(spec, prefix, img) is None:
+        raise ValueError(_NO_PE)
+    from .batch_inference import frame_size
+    H, W = frame_size(img)
+    if H < spec['height'] or W < spec['width']:
+        raise ValueError(f'frame {(H, W)} is smaller than the KB crop {(spec["height"], spec["width"])}')
+    return engine_for(model, bf16, config, sweep_slots(sweep)).sweep(img, sweep, pe, calib, sweep.cam_height, graph)
 
 
 def inference_point_cloud(model, img, pe=None, calib=None, cam_height=1.65, bf16=False, graph=True, K=None, out_file=None, **cloud_kw):

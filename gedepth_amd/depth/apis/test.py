@@ -35,7 +35,13 @@ pictures, or one ``.npz`` under ``format_only``).  The maps exist on the engine'
 
 ``scene_dir`` (KITTI protocol) writes every image's scene cloud — the prediction, the ground prior, the LiDAR ground truth and the
 slope-adjusted ground plane in one binary ``.ply`` (``DepthInferencer.scene_points`` -> ``write_scene_ply``) — through the engine, alone: it
-returns no results and combines with no other output.  The loop: speed not measured; the kernel: README "Scene clouds"."""
+returns no results and combines with no other output.  The loop: speed not measured; the kernel: README "Scene clouds".
+
+``prior_sweep=PriorSweep(...)`` (with ``device_eval``; KITTI protocol, ``eval_batch=1``, alone) answers what the numbers do when the
+calibration behind the ground prior is a little wrong: every frame runs ONCE through the batched engine with its V slots holding the
+frame under V priors (``BatchDepthInferencer.sweep``: one ``ge_infer_front_sweep`` launch, include/gedepth_sweep.h) and ONE
+``ge_depth_metrics_batch`` call reduces the V maps against one upload of the ground truth.  The loop returns ``(results, rows)``, ``rows``
+(N, V, 10) float64; ``dataset.evaluate_sweep`` prints the table.  Speed: README "Prior sweep"."""
 import os.path as osp
 
 import numpy as np
@@ -324,9 +330,53 @@ def _device_eval(model, data_loader, pre_eval, format_only, show, out_dir, ply_d
     return results if strata is None else (results, host_rows.numpy().copy())
 
 
+def _sweep_refusals(prior_sweep, device_eval, eval_batch, strata, errors, ground_dir, scene_dir, data_loader):
+    """What ``single_gpu_test(prior_sweep=...)`` refuses, before anything runs."""
+    from ..core.evaluation import PriorSweep
+    if not isinstance(prior_sweep, PriorSweep):
+        raise TypeError(f'prior_sweep must be a depth.core.PriorSweep, got {type(prior_sweep).__name__}')
+    if not device_eval:
+        raise NotImplementedError('prior_sweep: the variants are the slots of the device evaluation loop\'s engine: it needs device_eval=True '
+                                  '(the host loop is not covered)')
+    if eval_batch != 1:
+        raise NotImplementedError(f'prior_sweep with eval_batch={eval_batch}: the slots of a forward are the variants of ONE frame; use '
+                                  'eval_batch=1')
+    if strata is not None or errors is not None or ground_dir or scene_dir:
+        raise NotImplementedError('prior_sweep with strata / errors / ground_dir / scene_dir: those read one prior per frame; run them apart')
+    if getattr(data_loader.dataset, 'device_protocol', None) != 'kitti':
+        raise NotImplementedError(f'prior_sweep: {type(data_loader.dataset).__name__} is not evaluated by the KITTI protocol (on DDAD the '
+                                  'per-camera height also feeds the network, so the variants\' meaning needs its own decision)')
+
+
+def _device_eval_sweep(model, data_loader, pre_eval, format_only, show, out_dir, ply_dir, engine_graph, sweep):
+    """The ``prior_sweep`` loop of ``single_gpu_test``: per frame ONE ``BatchDepthInferencer.sweep`` (one decode, one upload, one front-end
+    launch, one forward over the V = ``sweep.count`` variants) and ONE ``dataset.pre_eval_device_sweep`` (one upload of the ground truth,
+    one ``ge_depth_metrics_batch`` call with V rows) into block ``row`` of an (N, V, 10) device buffer; the next frame's image and
+    ground-truth PNGs decode ahead; one synchronising copy at the end -> ``(results, rows)``."""
+    from ..core.evaluation import metrics_from_sums
+    from .batch_inference import decode_ahead
+    from .inference import _decode, sweep_slots
+    dataset = data_loader.dataset
+    if not pre_eval or format_only:
+        raise NotImplementedError('device_eval reduces every map to metric sums on the device: it needs pre_eval=True and no format_only')
+    if show or out_dir or ply_dir:
+        raise NotImplementedError('device_eval with show / out_dir / ply_dir: the depth maps never reach the host')
+    _, eng, indices, frames = _engine_frames(model, data_loader, 'prior_sweep', batch=sweep_slots(sweep))
+    rows = torch.empty(max(len(indices), 1), sweep.count, 10, device=eng.device, dtype=torch.float64)
+    jobs = [(lambda i=i, f=f: (_decode(f['img']), dataset.gt_raw(i))) for i, f in zip(indices, frames)]
+    for row, ((bgr, raw),) in enumerate(decode_ahead(jobs, 1)):
+        preds = eng.sweep(bgr, sweep, cam_height=sweep.cam_height, graph=engine_graph, to_host=False, path=frames[row]['img'])
+        with torch.cuda.stream(eng.stream):
+            dataset.pre_eval_device_sweep(preds, indices[row], rows[row], raw=raw)
+    with torch.cuda.stream(eng.stream):
+        host = rows[:len(indices)].cpu().numpy()                       # the one copy (and the one synchronisation) of the loop
+    torch.cuda.current_stream(eng.device).wait_stream(eng.stream)
+    return [metrics_from_sums(r) for r in host[:, 0]], host
+
+
 def single_gpu_test(model, data_loader, pre_eval=False, format_only=False, format_args=None, device=None, *, show=False,
                     out_dir=None, device_eval=False, ply_dir=None, ground_dir=None, eval_batch=1, engine_graph=True, scene_dir=None,
-                    strata=None, errors=None):
+                    strata=None, errors=None, prior_sweep=None):
     """Returns a list with one entry per image: the metric tuple (``pre_eval``) or the ``(1, H, W)`` depth map.  ``show`` / ``out_dir``:
     ``show_result`` of every image's map, written to ``out_dir/replace_str(ori_filename)`` (``format_only``: the raw map as
     ``out_dir/<ori_filename without extension>.npy``).  ``ply_dir``: every image's point cloud as ``ply_dir/<ori_filename with .ply>``
@@ -341,8 +391,14 @@ def single_gpu_test(model, data_loader, pre_eval=False, format_only=False, forma
     ``errors`` (a ``core.ErrorMaps``; with ``device_eval``, KITTI protocol, any ``eval_batch``, also with ``strata`` and ``ground_dir``): the
     loop also adds every LiDAR return's abs-rel error into the per-pixel planes of ``errors`` and, with ``errors.out_dir``, writes every
     image's error picture to ``out_dir/replace_str(<name in the split>)`` (include/gedepth_error.h); the result is what the loop returns
-    without ``errors``."""
+    without ``errors``.  ``prior_sweep`` (a ``core.PriorSweep``; with ``device_eval``, KITTI protocol, ``eval_batch=1``, alone): every frame
+    is evaluated under each of the sweep's V ground priors in one forward (``_device_eval_sweep``; include/gedepth_sweep.h) and the loop
+    returns ``(results, rows)``: ``rows`` an (N, V, 10) float64 array of metric sums per image and variant (``dataset.evaluate_sweep``
+    prints its table), ``results`` the tuples of ``rows[:, 0]``, the baseline, i.e. an ordinary result list."""
     model.eval()
+    if prior_sweep is not None:
+        _sweep_refusals(prior_sweep, device_eval, eval_batch, strata, errors, ground_dir, scene_dir, data_loader)
+        return _device_eval_sweep(model, data_loader, pre_eval, format_only, show, out_dir, ply_dir, engine_graph, prior_sweep)
     if errors is not None:
         if not device_eval:
             raise NotImplementedError('errors: the error maps are reduced by the device evaluation loop: it needs device_eval=True (the host '
@@ -398,13 +454,15 @@ def single_gpu_test(model, data_loader, pre_eval=False, format_only=False, forma
 
 def multi_gpu_test(model, data_loader, pre_eval=False, format_only=False, format_args=None, device=None, *, show=False, out_dir=None,
                    device_eval=False, ply_dir=None, ground_dir=None, eval_batch=1, engine_graph=True, scene_dir=None, strata=None,
-                   errors=None):
+                   errors=None, prior_sweep=None):
     """Each rank evaluates its shard of a non-shuffled DistributedSampler; rank 0 receives the results in dataset order.  ``show`` /
     ``out_dir`` / ``ply_dir`` / ``ground_dir`` / ``scene_dir`` / ``device_eval`` / ``eval_batch`` / ``engine_graph`` / ``strata`` as in
     ``single_gpu_test``: every rank writes the files of its own shard; with ``strata`` rank 0 receives ``(results, rows)``.  ``errors``:
     every rank writes its shard's pictures, and rank 0's ``errors`` receives the planes of all ranks, ``sum`` added in rank order, ``count``
     added exactly; the frames the sampler pads the last round with enter no plane and get no picture (``_unpadded``), so every image of
-    the split is counted once."""
+    the split is counted once.  ``prior_sweep`` raises: the sweep runs on one device (``single_gpu_test``)."""
+    if prior_sweep is not None:
+        raise NotImplementedError('multi_gpu_test(prior_sweep=...): the prior sweep runs on one device; use single_gpu_test')
     part = single_gpu_test(model, data_loader, pre_eval, format_only, format_args, device, show=show, out_dir=out_dir,
                            device_eval=device_eval, ply_dir=ply_dir, ground_dir=ground_dir, eval_batch=eval_batch, engine_graph=engine_graph,
                            scene_dir=scene_dir, strata=strata, errors=errors)

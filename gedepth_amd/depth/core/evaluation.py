@@ -88,6 +88,60 @@ class StrataSpec:
         return f'StrataSpec(edges={self.edges}, ground={self.ground}, ground_tol={self.ground_tol})'
 
 
+class PriorSweep:
+    """Which ground priors ``single_gpu_test(..., device_eval=True, prior_sweep=PriorSweep(...))`` evaluates every frame under
+    (include/gedepth_sweep.h states the rule): the baseline — the calibrated plane, untouched — first, then one variant per entry of
+    ``pitch_deg`` (degrees; positive: the ground comes closer, as when the camera pitches down against its calibration), then one per entry
+    of ``height_scale`` (the plane of a camera that many times as high), then, with ``drop``, the prior removed (all zeros).  At most eight
+    variants: they are the slots of one forward.  ``cam_height`` (metres) turns a pitch into the rule's ``c = tan(pitch) / cam_height``,
+    formed in float64 and rounded to float32 once.  ``variants``: the ``(c, s, drop)`` rows, ``names`` their labels, ``count`` their number."""
+
+    MAX = 8                            # GE_SWEEP_MAX of include/gedepth_sweep.h
+
+    def __init__(self, pitch_deg=(-1.0, -0.5, 0.5, 1.0), height_scale=(), drop=True, cam_height=1.65):
+        self.pitch_deg = tuple(float(d) for d in pitch_deg)
+        self.height_scale = tuple(float(s) for s in height_scale)
+        self.drop, self.cam_height = bool(drop), float(cam_height)
+        if not (np.isfinite(self.cam_height) and self.cam_height > 0.0):
+            raise ValueError(f'PriorSweep: cam_height must be a positive number of metres, got {cam_height}')
+        for d in self.pitch_deg:
+            if not np.isfinite(d) or abs(d) > 10.0 or d == 0.0:
+                raise ValueError(f'PriorSweep: a pitch must be finite, within +-10 degrees and not 0 (the baseline is always the first '
+                                 f'variant), got {d}')
+        for s in self.height_scale:
+            if not np.isfinite(s) or not 0.5 <= s <= 2.0 or s == 1.0:
+                raise ValueError(f'PriorSweep: a height scale must lie in [0.5, 2] and not be 1 (the baseline is always the first variant), '
+                                 f'got {s}')
+        self.variants = [(0.0, 1.0, 0)]
+        self.names = ['baseline']
+        for d in self.pitch_deg:
+            self.variants.append((float(np.float32(np.tan(np.radians(d)) / self.cam_height)), 1.0, 0))
+            self.names.append(f'pitch {d:+.2f} deg')
+        for s in self.height_scale:
+            self.variants.append((0.0, float(np.float32(s)), 0))
+            self.names.append(f'height x{s:.2f}')
+        if self.drop:
+            self.variants.append((0.0, 1.0, 1))
+            self.names.append('no prior')
+        if len(self.variants) > self.MAX:
+            raise ValueError(f'PriorSweep: at most {self.MAX} variants (the slots of one forward), the baseline included, got {len(self.variants)}')
+        if len(set(self.variants)) != len(self.variants) or len(set(self.names)) != len(self.names):
+            raise ValueError(f'PriorSweep: duplicate variants in pitch_deg={self.pitch_deg}, height_scale={self.height_scale}')
+
+    @property
+    def count(self):
+        """V, the number of variants."""
+        return len(self.variants)
+
+    def table(self):
+        """The ``(c, s, drop)`` rows as the ``GePriorVariant`` struct of include/gedepth_sweep.h takes them: two float32 values as Python
+        floats and an int."""
+        return list(self.variants)
+
+    def __repr__(self):
+        return f'PriorSweep(pitch_deg={self.pitch_deg}, height_scale={self.height_scale}, drop={self.drop}, cam_height={self.cam_height})'
+
+
 class ErrorMaps:
     """Where in the picture a split's error is (include/gedepth_error.h), for ``single_gpu_test(..., device_eval=True, errors=ErrorMaps(...))``:
     the loop adds every LiDAR return's abs-rel error e = |gt - pred| / gt into a per-pixel float64 ``sum`` and uint32 ``count`` on the

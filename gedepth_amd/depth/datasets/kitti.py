@@ -6,6 +6,7 @@ sample preparation, and the evaluation protocol (KB crop of the ground truth, Ga
 nan-mean summary).  The reference's experimental ``mask_pe`` / ``mask_pe_gt`` evaluation variants are not carried.
 """
 import os.path as osp
+import warnings
 from collections import OrderedDict
 
 import numpy as np
@@ -265,6 +266,61 @@ class KITTIDataset(Dataset):
         got = self._reduce_device('pre_eval_device_errors', _one(pred), [index], None if raw is None else [raw], sums_rows=_one(sums_row),
                                   strata=strata, rows=_one(rows), grounds=[ground], errors=errors, frames=[frame], outs=_one(out))
         return None if got is None else got[0]
+
+    def pre_eval_device_sweep(self, preds, index, out_rows, raw=None):
+        """The prior sweep's reduction: the V = ``out_rows.shape[0]`` <= 8 first maps of ``preds`` (a CUDA (F >= V, 1, 352, 1216) float32
+        tensor: ONE frame under V ground priors, ``BatchDepthInferencer.sweep``) against split entry ``index``'s ground truth ->
+        ``out_rows`` (V, 10), row v the ten metric sums of map v.  The ground-truth PNG goes up ONCE (``raw``: its ``gt_raw`` array when a
+        thread has decoded it ahead) and ONE ``ge_depth_metrics_batch`` call reads it through V table rows that all point at that upload,
+        so row v carries the bits ``pre_eval_device`` gives map v.  On the current stream, without synchronising."""
+        import torch
+        from ... import kernels as K
+        what = 'pre_eval_device_sweep'
+        if not (torch.is_tensor(out_rows) and out_rows.dim() == 2 and out_rows.shape[1] == 10 and 1 <= out_rows.shape[0] <= 8):
+            raise ValueError(f'{what} takes 1 .. 8 variants and one (10,) row each, got '
+                             f'{tuple(out_rows.shape) if torch.is_tensor(out_rows) else type(out_rows)}')
+        V = out_rows.shape[0]
+        if not (torch.is_tensor(preds) and preds.is_cuda and preds.dim() == 4 and tuple(preds.shape[1:]) == (1, 352, 1216)
+                and preds.shape[0] >= V and preds.dtype == torch.float32):
+            raise TypeError(f'{what} takes a CUDA (F >= {V}, 1, 352, 1216) float32 tensor, got '
+                            f'{tuple(preds.shape) if torch.is_tensor(preds) else type(preds)}')
+        raw = self.gt_raw(index) if raw is None else raw
+        top, left = int(raw.shape[0] - 352), int((raw.shape[1] - 1216) / 2)        # eval_kb_crop
+        uploads = self.__dict__.setdefault('_gt_uploads', [])
+        if not uploads:
+            uploads.append(PinnedUpload())
+        dev = uploads[0](raw, preds.device)
+        K.depth_metric_sums_batch(preds, [dev] * V, [top] * V, [left] * V, self.eval_rect(352, 1216), self.depth_scale, self.min_depth,
+                                  self.max_depth, out_rows)
+
+    def evaluate_sweep(self, rows, spec, logger=None):
+        """``rows`` (N, V, 10) float64 from the sweep loop, ``spec`` its ``core.PriorSweep`` -> ``{variant name: {metric: value}}``: the
+        nine metrics as the nan-mean over images of ``metrics_from_sums(row)`` — the convention of ``evaluate``'s headline numbers, so the
+        baseline line is what ``evaluate`` prints for the loop's ``results`` — and, for every variant but the baseline, ``d_abs_rel``,
+        ``d_rmse`` and ``d_a1``: its value minus the baseline's.  Prints one line per variant."""
+        from ..core.evaluation import metrics_from_sums
+        rows = np.asarray(rows, dtype=np.float64)
+        if rows.ndim != 3 or rows.shape[1:] != (spec.count, 10):
+            raise ValueError(f'evaluate_sweep takes (N, {spec.count}, 10) rows for {spec!r}, got {rows.shape}')
+        table = OrderedDict()
+        for v, name in enumerate(spec.names):
+            tuples = [metrics_from_sums(r) for r in rows[:, v]]
+            with warnings.catch_warnings():
+                warnings.simplefilter('ignore', RuntimeWarning)                     # a split without a counted pixel: NaN, as ``evaluate``
+                table[name] = OrderedDict((k, float(np.nanmean([t[i] for t in tuples])) if tuples else float('nan'))
+                                          for i, k in enumerate(METRIC_NAMES))
+        base = table[spec.names[0]]
+        for name in spec.names[1:]:
+            for k in ('abs_rel', 'rmse', 'a1'):
+                table[name][f'd_{k}'] = table[name][k] - base[k]
+        width = max(len(name) for name in table)
+        deltas = ('d_abs_rel', 'd_rmse', 'd_a1')
+        lines = ['Prior sweep:', ' | '.join([' ' * width] + [f'{k:>8s}' for k in METRIC_NAMES] + [f'{k:>9s}' for k in deltas])]
+        for name, entry in table.items():
+            lines.append(' | '.join([f'{name:<{width}s}'] + [f'{entry[k]:8.4f}' for k in METRIC_NAMES]
+                                    + [f'{entry[k]:+9.4f}' if k in entry else ' ' * 9 for k in deltas]))
+        (logger.info if logger is not None and hasattr(logger, 'info') else print)('\n'.join(lines))
+        return table
 
     def evaluate_strata(self, rows, spec, logger=None):
         """``rows`` (N, S, 10) float64 from the device loop -> ``{'<stratum>.<metric>': value}`` (the nine metrics, ``pixels`` and ``images``

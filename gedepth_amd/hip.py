@@ -17,7 +17,9 @@ include/gedepth_error.h (the error images and the split-level error planes, wrap
 seventh: ``ACCUM_SIGNATURES`` for include/gedepth_accum.h (the optimizer's gradient accumulation, wrapped in gedepth_amd/accum_kernels.py).
 ``DDAD_BATCH_HEADERS`` is an eighth: ``DDAD_BATCH_SIGNATURES`` for include/gedepth_ddad_batch.h (the batched DDAD front end and resized
 metric sums, wrapped in gedepth_amd/ddad_batch_kernels.py; they take the ``GeBatchFrame`` of include/gedepth_batch.h).
-``lib()`` binds the entry points of all eight tables.
+``SWEEP_HEADERS`` is a ninth: ``SWEEP_SIGNATURES`` for include/gedepth_sweep.h (the prior sweep's front end, wrapped in
+gedepth_amd/sweep_kernels.py, which mirrors its ``GePriorVariant`` struct).
+``lib()`` binds the entry points of all nine tables.
 
 There is deliberately NO fallback: if the shared library is missing, or a tensor is not a
 contiguous CUDA(HIP) tensor of the expected dtype, the call raises.  Build the library with
@@ -40,6 +42,7 @@ NECK_HEADERS = {'NECK_SIGNATURES': 'gedepth_neck.h'}         # and after those
 ERROR_HEADERS = {'ERROR_SIGNATURES': 'gedepth_error.h'}      # and after those
 ACCUM_HEADERS = {'ACCUM_SIGNATURES': 'gedepth_accum.h'}      # and after those
 DDAD_BATCH_HEADERS = {'DDAD_BATCH_SIGNATURES': 'gedepth_ddad_batch.h'}      # and after those
+SWEEP_HEADERS = {'SWEEP_SIGNATURES': 'gedepth_sweep.h'}      # and after those
 GE_F32, GE_BF16 = 0, 1
 GE_COLORIZE_VMIN_DATA, GE_COLORIZE_VMAX_DATA, GE_COLORIZE_EQUAL = 1, 2, 4      # ge_depth_colorize flags
 
@@ -72,7 +75,7 @@ def parse_header(text):
 
 
 for _table, _header in {**HEADERS, **EXTRA_HEADERS, **SCENE_HEADERS, **STRATA_HEADERS, **NECK_HEADERS, **ERROR_HEADERS, **ACCUM_HEADERS,
-                        **DDAD_BATCH_HEADERS}.items():          # SIGNATURES, EVAL_SIGNATURES, ...: name -> (restype, argtypes)
+                        **DDAD_BATCH_HEADERS, **SWEEP_HEADERS}.items():          # SIGNATURES, EVAL_SIGNATURES, ...: name -> (restype, argtypes)
     with open(os.path.join(os.path.dirname(_HERE), 'include', _header)) as _fh:
         globals()[_table] = parse_header(_fh.read())
 
@@ -93,7 +96,7 @@ def lib():
                 f'Run gedepth_amd/csrc/build.sh (hipcc --offload-arch=gfx950). There is no CPU/eager fallback.')
         handle = ctypes.CDLL(LIB_PATH)
         for table in (*HEADERS, *EXTRA_HEADERS, *SCENE_HEADERS, *STRATA_HEADERS, *NECK_HEADERS, *ERROR_HEADERS, *ACCUM_HEADERS,
-                      *DDAD_BATCH_HEADERS):
+                      *DDAD_BATCH_HEADERS, *SWEEP_HEADERS):
             for name, (res, args) in globals()[table].items():
                 fn = getattr(handle, name)   # AttributeError here == ABI mismatch: fail loudly
                 fn.restype, fn.argtypes = res, args

@@ -2135,3 +2135,7 @@ from .error_kernels import error_accumulate, error_accumulate_batch, error_image
 # --------------------------------------------------------------------- batched DDAD inference / evaluation (csrc/infer.hip,
 # csrc/eval.hip, include/gedepth_ddad_batch.h)
 from .ddad_batch_kernels import depth_metric_sums_resized_batch, infer_front_ddad_batch  # noqa: E402,F401
+
+# --------------------------------------------------------------------- the prior sweep's front end (csrc/infer.hip,
+# include/gedepth_sweep.h)
+from .sweep_kernels import infer_front_sweep  # noqa: E402,F401

@@ -41,6 +41,13 @@ error picture per test image, ``DIR/<name in the split, '/' as '_'>`` — every 
 frame — and for the split ``DIR/summary.npz`` (per-pixel ``sum`` and ``count`` of the abs-rel error, ``tau``, ``rect``, ``frames``) and
 ``DIR/mean_abs_rel.png``; the mean per eight image rows is printed.  ``--error-no-pictures`` keeps the split's summary only.  The metrics
 printed are those without ``--error-dir``.
+
+``--prior-sweep`` (with ``--eval --device-eval``; KITTI protocol, one device, ``--eval-batch 1``, without ``--strata`` / ``--error-dir`` /
+``--ground-dir``) evaluates every frame under perturbed ground priors in one forward (include/gedepth_sweep.h): the calibrated plane, the
+plane of a camera pitched by each ``--sweep-pitch D`` degrees (default -1 -0.5 0.5 1; positive brings the ground closer), of a camera
+``--sweep-height S`` times as high (default none) and, unless ``--sweep-no-drop``, no prior at all; at most eight variants.  The usual
+summary is the baseline's; the table after it has one line per variant with its differences to the baseline.  ``--sweep-out FILE.npz``
+stores ``rows`` (N, V, 10), ``names``, ``pitch_deg``, ``height_scale`` and ``cam_height``.
 """
 import argparse
 import os
@@ -85,6 +92,13 @@ def parse_args(argv=None):
     p.add_argument('--error-tau', type=float, default=0.05, help='the abs-rel error at the middle of the ten colour bands, in (0, 1]')
     p.add_argument('--error-radius', type=int, default=1, help='a return is drawn 2 R + 1 pixels wide, R in 0 .. 3')
     p.add_argument('--error-no-pictures', action='store_true', help='the split\'s summary only, no picture per image')
+    p.add_argument('--prior-sweep', action='store_true',
+                   help='with --eval --device-eval (KITTI protocol, one device): every frame under perturbed ground priors in one forward')
+    p.add_argument('--sweep-pitch', nargs='+', type=float, default=None, metavar='D',
+                   help='the pitch errors in degrees (default: -1 -0.5 0.5 1); positive brings the ground closer')
+    p.add_argument('--sweep-height', nargs='+', type=float, default=None, metavar='S', help='camera-height scales in [0.5, 2] (default: none)')
+    p.add_argument('--sweep-no-drop', action='store_true', help='leave out the variant without a prior')
+    p.add_argument('--sweep-out', help='.npz file that receives rows (N, V, 10), names, pitch_deg, height_scale and cam_height')
     p.add_argument('--out', help='output result file in pickle format (.pkl / .pickle), written by rank 0')
     p.add_argument('--format-only', action='store_true',
                    help='format the results (dataset.format_results) without evaluating; with --show-dir the raw maps are saved as .npy')
@@ -135,6 +149,21 @@ def parse_args(argv=None):
         if not (args.eval and args.device_eval):
             raise ValueError('--error-dir needs --eval and --device-eval: the error maps are reduced by the device evaluation loop')
         error_maps(args)                                               # ValueError for a tau or radius outside its range
+    if not args.prior_sweep:
+        if args.sweep_pitch is not None or args.sweep_height is not None or args.sweep_no_drop or args.sweep_out:
+            raise ValueError('--sweep-pitch / --sweep-height / --sweep-no-drop / --sweep-out need --prior-sweep')
+    else:
+        if not (args.eval and args.device_eval):
+            raise ValueError('--prior-sweep needs --eval and --device-eval: the variants are the slots of the device evaluation loop\'s engine')
+        clash = [flag for flag, on in (('--eval-batch', args.eval_batch != 1), ('--strata', args.strata is not None),
+                                       ('--error-dir', args.error_dir), ('--ground-dir', args.ground_dir),
+                                       ('--launcher pytorch', args.launcher == 'pytorch')) if on]
+        if clash:
+            raise ValueError(f'--prior-sweep cannot be combined with {" / ".join(clash)}: the sweep runs alone, on one device (its baseline '
+                             'row is the ordinary result)')
+        if args.sweep_out is not None and not args.sweep_out.endswith('.npz'):
+            raise ValueError('--sweep-out must be an .npz file')
+        prior_sweep(args)                                              # ValueError for a pitch or scale outside its range
     if args.eval_batch != 1 and args.ground_dir:
         raise ValueError('--eval-batch > 1 cannot be combined with --ground-dir: the ground maps come from the single-frame engine')
     if args.ground_dir and args.eval and not args.device_eval:
@@ -161,6 +190,24 @@ def report_strata(args, dataset, spec, rows):
         os.makedirs(osp.dirname(osp.abspath(args.strata_out)), exist_ok=True)
         np.savez(args.strata_out, rows=rows, names=np.array(spec.names(dataset.min_depth, dataset.max_depth)), edges=np.array(spec.edges))
         print(f'writing strata sums to {args.strata_out}')
+
+
+def prior_sweep(args):
+    """The ``PriorSweep`` of ``--prior-sweep`` and its companions, or None."""
+    if not args.prior_sweep:
+        return None
+    from gedepth_amd.depth.core import PriorSweep
+    return PriorSweep((-1.0, -0.5, 0.5, 1.0) if args.sweep_pitch is None else args.sweep_pitch, args.sweep_height or (), not args.sweep_no_drop)
+
+
+def report_sweep(args, dataset, sweep, rows):
+    """The table after the usual summary, and ``--sweep-out``."""
+    dataset.evaluate_sweep(rows, sweep)
+    if args.sweep_out:
+        os.makedirs(osp.dirname(osp.abspath(args.sweep_out)), exist_ok=True)
+        np.savez(args.sweep_out, rows=rows, names=np.array(sweep.names), pitch_deg=np.array(sweep.pitch_deg),
+                 height_scale=np.array(sweep.height_scale), cam_height=np.float64(sweep.cam_height))
+        print(f'writing prior-sweep sums to {args.sweep_out}')
 
 
 def error_maps(args):
@@ -203,13 +250,14 @@ def run_dataset(args, cfg):
     model = model.cuda().eval()
     model.cfg = cfg
     test = multi_gpu_test if distributed else single_gpu_test
-    spec, rows, errors = strata_spec(args), None, error_maps(args)
+    spec, rows, errors, sweep = strata_spec(args), None, error_maps(args), prior_sweep(args)
+    own = {} if sweep is None else dict(prior_sweep=sweep)               # one device only (parse_args refuses it with --launcher pytorch)
     with torch.autocast('cuda', dtype=torch.bfloat16, enabled=args.bf16):
         results = test(model, loader, pre_eval=args.eval is not None, format_only=args.format_only, format_args=eval_kwargs,
                        show=args.show, out_dir=args.show_dir, device_eval=args.device_eval, ply_dir=args.ply_dir,
-                       ground_dir=args.ground_dir, eval_batch=args.eval_batch, scene_dir=args.scene_dir, strata=spec, errors=errors)
+                       ground_dir=args.ground_dir, eval_batch=args.eval_batch, scene_dir=args.scene_dir, strata=spec, errors=errors, **own)
     rank, _ = get_dist_info()
-    if spec is not None and results is not None:
+    if (spec is not None or sweep is not None) and results is not None:
         results, rows = results
     if rank == 0:
         if args.out:
@@ -219,6 +267,8 @@ def run_dataset(args, cfg):
                 pickle.dump(results, fh)
         if args.eval:
             dataset.evaluate(results, args.eval, **eval_kwargs)
+            if sweep is not None:
+                report_sweep(args, dataset, sweep, rows)
             if spec is not None:
                 report_strata(args, dataset, spec, rows)
             if errors is not None:
@@ -248,13 +298,15 @@ def main():
         dataset = build_dataset(cfg.data.test, dict(test_mode=True))
         loader = build_dataloader(dataset, 1, cfg.data.workers_per_gpu, dist=False, shuffle=False)
         model.cfg = cfg
-        spec, errors = strata_spec(args), error_maps(args)
+        spec, errors, sweep = strata_spec(args), error_maps(args), prior_sweep(args)
         with torch.autocast('cuda', dtype=torch.bfloat16, enabled=args.bf16):
             results = single_gpu_test(model, loader, pre_eval=True, device_eval=args.device_eval, eval_batch=args.eval_batch, strata=spec,
-                                      errors=errors)
-        if spec is not None:
+                                      errors=errors, prior_sweep=sweep)
+        if spec is not None or sweep is not None:
             results, rows = results
         dataset.evaluate(results)
+        if sweep is not None:
+            report_sweep(args, dataset, sweep, rows)
         if spec is not None:
             report_strata(args, dataset, spec, rows)
         if errors is not None:
