@@ -1,43 +1,21 @@
-"""Depth for several KITTI frames per forward: ``BatchDepthInferencer``, the engine of apis/inference.py with F <= 8 frame slots.
+"""Depth for several frames per forward: the F-slot faces of the frame engine (apis/engine.py has the engine and its steps).
 
-Per batch of n <= F frames, on the engine's stream:
-
-  1. n uploads, each slot through its own pinned buffer (``PinnedUpload``), non-blocking;
-  2. ONE ``ge_infer_front_batch`` (csrc/infer.hip) writes the flip views of the n frames, frame-major, into the first ``views * n``
-     images of the static ``(views * F, 5, 352, 1216)`` input; the frames may differ in size (the KITTI days do), each has its own crop
-     offsets and ground depth.  Outside the graph: only its arguments change from batch to batch;
-  3. ``model.encode_decode`` runs all ``views * F`` images as one forward and ONE ``ge_tta_merge_batch`` merges the F pairs into the
-     static ``(F, 1, 352, 1216)`` output (a one-view config: a copy) — captured in a hipGraph after ``WARMUP`` eager batches;
-  4. the first n maps go to the host, or stay on the device (``to_host=False``).
-
-A last batch of n < F frames fills the first n slots; the others keep what they held — zeros (the input is allocated with zeros) or an
-older frame — and the forward still runs on all F slots.  Only the n maps are ever returned: in eval mode no operation of the model
-crosses samples (BatchNorm uses its running statistics, attention windows and the deformable attention stay inside a sample), so what
-slot f holds does not reach another slot's map.
+``BatchDepthInferencer`` (KITTI protocol): ``batch(imgs)`` runs n <= F frames, which may differ in size; ``sweep`` fills the slots with
+ONE frame under V <= F ground priors instead (include/gedepth_sweep.h: a global pitch, a height scale, the prior removed), on the same
+captured graph.  ``BatchDDADInferencer`` (DDAD protocol; one view per frame, no merge): the slots of a batch may hold different cameras,
+each with its own ground depth and its own entry of ``static_height``.  ``run`` of either takes any number of frames in batches of F.
+``inference_depther(batch > 1)`` stays refused for a DDAD config (``check_batch``): files to maps in batches is
+``BatchDDADInferencer.run``, the loop's route is ``single_gpu_test(device_eval=True, eval_batch=F)``.  ``ground_maps``, ``points``,
+``scene_points`` and ``error_map`` stay single-frame (``DepthInferencer``).
 
 ``decode_ahead`` is the host side: a pool of at most ``DECODE_WORKERS`` threads decodes the next batch's PNGs (PIL releases the GIL while
-inflating) while the device computes the current one.  ``points`` and ``ground_maps`` stay single-frame (``DepthInferencer``).
-
-``BatchDepthInferencer.sweep`` fills the slots with ONE frame under V <= F ground priors instead (include/gedepth_sweep.h: a global pitch,
-a height scale, the prior removed): one upload and one ``ge_infer_front_sweep`` launch in place of step 1 and 2, then steps 3 and 4
-unchanged, on the same captured graph.
-
-``BatchDDADInferencer`` is the same engine for the DDAD protocol (one view per frame, no merge): n uploads, ONE
-``ge_infer_front_ddad_batch`` into the first n images of the static ``(F, 5, Hd, Wd)`` input, the n cameras' heights into the static
-``(F,)`` tensor the adaptive ground embedding reads (one small copy, outside the graph), one captured forward over all F slots.  The slots
-of a batch may hold different cameras.  ``inference_depther(batch > 1)`` stays refused for a DDAD config (``check_batch``): files to
-maps in batches is ``BatchDDADInferencer.run``, the loop's route is ``single_gpu_test(device_eval=True, eval_batch=F)``."""
+inflating) while the device computes the current one."""
 from concurrent.futures import ThreadPoolExecutor
 
-import numpy as np
-import torch
-from PIL import Image
-
-from ... import kernels as K
 from ...batch_kernels import BATCH_MAX
-from ..utils.pinned import PinnedUpload
-from ..datasets.pipelines import loading    # _DDAD_CAMERA_HEIGHT is read through the module at every use, as apis/inference.py does
-from .inference import DepthInferencer, _config_of, _ddad_camera, _decode, _per_frame
+from ...sweep_kernels import variant_table
+from ..datasets.pipelines import loading    # _DDAD_CAMERA_HEIGHT is read through the module at every use, as apis/engine.py does
+from .engine import FrameEngine, _check_count, _config_of, _ddad_camera, _decode, _paths_of, _per_frame, check_ddad_frames
 
 __all__ = ['BatchDepthInferencer', 'BatchDDADInferencer', 'check_batch', 'check_ddad_batch', 'decode_ahead', 'DECODE_WORKERS']
 
@@ -55,6 +33,12 @@ def check_batch(batch, spec=None, what='batch', ddad=False):
                                   f'run one at a time ({what}=1), or in batches through BatchDDADInferencer.run and '
                                   'single_gpu_test(device_eval=True, eval_batch=F)')
     return batch
+
+
+def check_ddad_batch(spec, slots, sizes, pes, cameras, paths, frame_size=None):
+    """The argument errors of one DDAD batch, host work only -> ``(cameras, the frames' one (H, W))``: the DDAD front's own check
+    (``engine.check_ddad_frames``) in a batch's words."""
+    return check_ddad_frames(spec, slots, sizes, pes, cameras, paths, frame_size)
 
 
 def decode_ahead(jobs, size, workers=DECODE_WORKERS):
@@ -77,34 +61,25 @@ def decode_ahead(jobs, size, workers=DECODE_WORKERS):
                 raise
 
 
-def frame_size(img):
-    """(H, W) of a frame without decoding it: the PNG header of a path, the shape of an array."""
-    if isinstance(img, str):
-        with Image.open(img) as im:
-            return im.size[1], im.size[0]
-    return tuple(np.shape(img)[:2])
-
-
-class _BatchEngine(DepthInferencer):
-    """What the two engines of ``frames`` = F slots share: the capture key, the head and the tail of ``batch``, the chunks of ``run``
-    and what ``reset`` clears.  The front-end calls, the forward and the order of work on the engine's stream are each engine's own."""
-
-    # plain attributes (the base class derives them from its one frame): a batch keeps lists of its own under these names
-    last_frames = last_ground_depths = None
+class _BatchEngine(FrameEngine):
+    """What the two faces with ``frames`` = F slots share: the capture key, ``batch`` behind its argument lists, its tail and the chunks
+    of ``run``."""
 
     def _key(self, ground=False):
         return super()._key(ground) + ('batch', self.frames)
 
-    def _head(self, imgs, paths):
-        """The frame count of ``batch(imgs)`` against the slots -> ``(n, paths, by default the images that are paths)``."""
-        n = len(imgs)
-        if not 1 <= n <= self.frames:
-            raise ValueError(f'{n} frames for an engine of {self.frames} slots')
-        return n, paths if paths is not None else [i if isinstance(i, str) else None for i in imgs]
+    def _batch(self, imgs, paths, pes, cameras, graph, to_host, **own):
+        """n <= F frames through the front's check (every argument error before any device work) and ``_submit``."""
+        paths = paths if paths is not None else _paths_of(imgs)
+        bgrs = [_decode(i) for i in imgs]
+        n, sizes = len(bgrs), [b.shape[:2] for b in bgrs]
+        cams, oris = self.front.check(self, sizes, paths, cameras, pes)
+        pes = pes if pes is not None else [None] * n
+        return self._submit(n, lambda: self.front.fill(self, bgrs, paths, cams, pes, **own), self._metas(paths, sizes, oris), graph,
+                            lambda: self._maps(n, to_host))
 
     def _maps(self, n, to_host):
-        """The tail of ``batch``, on the engine's stream behind ``_run``: n fresh host arrays, or the view ``static_out[:n]``."""
-        self.last_n = n
+        """The tail of a call, on the engine's stream behind ``_run``: n fresh host arrays, or the view ``static_out[:n]``."""
         if not to_host:
             return self.static_out[:n]
         host = self.static_out[:n].cpu().numpy()                               # synchronises the engine's stream
@@ -115,38 +90,17 @@ class _BatchEngine(DepthInferencer):
         for k, bgrs in enumerate(decode_ahead([(lambda i=i: _decode(i)) for i in imgs], self.frames)):
             yield slice(k * self.frames, k * self.frames + len(bgrs)), bgrs
 
-    def reset(self):
-        super().reset()
-        self.last_n = 0                              # the frame count of the last batch
-        self.last_ground_depths = None               # KITTI: the raw (H, W) f32 ground depths the last batch's front end was given
-        self.last_frames = None                      # KITTI: [(device uint8 BGR frame, top, left)] of the last batch, for the error images
-
 
 class BatchDepthInferencer(_BatchEngine):
-    """The flip-TTA engine with ``frames`` = F slots (module docstring); KITTI protocol.  ``batch(imgs)`` runs n <= F frames.  Captures are
-    keyed as ``DepthInferencer``'s plus ``('batch', F)``; the capture itself (``_run``) and the contract that parameters are updated IN PLACE
-    (a replay then sees the new values: ``FusedAdamW`` updates its arena in place) are the base class's."""
+    """The flip-TTA engine with ``frames`` = F slots; KITTI protocol.  ``batch(imgs)`` runs n <= F frames, ``sweep`` one frame under V <= F
+    ground priors.  Captures are keyed as ``DepthInferencer``'s plus ``('batch', F)``."""
 
     def __init__(self, model, frames, bf16=False, config=None):
         config = config or _config_of(model)
-        self.frames = check_batch(frames, config[0], 'frames')
-        super().__init__(model, bf16, config)
-        if self.ddad:
+        check_batch(frames, config[0], 'frames')
+        if config[0]['protocol'] == 'ddad':
             raise NotImplementedError('BatchDepthInferencer with a DDAD config: the batched engine implements the KITTI protocol only')
-        s, F = self.spec, self.frames
-        # zeros: a slot no frame has filled yet still holds finite values for the forward that runs over all slots
-        self.static_in = torch.zeros(s['views'] * F, 5, s['height'], s['width'], device=self.device, dtype=torch.float32)
-        self.static_out = torch.empty(F, 1, s['height'], s['width'], device=self.device, dtype=torch.float32)
-        self._stagings = [PinnedUpload() for _ in range(F)]
-
-    def _body(self, metas, ground=False):
-        with torch.no_grad(), torch.autocast('cuda', dtype=torch.bfloat16, enabled=self.bf16):
-            pred = self.model.encode_decode(self.static_in, metas, rescale=True)
-        pred = pred.float().contiguous()
-        if self.spec['views'] == 2:
-            K.tta_merge_batch(pred, self.static_out)          # all F slots: the captured launch does not depend on n
-        else:
-            self.static_out.copy_(pred)
+        super().__init__(model, frames, bf16, config)
 
     def _single(self, *a, **kw):
         raise NotImplementedError('a BatchDepthInferencer runs batch(imgs); single frames, points, scene_points, error_map and ground_maps go through the '
@@ -159,28 +113,7 @@ class BatchDepthInferencer(_BatchEngine):
         ``paths`` names their files, for the ground depth of the test tree); ``pes``: one raw ground depth per frame or None.  Returns a
         list of n fresh (1, 352, 1216) float32 host arrays, or with ``to_host=False`` the view ``static_out[:n]`` of the static device
         buffer, without synchronising: valid until the next call, ordered on ``self.stream``."""
-        (n, paths), s = self._head(imgs, paths), self.spec
-        pes = pes if pes is not None else [None] * n
-        bgrs = [_decode(i) for i in imgs]
-        for b in bgrs:
-            self.front.frame(self, b.shape[0], b.shape[1], None, None)           # a frame smaller than the crop, before any device work
-        metas = [m for b, p in zip(bgrs, paths) for m in self._metas(p, b.shape[:2], (s['height'], s['width'], 5))]
-        metas += metas[-s['views']:] * (self.frames - n)
-        cur = torch.cuda.current_stream(self.device)
-        self.stream.wait_stream(cur)
-        with torch.cuda.stream(self.stream):
-            tops = [int(b.shape[0] - s['height']) for b in bgrs]                  # KBCrop
-            lefts = [int((b.shape[1] - s['width']) / 2) for b in bgrs]
-            raws = [self.ground_depth(b.shape[0], b.shape[1], p, pe, calib, cam_height) for b, p, pe in zip(bgrs, paths, pes)]
-            self.last_ground_depths = raws                    # kept for the stratified evaluation, as last_ground_depth is
-            devs = [up(b, self.device) for up, b in zip(self._stagings, bgrs)]
-            K.infer_front_batch(devs, raws, self.static_in, tops, lefts, s['mean'], s['std'], s['views'], s['to_rgb'], s['pe_max'],
-                                s['depth_scale'])
-            self.last_frames = list(zip(devs, tops, lefts))   # kept for the error images, as last_frame is
-            self._run(self._key(), graph, lambda: self._body(metas))
-            out = self._maps(n, to_host)
-        cur.wait_stream(self.stream)
-        return out
+        return self._batch(imgs, paths, pes, None, graph, to_host, calib=calib, cam_height=cam_height)
 
     def sweep(self, img, variants, pe=None, calib=None, cam_height=1.65, graph=True, to_host=True, path=None):
         """ONE frame under V = ``len(variants)`` <= F ground priors -> its V maps, in the variants' order.  ``variants``: a
@@ -189,89 +122,35 @@ class BatchDepthInferencer(_BatchEngine):
         ``ge_infer_front_sweep`` launch fill the first ``views * V`` images of ``static_in``; the forward is ``batch``'s, under its
         key and on its static buffers, so both share one captured graph.  Slots from V on keep what they held.  Returns as ``batch``;
         ``last_ground_depths`` / ``last_frames`` hold the unperturbed plane / the uploaded frame V times."""
-        from ...sweep_kernels import variant_table
         rows = variants.table() if hasattr(variants, 'table') else list(variants)
-        V, s = len(variant_table(rows)), self.spec                              # the rows' argument errors, before any device work
-        if V > self.frames:
-            raise ValueError(f'{V} variants for an engine of {self.frames} slots')
-        path = path if path is not None else (img if isinstance(img, str) else None)
+        V = len(variant_table(rows))                                            # the rows' argument errors, before any device work
+        _check_count(V, self.frames, 'variants')
+        paths = [path if path is not None else (img if isinstance(img, str) else None)]
         bgr = _decode(img)
-        H, W = bgr.shape[:2]
-        self.front.frame(self, H, W, None, None)                                  # a frame smaller than the crop, before any device work
-        metas = self._metas(path, (H, W), (s['height'], s['width'], 5)) * self.frames
-        cur = torch.cuda.current_stream(self.device)
-        self.stream.wait_stream(cur)
-        with torch.cuda.stream(self.stream):
-            top, left = int(H - s['height']), int((W - s['width']) / 2)          # KBCrop
-            raw = self.ground_depth(H, W, path, pe, calib, cam_height)
-            dev = self._stagings[0](bgr, self.device)
-            K.infer_front_sweep(dev, raw, rows, self.static_in, top, left, s['mean'], s['std'], s['views'], s['to_rgb'], s['pe_max'],
-                                s['depth_scale'])
-            self.last_ground_depths, self.last_frames = [raw] * V, [(dev, top, left)] * V
-            self._run(self._key(), graph, lambda: self._body(metas))
-            out = self._maps(V, to_host)
-        cur.wait_stream(self.stream)
-        return out
+        sizes = [bgr.shape[:2]]
+        _, oris = self.front.check(self, sizes, paths, None, None)                # a frame smaller than the crop, before any device work
+        return self._submit(V, lambda: self.front.fill(self, [bgr], paths, None, [pe], calib, cam_height, rows),
+                            self._metas(paths, sizes, oris) * V, graph, lambda: self._maps(V, to_host))
 
     def run(self, imgs, pes=None, calib=None, cam_height=1.65, graph=True):
         """Any number of frames, in batches of F with the next batch decoding ahead -> one host map per frame, in order."""
         pes = pes if pes is not None else [None] * len(imgs)
         out = []
         for part, bgrs in self._chunks(imgs):
-            out += self.batch(bgrs, pes[part], calib, cam_height, graph, paths=[i if isinstance(i, str) else None for i in imgs[part]])
+            out += self.batch(bgrs, pes[part], calib, cam_height, graph, paths=_paths_of(imgs[part]))
         return out
 
 
-def check_ddad_batch(spec, slots, sizes, pes, cameras, paths, frame_size=None):
-    """The argument errors of one DDAD batch, host work only -> ``(cameras, the frames' one (H, W))``.  ``sizes``: the frames' (H, W);
-    ``pes`` / ``cameras`` / ``paths``: None or one entry per frame; ``frame_size``: what the engine has taken so far, or None."""
-    n = len(sizes)
-    if not 1 <= n <= slots:
-        raise ValueError(f'{n} frames for an engine of {slots} slots')
-    for name, v in (('ground depths', pes), ('cameras', cameras), ('paths', paths)):
-        if v is not None and len(v) != n:
-            raise ValueError(f'{len(v)} {name} for {n} frames')
-    cameras = cameras if cameras is not None else [None] * n
-    paths = paths if paths is not None else [None] * n
-    cams = [_ddad_camera(c, p) for c, p in zip(cameras, paths)]           # ValueError for a camera without a known height
-    if any(c is None for c in cams):
-        raise ValueError(f'no camera for frame {cams.index(None)}: pass cameras= (out of {", ".join(sorted(loading._DDAD_CAMERA_HEIGHT))}) or '
-                         'image paths whose parent directory is the camera name')
-    for H, W in sizes:
-        if H < spec['height'] or W < spec['width']:
-            raise ValueError(f'frame {(H, W)} is smaller than DDADResize\'s shape {(spec["height"], spec["width"])}')
-        if frame_size is not None and frame_size != (H, W):
-            raise ValueError(f'frame {(H, W)}: this engine takes frames of {frame_size} (reset() to change)')
-        frame_size = (H, W)
-    return cams, frame_size
-
-
 class BatchDDADInferencer(_BatchEngine):
-    """The DDAD engine with ``frames`` = F slots (module docstring).  ``batch(imgs)`` runs n <= F frames, which may come from different
-    cameras: each slot has its own ground depth and its own entry of ``static_height``.  Captures are keyed as ``DepthInferencer``'s plus
-    ``('batch', F)``; the capture itself and the in-place contract on the parameters are the base class's, and so is the rule that one
-    engine takes frames of one size."""
+    """The DDAD engine with ``frames`` = F slots.  ``batch(imgs)`` runs n <= F frames, which may come from different cameras.  Captures
+    are keyed as ``DepthInferencer``'s plus ``('batch', F)``; one engine takes frames of one size."""
 
     def __init__(self, model, frames, bf16=False, config=None):
         config = config or _config_of(model)
-        self.frames = check_batch(frames, what='frames')
+        check_batch(frames, what='frames')
         if config[0]['protocol'] != 'ddad':
             raise NotImplementedError('BatchDDADInferencer with a KITTI config: the KITTI protocol runs in a BatchDepthInferencer')
-        super().__init__(model, bf16, config)
-        s, F = self.spec, self.frames
-        # zeros, and a camera's height: a slot no frame has filled yet still holds finite values for the forward that runs over all slots
-        self.static_in = torch.zeros(F, 5, s['height'], s['width'], device=self.device, dtype=torch.float32)
-        self.static_out = torch.empty(F, 1, s['height'], s['width'], device=self.device, dtype=torch.float32)
-        self._heights = [float(min(loading._DDAD_CAMERA_HEIGHT.values()))] * F
-        self.static_height = torch.tensor(self._heights, device=self.device, dtype=torch.float32)
-        self._forward_kw = dict(height=self.static_height)
-        self._heights_host, self._heights_done = torch.empty(F, dtype=torch.float32, pin_memory=True), None
-        self._stagings = [PinnedUpload() for _ in range(F)]
-
-    def _body(self, metas, ground=False):
-        with torch.no_grad(), torch.autocast('cuda', dtype=torch.bfloat16, enabled=self.bf16):
-            pred = self.model.encode_decode(self.static_in, metas, rescale=True, **self._forward_kw)
-        self.static_out.copy_(pred)                           # all F slots: the captured forward does not depend on n
+        super().__init__(model, frames, bf16, config)
 
     def _single(self, *a, **kw):
         raise NotImplementedError('a BatchDDADInferencer runs batch(imgs); single frames and ground_maps go through the DepthInferencer of '
@@ -286,37 +165,7 @@ class BatchDDADInferencer(_BatchEngine):
         list of n fresh (1, Hd, Wd) float32 host arrays, or with ``to_host=False`` the view ``static_out[:n]`` of the static device
         buffer, without synchronising: valid until the next call, ordered on ``self.stream``.  Every argument error is raised before any
         device work."""
-        (n, paths), s = self._head(imgs, paths), self.spec
-        if len(paths) != n:
-            raise ValueError(f'{len(paths)} paths for {n} frames')
-        bgrs = [_decode(i) for i in imgs]
-        cams, self.frame_size = check_ddad_batch(s, self.frames, [b.shape[:2] for b in bgrs], pes, cameras, paths, self.frame_size)
-        pes = pes if pes is not None else [None] * n
-        metas = [m for b, p in zip(bgrs, paths) for m in self._metas(p, b.shape[:2], tuple(b.shape[:2]) + (5,))]
-        metas += metas[-1:] * (self.frames - n)
-        self._heights[:n] = [float(loading._DDAD_CAMERA_HEIGHT[c]) for c in cams]      # the other slots keep the height they had
-        cur = torch.cuda.current_stream(self.device)
-        self.stream.wait_stream(cur)
-        with torch.cuda.stream(self.stream):
-            raws = [self.ground_depth_ddad(c, b.shape[0], b.shape[1], pe) for c, b, pe in zip(cams, bgrs, pes)]
-            devs = [up(b, self.device) for up, b in zip(self._stagings, bgrs)]
-            K.infer_front_ddad_batch(devs, raws, self.static_in, s['mean'], s['std'], s['to_rgb'], s['pe_max'], s['depth_scale'])
-            # one small copy into the tensor the captured forward reads through its device pointer; the order of PinnedUpload
-            if self._heights_done is not None:
-                self._heights_done.synchronize()
-            self._heights_host.numpy()[...] = self._heights
-            self.static_height.copy_(self._heights_host, non_blocking=True)
-            self._heights_done = torch.cuda.Event()
-            self._heights_done.record()
-            self._run(self._key(), graph, lambda: self._body(metas))
-            self.last_cameras = cams
-            out = self._maps(n, to_host)
-        cur.wait_stream(self.stream)
-        return out
-
-    def reset(self):
-        super().reset()
-        self.last_cameras = None                     # the cameras of the last batch
+        return self._batch(imgs, paths, pes, cameras, graph, to_host)
 
     def run(self, imgs, pes=None, cameras=None, graph=True):
         """Any number of frames, in batches of F with the next batch decoding ahead -> one host map per frame, in order: the files-to-maps
@@ -325,7 +174,7 @@ class BatchDDADInferencer(_BatchEngine):
         imgs = imgs if isinstance(imgs, list) else [imgs]
         pes = _per_frame(pes, len(imgs), '{n} ground-depth maps for {m} frames')
         cameras = _per_frame(cameras, len(imgs), '{n} cameras for {m} frames')
-        paths = [i if isinstance(i, str) else None for i in imgs]
+        paths = _paths_of(imgs)
         for c, p in zip(cameras, paths):                                          # every frame's camera, before the first batch runs
             if _ddad_camera(c, p) is None:
                 raise ValueError(f'no camera for a frame: pass cameras= (out of {", ".join(sorted(loading._DDAD_CAMERA_HEIGHT))}) or image '

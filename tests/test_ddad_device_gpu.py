@@ -456,6 +456,39 @@ def test_graph_replay_follows_the_camera_height(toy, monkeypatch):
     model.__dict__.pop('_ge_inferencers', None)
 
 
+def test_back_to_back_frames_each_get_their_own_camera_height(toy, monkeypatch):
+    """The camera height travels through one reused pinned buffer and a non-blocking copy: six replayed frames, alternating two cameras,
+    queued without any host synchronisation between them.  Each call's map (and height) is cloned on the caller's stream right behind
+    it and must equal, bit for bit, the map the same engine gives that frame with ``to_host=True``.  A pinned buffer overwritten before
+    its copy has run would give a frame the other camera's height, which moves the map by more than 100 times the replay bound
+    (test_graph_replay_follows_the_camera_height); bit equality needs the reproducible convolutions, as there."""
+    from gedepth_amd.depth.apis.inference import DepthInferencer
+    from gedepth_amd.depth.datasets.pipelines import loading
+    heights = {'CAMERA_01': 1.2, 'CAMERA_05': 2.2, 'CAMERA_06': 1.53, 'CAMERA_09': 1.53}
+    monkeypatch.setattr(loading, '_DDAD_CAMERA_HEIGHT', heights)
+    model, ds, _ = toy
+    frames = [(ds.img_infos[0]['filename'], 'CAMERA_01'), (ds.img_infos[2]['filename'], 'CAMERA_05')]
+    order = [0, 1, 0, 1, 0, 1]
+    with _reproducible_convolutions():
+        eng = DepthInferencer(model)
+        for _ in range(eng.WARMUP + 1):
+            eng(frames[0][0])
+        assert eng.captures == 1
+        want = [eng(f) for f, _ in frames]                                              # replays; to_host=True synchronises
+        maps, seen = [], []
+        for k in order:
+            out = eng(frames[k][0], to_host=False)
+            assert out is eng.static_out
+            maps.append(out.clone())
+            seen.append(eng.static_height.clone())
+        torch.cuda.synchronize()
+        assert eng.captures == 1 and eng.replays == 1 + len(want) + len(order)
+    assert not np.array_equal(want[0], want[1])
+    for call, (k, m, h) in enumerate(zip(order, maps, seen)):
+        assert h.cpu().numpy().tolist() == [np.float32(heights[frames[k][1]])], f'call {call}: the height of {frames[k][1]}'
+        assert np.array_equal(m.cpu().numpy(), want[k]), f'call {call}: not the map of its own frame and camera'
+
+
 def _host_counted(ds, i):
     gt = np.load(ds.img_infos[i]['ann']['depth_map'])['depth'].astype(np.float32)
     return gt, D.mask_of(gt, *LIMITS)
